@@ -14,19 +14,24 @@ and compaction, correspondence RANSAC with 3-point Kabsch.  Synthetic inputs of 
 Multi-GPU: independent scene pairs are sharded across ranks, no data-path
 collective; one all_gather of the 4x4 poses (RCCL) closes the timed region.  Weak scaling.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), with
   roofline     -- the dominant kernel (int8 MFMA coarse pass): algorithmic operations 2*N*M*D per launch
-                  / average launch duration measured with HIP events on its stream, vs the dense int8
+                  / average launch duration measured with HIP events on its stream during the timed steps, vs the dense int8
                   MFMA peak (5 POP/s = 2 x the 2.5 PFLOP/s fp16 figure of MI355X_MICROARCH.md: the
                   32x32x32 i8 instruction has twice the k of 32x32x16 f16 at the same issue rate);
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+--full adds what takes runs of its own, outside the timed region:
   cpu_baseline -- the CPU oracle (oracle/, a port: faiss and Open3D are absent) timed on this
-                  box's host cores on a bounded sample of the same workload;
-  extra        -- outside the timed region: |T_gpu - T_oracle|_F of one pair ("pose delta vs ref"); C2_full_width / C2_sustained /
+                  box's host cores on a bounded sample of the same workload (--no-cpu-baseline: skipped);
+  roofline.single_stream, roofline.traffic measured in the run (two rocprofv3 --pmc subprocesses; --no-live-traffic: skipped);
+  extra        -- |T_gpu - T_oracle|_F of one pair ("pose delta vs ref"); C2_full_width / C2_sustained /
                   C2_lifted (the same timed-loop form with the full-width pass, over 200 steps, and on descriptors that look like
-                  lifted ViT features -- figures that do not rest on D.2's prunable noise); config C3 end to end (+ the ViT's
-                  roofline entry) and config C5 (+ its coarse kernel's roofline entry).
+                  lifted ViT features -- figures that do not rest on D.2's prunable noise); every stage alone; config C3 end to
+                  end (+ the ViT's roofline entry) and config C5 (+ its coarse kernel's roofline entry) (--no-extra: skipped).
 --pairs P (config C4): P independent scene pairs, pair p generated from seed 42 + p on rank p mod N and registered
 there; every rank prints its own rate to stderr before the gather.
+--dump-outputs DIR: rank 0 writes what its last timed registration returned as DIR/<name>.npy (float32 / float64, at most
+64 MB in all); the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -864,6 +869,8 @@ def run_c3_form(args, dev, rank, world):
     errs = [float(np.linalg.norm(all_poses[g].cpu().numpy() - np.eye(4))) for g in local_ids]   # the planted transform is the identity
     if rank == 0 and args.dump_poses:
         np.savez(args.dump_poses, poses=all_poses.cpu().numpy(), counts=all_counts.cpu().numpy())
+    if rank == 0 and args.dump_outputs:   # the last timed registration of this rank: its pose and correspondence count
+        write_outputs(args.dump_outputs, {"T": res_T[steps - 1].cpu().numpy(), "count": res_c[steps - 1].cpu().numpy()})
     if rank == 0:
         print(json.dumps({
             "metric": "registrations/sec from uint8 images (C3: ViT-S/14 on 6 x 1200x1600 + lifting + 20k<->200k registration)",
@@ -879,6 +886,42 @@ def run_c3_form(args, dev, rank, world):
             "per_rank_registrations_per_s": per_rank, "roofline": None, "cpu_baseline": None}), flush=True)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: what one run may write in all
+DUMP_SAMPLE_ROWS = 4096        # ... and, above it, the arrays whose rows are sampled (per-query / per-correspondence ones; not the pose)
+
+
+def step_outputs(out):
+    """What RegistrationPipeline.register returned to its caller, on the host; the per-correspondence arrays cut at `count`
+    (the rows behind it are left over from earlier registrations that used the same buffer set)."""
+    k = int(out["count"].item())
+    host = {name: out[name].cpu().numpy() for name in ("T", "fitness", "rmse", "best_hyp", "count", "idx", "sim")}
+    host.update(keep=out["keep"][:k].cpu().numpy(), corres=out["corres"][:k].cpu().numpy(), inlier_mask=out["mask"][:k].cpu().numpy())
+    return host
+
+
+def write_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """`--dump-outputs`: every array as DIR/<name>.npy, float32 / float64 kept, integers and flags widened to float64 (exact below
+    2^53).  Above `max_bytes` in all, the arrays of DUMP_SAMPLE_ROWS rows or more keep a fixed, seeded sample of their rows (the row numbers
+    in DIR/<name>_rows.npy; arrays of the same length keep the same rows)."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    if sum(a.nbytes for a in out.values()) > max_bytes:
+        long = [name for name, a in out.items() if a.ndim and a.shape[0] >= DUMP_SAMPLE_ROWS]
+        fixed = sum(a.nbytes for name, a in out.items() if name not in long)
+        per_row = sum(out[name].shape[0] * (out[name].nbytes // out[name].shape[0] + 8) for name in long)   # + 8: the row number
+        frac = 0.99 * (max_bytes - fixed - 256 * (2 * len(out) + 1)) / per_row    # (256: room for the .npy headers)
+        for name in long:
+            a = out[name]
+            pick = np.sort(np.random.default_rng(seed).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+            out[name], out[name + "_rows"] = a[pick], pick.astype(np.float64)
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+    return sorted(out)
 
 
 def main():
@@ -892,11 +935,16 @@ def main():
     ap.add_argument("--resident", type=int, default=RESIDENT_MAX,
                     help="distinct scene pairs kept in HBM per rank (338 MB each at C2 size); a rank with more pairs than that cycles through "
                          "its resident ones (pair j of the rank is registered on the data of its pair j mod resident)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C5 measurements reported under `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the CPU oracle baseline, the coarse kernel alone on one stream, its HBM traffic measured in this "
+                         "run, and the other configurations / variants / stage table under `extra` (off: the run does only what `value` needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 / C5 measurements reported under `extra`")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="roofline.traffic from the committed PMC passes under profiles/ instead of two rocprofv3 --pmc subprocesses of this run "
-                         "(--no-extra implies it; so does running bench.py itself under rocprofv3)")
+                    help="with --full: roofline.traffic from the committed PMC passes under profiles/ instead of two rocprofv3 --pmc subprocesses "
+                         "of this run (--no-extra implies it; so does running bench.py itself under rocprofv3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     # (--scan-rows / --map-rows: the spellings to use behind `python -m torch.distributed.run`, whose own parser takes "--n" / "--m" for
     # abbreviations of its options even behind the script's name)
     ap.add_argument("--n", "--scan-rows", dest="n", type=int, default=N_SCAN)
@@ -997,12 +1045,15 @@ def main():
     res_T = torch.empty((steps, 4, 4), dtype=torch.float64, device=dev)
     res_c = torch.empty((steps, 1), dtype=torch.int64, device=dev)
 
+    last = {}
+
     def register_pair(i):
         lib.vfm_prof_arm(events[i][0], events[i][1])
         out = step(i)
         with torch.cuda.stream(out["result_stream"]):  # snapshot the result on the producing stream
             res_T[i].copy_(out["T"])
             res_c[i].copy_(out["count"])
+        last["out"] = out
 
     # untimed warm-up: the sharding / gather path first, then the complete step
     vdist.gather_poses(torch.zeros((1, 4, 4), dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
@@ -1064,6 +1115,8 @@ def main():
         per_rank = [float(x) for x in rates.cpu()]
     print(f"[rank {rank}] {steps} registrations in {local_elapsed * 1e3:.1f} ms = {steps / local_elapsed:.1f} registrations/s "
           f"(before the gather)", file=sys.stderr, flush=True)
+    if rank == 0 and args.dump_outputs:   # (every stream is synchronised: the last step's buffer set is complete and untouched)
+        write_outputs(args.dump_outputs, step_outputs(last["out"]))
 
     ms = C.c_float()
     durs = []
@@ -1084,7 +1137,7 @@ def main():
     surv = pipe.last_rescans
     # the same kernel without the concurrent RANSAC stream (information only; not part of `value`)
     iso = []
-    if S == 2:
+    if S == 2 and args.full:
         pipe1 = RegistrationPipeline(n, m, d, n_iter=args.iters, device=dev, overlap_ransac=False,
                                      coarse=(("mx6-half" if getattr(pipe, "mx6_half", False) else "int8-half") if mode_half
                                              else "int8-top2" if mode_top2 else "int8" if mode_i8 else "fp16"))
@@ -1103,9 +1156,10 @@ def main():
 
     # sanity of the timed work: every pose of this rank must recover the planted transform of ITS pair
     local_ids = mine[:steps] if args.pairs > 0 else [rank + world * i for i in range(steps)]
-    errs = [float(np.linalg.norm(all_poses[g].cpu().numpy() - pairs[i % n_res]["T_gt"])) for i, g in enumerate(local_ids)]
+    poses_host = all_poses.cpu().numpy()
+    errs = [float(np.linalg.norm(poses_host[g] - pairs[i % n_res]["T_gt"])) for i, g in enumerate(local_ids)]
     ncorr = int(all_counts[local_ids[-1]].item())
-    T0 = all_poses[0].cpu().numpy()  # global pair 0 lives on rank 0
+    T0 = poses_host[0]  # global pair 0 lives on rank 0
     if rank == 0 and args.dump_poses:
         np.savez(args.dump_poses, poses=all_poses.cpu().numpy(), counts=all_counts.cpu().numpy())
 
@@ -1146,7 +1200,7 @@ def main():
                 break
         traffic_committed = traffic
         profiled = any(k.startswith(("ROCP_", "ROCPROF", "ROCTRACER_")) for k in os.environ)   # bench.py itself under rocprofv3: no nested profiler
-        if (world == 1 and not args.no_live_traffic and not args.no_extra and not profiled and (n, m, d) == (N_SCAN, N_MAP, DIM) and mode_i8):
+        if (args.full and world == 1 and not args.no_live_traffic and not args.no_extra and not profiled and (n, m, d) == (N_SCAN, N_MAP, DIM) and mode_i8):
             # ... and measured in THIS run: the same two passes on the same kernel, in subprocesses (this process holds no counters)
             live = live_traffic(records_kind)
             if live is not None:
@@ -1207,19 +1261,19 @@ def main():
                                         f"{2.0 * n * m * d:.4g}; the half-width pass computes half of it and bounds the rest (DESIGN.md 4.15); "
                                         "achieved / frac count the operations performed, not the product avoided") if half else
                                        "2 N M D, the reference's all-pairs product",
-                         "single_stream": {"avg_launch_ms": iso_ms, "achieved": flops / (iso_ms * 1e-3) / 1e12,
-                                           "frac": flops / (iso_ms * 1e-3) / 1e12 / peak,
-                                           "note": "same kernel without the RANSAC of the previous pair running beside it"}},
+                         "single_stream": ({"avg_launch_ms": iso_ms, "achieved": flops / (iso_ms * 1e-3) / 1e12,
+                                            "frac": flops / (iso_ms * 1e-3) / 1e12 / peak,
+                                            "note": "same kernel without the RANSAC of the previous pair running beside it"} if args.full else None)},
         }
-        extra = {"note": "measured outside the timed region; the headline `value` is C2 only"}
-        if not args.no_cpu_baseline and world == 1:
+        extra = {"note": "measured outside the timed region; the headline `value` is C2 only" + ("" if args.full else " (--full: the other figures)")}
+        if args.full and not args.no_cpu_baseline and world == 1:
             host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in pairs[0].items()}
             line["cpu_baseline"], delta = cpu_baseline(host, args.iters, T_gpu=T0)
             if delta is not None:
                 extra["pose_delta_vs_oracle"] = delta
         else:
             line["cpu_baseline"] = None
-        if not args.no_extra and world == 1 and (n, m) == (N_SCAN, N_MAP):  # N > 1: the other ranks would idle at the barrier
+        if args.full and not args.no_extra and world == 1 and (n, m) == (N_SCAN, N_MAP):  # N > 1: the other ranks would idle at the barrier
             del pipe
             try:
                 extra.update(c2_variants(dev, lib, pairs[:4], vdist.pairs_per_rank(num_pairs, world), args.warmup, args.iters, S))

@@ -7,6 +7,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -28,13 +29,31 @@ def _check(out: str, steps: int):
     return d
 
 
-def test_bench_plain_small_run():
+def test_bench_plain_small_run(tmp_path):
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(dump)],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 4)
     assert d["config"]["collective"].startswith("none")
+    # a plain run is the headline alone: no CPU oracle, no run of the kernel on its own, no profiler passes, no other configurations
+    assert d["cpu_baseline"] is None and d["roofline"]["single_stream"] is None
+    assert not (d["roofline"]["traffic_source"] or "").startswith("this run") and set(d["extra"]) == {"note"}
+    # --dump-outputs: what the last timed registration returned, float32 / float64 only, at most 64 MB
+    files = {p.stem: p for p in dump.glob("*.npy")}
+    assert set(files) == {"T", "fitness", "rmse", "best_hyp", "count", "idx", "sim", "keep", "corres", "inlier_mask"}, sorted(files)
+    assert sum(p.stat().st_size for p in files.values()) <= 64 * 10 ** 6
+    o = {k: np.load(p) for k, p in files.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values())
+    k = int(o["count"][0])
+    assert k == d["config"]["correspondences_last_step"] and o["corres"].shape == (k, 2) and o["inlier_mask"].shape == (k,)
+    assert o["idx"].shape == o["sim"].shape == (20000,)
+    np.testing.assert_array_equal(o["corres"][:, 0], o["keep"])
+    np.testing.assert_array_equal(o["corres"][:, 1], o["idx"][o["keep"].astype(np.int64)])
+    assert (o["sim"][o["keep"].astype(np.int64)] >= 0.8).all() and 0 < o["inlier_mask"].sum() <= k
+    T = o["T"]
+    assert T.shape == (4, 4) and np.allclose(T[:3, :3] @ T[:3, :3].T, np.eye(3), atol=1e-9) and np.array_equal(T[3], [0, 0, 0, 1])
     # one pipelined warm-up step is enough: the auto policy has settled (on the half-width pass, D.2 data) before the timed region
     assert d["config"]["policy_settle_registrations"] == 6 and "half-width" in d["config"]["coarse_pass"]
     # the kernel the line reports is the kernel the C2 parity test compares with the oracle
@@ -46,7 +65,7 @@ def test_bench_under_torch_distributed_run_world1():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29517", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1"]
+           "--master-port", "29517", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 4)

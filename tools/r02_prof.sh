@@ -4,8 +4,8 @@ O=$R/gpurun_out/r02prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for V in ${VARIANTS:-0 4}; do
-  VFM_VARIANT=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v$V -o bench -- python $R/bench.py --no-cpu-baseline --steps 30 > $O/bench_v$V.json 2> $O/prof_v$V.err
-  VFM_VARIANT=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$V -o bench -- python $R/bench.py --no-cpu-baseline --steps 30 --streams 1 > $O/bench_s$V.json 2> $O/prof_s$V.err
+  VFM_VARIANT=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/v$V -o bench -- python $R/bench.py --full --no-cpu-baseline --steps 30 > $O/bench_v$V.json 2> $O/prof_v$V.err
+  VFM_VARIANT=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s$V -o bench -- python $R/bench.py --full --no-cpu-baseline --steps 30 --streams 1 > $O/bench_s$V.json 2> $O/prof_s$V.err
   for k in v s; do
     f=$(find $O/$k$V -name "*kernel_stats.csv" | head -1)
     echo "== variant $V $k"; python - "$f" <<'PY'

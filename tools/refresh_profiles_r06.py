@@ -155,7 +155,7 @@ collected by `python tools/refresh_profiles_r06.py`.  Raw files are next to this
 
 ## bench.py (default: `auto` -- on D.2 descriptors the half-width pass in fp6 with the bound test inside the kernel, record kind 8)
 
-`python bench.py` -> `profiles/r06_bench.json`: **{b['value']:.1f} registrations/s** ({b['ms_per_step']:.3f} ms per
+`python bench.py --full` -> `profiles/r06_bench.json`: **{b['value']:.1f} registrations/s** ({b['ms_per_step']:.3f} ms per
 registration), dominant kernel `{r['kernel'].split(' (')[0]}` {r['avg_launch_ms']:.3f} ms per launch inside the timed region =
 {r['achieved']:.0f} TOP/s = {r['frac']:.3f} of {r['peak'] / 1000:.1f} POP/s ({r.get('peak_note', 'dense MFMA peak')}; operations of the kernel as launched:
 {r['flops_per_launch'] / 1e12:.3f} TOP -- coarse pass in use: {cfg.get('coarse_pass', '?')}; surviving chunks per query of the half-width
