@@ -559,3 +559,93 @@ def test_scene_level_descriptor_builder_equals_the_per_cloud_calls(tmp_path):
     back = read_scenes(out)
     for a, b in zip(back["map_point_clouds"], map_clouds):
         np.testing.assert_array_equal(a, b)
+
+
+def test_ransac_registration_on_an_all_lifted_scene_cold_warm_and_through_a_handle(orc):
+    """RegistrationNode.ransac_registration(voxel_map, raw_scan, "vfm", run_icp=True) on the data the reference sends: a ~200 000-row map
+    whose every row is a lifted ViT feature (all alike: hundreds of candidate chunks per query) and a scan voxelised down to a few
+    hundred rows (RN:399-414).  Cold, warm (cache_map=True, second call) and through set_map: all three equal the oracle bit for bit."""
+    from vfmreg import o3d, synth
+    from vfmreg.mapping import VoxelHashMap
+    from vfmreg.registration import RegistrationNode
+    VoxelHashMap.quiet = True
+    p = synth.make_all_lifted_pair_device(20000, 200000, 384, seed=19, zero_rows=0.05)
+    voxel_map = np.c_[p["b_xyz"].cpu().numpy(), p["b_desc"].cpu().numpy()]
+    raw_scan = np.c_[p["q_xyz"].cpu().numpy(), p["q_desc"].cpu().numpy()]
+    bn = torch.nn.functional.normalize(p["b_desc"].double(), dim=1)
+    assert float(bn.mean(0).norm()) >= 0.5
+    ref_pose, ref_icp, ref_corres = orc.ransac_registration_vfm(voxel_map, raw_scan, n_iter=3000, run_icp=True)
+    assert len(ref_corres) >= 75
+    print(f"|mean of the normalised map rows| {float(bn.mean(0).norm()):.3f}; oracle correspondences {len(ref_corres)}")
+    node = RegistrationNode(ransac_iterations=3000, cache_map=True)
+    runs = []
+    for nd, vm in ((RegistrationNode(ransac_iterations=3000), voxel_map), (node, voxel_map), (node, voxel_map),
+                   (RegistrationNode(ransac_iterations=3000), None)):
+        o3d.utility.random.seed(42)
+        runs.append(nd.ransac_registration(vm if vm is not None else nd.set_map(voxel_map), raw_scan, "vfm", run_icp=True))
+    assert node._map_cache is not None
+    for pose, icp in runs:
+        np.testing.assert_array_equal(pose, ref_pose)
+        np.testing.assert_array_equal(icp, ref_icp)
+
+
+def test_prepare_map_runs_under_the_pipelines_own_config(orc):
+    """RegistrationPipeline(config=...).prepare_map called from a thread bound to ANOTHER config prepares the map under the pipeline's
+    config, as register() runs under it: every library call it makes sees that binding, the prepared bytes are those of a prepare_map
+    made under the pipeline's config, and register(..., reuse_map=True) gives the oracle's answers."""
+    import threading
+    from vfmreg import _lib, synth
+    from vfmreg.pipeline import RegistrationPipeline
+    n, m, d = 3000, 20000, 384
+    p = synth.make_pair_device(n, m, d, seed=29)
+    own = _lib.Config(coarse_variant=41, prep_grid=7)
+    lib = _lib.load()
+    real = lib.vfm_match_prepare
+    seen = []
+
+    def spy(*args):
+        seen.append(_lib.current())
+        return real(*args)
+    lib.vfm_match_prepare = spy
+    try:
+        with _lib.using(own):
+            ref_pipe = RegistrationPipeline(n, m, d, n_iter=2000, coarse="int8")
+            for r in ref_pipe.sets:
+                r.bprep.zero_()                               # (bytes no preparation writes compare equal too)
+            ref_pipe.prepare_map(p["b_desc"])
+        torch.cuda.synchronize()
+        pipe = RegistrationPipeline(n, m, d, n_iter=2000, coarse="int8", config=own)
+        for r in pipe.sets:
+            r.bprep.zero_()
+        seen.clear()
+        errors = []
+
+        def other_thread():
+            try:
+                with _lib.using(_lib.Config(coarse_variant=40, prep_grid=3)):
+                    pipe.prepare_map(p["b_desc"])
+                    torch.cuda.synchronize()
+            except Exception as e:   # (re-raised below, in the test's thread)
+                errors.append(e)
+        t = threading.Thread(target=other_thread)
+        t.start()
+        t.join()
+        assert not errors, errors
+    finally:
+        lib.vfm_match_prepare = real
+    assert seen and all(c is own for c in seen), seen
+    for r, rr in zip(pipe.sets, ref_pipe.sets):
+        assert torch.equal(r.bprep, rr.bprep)
+    out = pipe.register(p["q_desc"], p["q_xyz"], p["b_desc"], p["b_xyz"], reuse_map=True)
+    pipe.synchronize()
+    torch.cuda.synchronize()
+    qn, _ = orc.l2norm_rows(p["q_desc"].cpu().numpy())
+    bn, _ = orc.l2norm_rows(p["b_desc"].cpu().numpy())
+    ridx, rsim = orc.match_ip_top1(qn, bn)
+    keep = ~(rsim.astype(np.float64) < 0.8)
+    corres = np.stack([np.nonzero(keep)[0], ridx[keep]], 1).astype(np.int32)
+    ref = orc.ransac_corr(p["q_xyz"].cpu().numpy(), p["b_xyz"].cpu().numpy(), corres, 10000.0, 2000, seed=42)
+    c = int(out["count"].item())
+    assert c == len(corres) and c > 500
+    np.testing.assert_array_equal(out["corres"].cpu().numpy()[:c], corres)
+    np.testing.assert_array_equal(out["T"].cpu().numpy(), ref.transformation)

@@ -267,3 +267,78 @@ def test_register_frame_other_widths_take_the_vectorxd_loop(width, zero_rows):
         np.testing.assert_array_equal(tgt.cpu().numpy()[z], plain_t.cpu().numpy()[z])
     # an empty descriptor map hands the guess back (Registration.cpp:389)
     np.testing.assert_array_equal(register_frame(scan, get_voxel_hash_map(cfg), guess, 6.0, 0.6), guess)
+
+
+def _rebuild_scene(width, seed):
+    """Two maps of the same kept count: A (coordinates in [1, 51] x [1, 51] x [1, 7], so that every key is trunc of a positive number)
+    and B = A moved by three whole voxels in x with other descriptors; a scan of each (a planted pose, 0.02 m of noise, descriptors =
+    the map's + noise) and a guess near the planted pose.  387 columns: the descriptors are lifted ViT features (all alike)."""
+    from vfmreg import synth
+    rng = np.random.default_rng(seed)
+    m, n, f = 20000, 3000, width - 3
+    xyz = np.c_[rng.uniform(1, 51, m), rng.uniform(1, 51, m), rng.uniform(1, 7, m)]
+    if width == 387:
+        descs = [synth.make_all_lifted_pair_device(1, m, 384, seed=seed + k)["b_desc"].cpu().numpy().astype(np.float64) for k in (0, 1)]
+    else:
+        descs = [rng.standard_normal((m, f)) for _ in range(2)]
+    out = []
+    for k, shift in enumerate((0.0, 3.0)):
+        mxyz = xyz + [shift, 0.0, 0.0]
+        T = synth.random_pose(rng)
+        T[:3, 3] *= 0.1
+        pick = rng.choice(m, n, replace=False)
+        s_xyz = (mxyz[pick] - T[:3, 3]) @ T[:3, :3] + rng.normal(0, 0.02, (n, 3))
+        rows = mxyz if width == 3 else np.c_[mxyz, descs[k]]
+        scan = s_xyz if width == 3 else np.c_[s_xyz, descs[k][pick] + 0.1 * rng.standard_normal((n, f))]
+        guess = T.copy()
+        guess[:3, 3] += rng.normal(0, 0.25, 3)
+        out.append((rows, scan, guess))
+    return out
+
+
+def _oracle_pose(width, scan, vhm, guess, sigma):
+    from oracle import oracle as orc
+    if width == 3:
+        return orc.register_frame(scan, vhm.point_cloud(), vhm.voxel_size, guess, 3 * sigma, sigma / 3)
+    if width == 387:
+        return orc.register_frame_nd(scan, vhm.point_cloud_n(), vhm.voxel_size, guess, 3 * sigma, sigma / 3)[0]
+    return orc.register_frame_xd(scan, vhm.point_cloud_n(), vhm.voxel_size, guess, 3 * sigma, sigma / 3)
+
+
+@pytest.mark.parametrize("width", [3, 387, 67])
+def test_register_frame_after_the_map_is_rebuilt_searches_the_new_map(width):
+    """register_frame keeps its ICP grid with the map (the 3-D grid: icp._grid_of; the descriptor grid of the VectorXd loop:
+    icp._register_frame_xd), keyed on the kept-row count.  A map cleared and refilled with another cloud of the SAME kept count must be
+    searched through the new coordinates and descriptors: the pose equals the oracle's on the new map and a fresh map's.  Likewise a
+    map that a second add_points extends.  Widths: 3 columns, 3 + 384 (the descriptor-seeded loop, on lifted features), 3 + 64."""
+    from vfmreg.config import load_config
+    from vfmreg.icp import register_frame
+    from vfmreg.mapping import VoxelHashMap, get_voxel_hash_map
+    VoxelHashMap.quiet = True
+    cfg = load_config(None, None)
+    sigma = cfg.adaptive_threshold.initial_threshold
+    (rows_a, scan_a, guess_a), (rows_b, scan_b, guess_b) = _rebuild_scene(width, seed=width)
+
+    def fresh(*blocks):
+        v = get_voxel_hash_map(cfg)
+        for r in blocks:
+            v.add_points(r)
+        return v
+    vhm = fresh(rows_a)
+    pose_a = register_frame(scan_a, vhm, guess_a, 3 * sigma, sigma / 3)
+    np.testing.assert_array_equal(pose_a, _oracle_pose(width, scan_a, vhm, guess_a, sigma))
+    kept = len(vhm.point_cloud())
+    vhm.clear()
+    vhm.add_points(rows_b)
+    assert len(vhm.point_cloud()) == kept                   # the grids' key alone cannot tell the maps apart
+    pose_b = register_frame(scan_b, vhm, guess_b, 3 * sigma, sigma / 3)
+    np.testing.assert_array_equal(pose_b, register_frame(scan_b, fresh(rows_b), guess_b, 3 * sigma, sigma / 3))
+    np.testing.assert_array_equal(pose_b, _oracle_pose(width, scan_b, vhm, guess_b, sigma))
+    assert np.abs(pose_b - pose_a).max() > 0.1              # (the planted poses differ: a stale map would not give this one)
+    # refilled without clear(): the map holds both clouds
+    vhm = fresh(rows_a)
+    register_frame(scan_a, vhm, guess_a, 3 * sigma, sigma / 3)
+    vhm.add_points(rows_b)
+    pose_ab = register_frame(scan_b, vhm, guess_b, 3 * sigma, sigma / 3)
+    np.testing.assert_array_equal(pose_ab, register_frame(scan_b, fresh(rows_a, rows_b), guess_b, 3 * sigma, sigma / 3))
+    np.testing.assert_array_equal(pose_ab, _oracle_pose(width, scan_b, vhm, guess_b, sigma))

@@ -181,3 +181,38 @@ def test_descriptor_seeded_icp_restatement_recovers_the_planted_pose_and_its_med
     assert "vfm" in kinds and "icp" in kinds and kinds == sorted(kinds, key=lambda k: k != "vfm")   # the VFM stage first
     assert np.linalg.norm(T - p["T_gt"]) < 5e-3 < np.linalg.norm(guess - p["T_gt"])
     assert len(s) == len(t) > 100 and np.linalg.norm(s - t, axis=1).max() < 0.2
+
+
+def test_accelerated_match_oracle_on_all_lifted_like_rows_equals_the_bruteforce_oracle():
+    """The GPU tests' oracle on the data where its candidate lists grow: map rows that are all lifted features (bilinear samples of a
+    few cameras' patch grids, every point seen again by ten clouds, plus the large common component of a ViT's patch tokens: every row
+    is a near-duplicate of many others).  The BLAS fp32 proposal + window + exact decision of ``match_ip_top1`` must give the all-pairs
+    fp64 decision on every row, at several block sizes; rows that are exact copies of map rows (ties: lowest index) and all-zero rows
+    (index 0, similarity 0) included."""
+    import torch
+    from vfmreg import synth
+    n, m, d = 500, 30000, 384
+    b = synth.lifted_map(m, d, clouds=10, cams=6, gh=16, gw=21, seed=5, view_noise=0.05, device="cpu", revisit=400)
+    g = torch.Generator().manual_seed(6)
+    rms = b.pow(2).mean().sqrt()
+    b = (b + 2.0 * rms * torch.randn((1, d), generator=g)).numpy()
+    rng = np.random.default_rng(7)
+    pick = rng.integers(0, m, n)
+    q = b[pick] + np.float32(0.02 * float(rms)) * rng.standard_normal((n, d)).astype(np.float32)
+    q[::25] = b[pick[::25]]                      # exact copies: the copy and its duplicates tie at the top
+    q[7] = 0.0
+    qn, _ = orc.l2norm_rows(q)
+    bn, _ = orc.l2norm_rows(b)
+    mean = np.linalg.norm(bn.astype(np.float64).mean(0))
+    assert mean >= 0.5, mean                     # the regime: rows that are all alike
+    idx, sim = orc.match_ip_top1_bruteforce(qn, bn)
+    assert idx[7] == 0 and sim[7] == 0.0
+    for block in (256, 1024):
+        ia, sa = orc.match_ip_top1(qn, bn, block=block)
+        np.testing.assert_array_equal(ia, idx)
+        np.testing.assert_array_equal(sa, sim)
+    # the window really held long lists: many rows of the map score within 0.01 of the best for a typical query
+    s = qn[:50] @ bn.T
+    near = (s >= s.max(1, keepdims=True) - 0.01).sum(1)
+    print(f"|mean of the normalised map rows| {mean:.3f}; rows within 0.01 of the best, median over 50 queries: {int(np.median(near))}")
+    assert np.median(near) >= 10

@@ -51,6 +51,13 @@ class VoxelHashMap:
         self._load = None       # pinned int32[1]: load figure of the last gated search
         self._load_pending = None
         self._xyz = None        # cached xyz_map() (it carries the ICP grid register_frame builds from it)
+        self._drop_icp_grids()
+
+    def _drop_icp_grids(self):
+        # the ICP grids register_frame keeps with the map (icp._grid_of, icp._register_frame_xd) are keyed on the kept-row count only:
+        # a map refilled with as many other rows would be searched through the old coordinates and descriptors
+        self.__dict__.pop("_icp_grid", None)
+        self.__dict__.pop("_icp_desc_grid", None)
 
     @staticmethod
     def _kind(width: int) -> str:
@@ -123,7 +130,7 @@ class VoxelHashMap:
         self._dev = None
         self._prep = None
         self._xyz = None
-        self.__dict__.pop("_icp_grid", None)
+        self._drop_icp_grids()
 
     def add_points_device(self, rows: torch.Tensor, xyz64: torch.Tensor):
         """add_points on rows that are already on the device (rows [n, w] fp32 / fp64, xyz64 [n, 3] fp64)."""
@@ -146,7 +153,7 @@ class VoxelHashMap:
         self._dev = None
         self._prep = None
         self._xyz = None
-        self.__dict__.pop("_icp_grid", None)
+        self._drop_icp_grids()
 
     def _cloud(self, kind: str):
         """(rows, xyz64) of one of the maps as the reference walks it (VoxelHashMap.cpp:628-676), on the device."""

@@ -240,6 +240,12 @@ class RegistrationPipeline:
     def prepare_map(self, b_desc: torch.Tensor) -> None:
         """IndexFlatIP.add: normalise + convert the map once (it is immutable per scene); every buffer
         set gets its own copy so that ``register(..., reuse_map=True)`` never re-prepares."""
+        if self.config is None:
+            return self._prepare_map(b_desc)
+        with _lib.using(self.config):     # under this pipeline's policy, as register(), whichever thread calls
+            return self._prepare_map(b_desc)
+
+    def _prepare_map(self, b_desc: torch.Tensor) -> None:
         lib = _lib.load()
         ops._chk(b_desc, torch.float32, "b_desc")
         if b_desc.shape != (self.m, self.d):

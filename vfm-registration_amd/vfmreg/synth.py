@@ -130,3 +130,85 @@ def make_lifted_pair_device(n: int, m: int, d: int = 384, seed: int = 42, device
         b, q = b + mu, q + mu
     base["b_desc"], base["q_desc"] = b.contiguous(), q.contiguous()
     return base
+
+
+_VIT_GRIDS = {}
+
+
+def _vit_grids(seed: int, device):
+    """(images, patch grids) of the repository's ViT-S/14 with random weights on 6 seeded 1200 x 1600 camera images (kept: the
+    forward is the same for every pair of a seed)"""
+    key = (int(seed), str(device))
+    if key not in _VIT_GRIDS:
+        import torch
+        from . import vit as V
+        rng = np.random.default_rng(seed)
+        imgs = torch.from_numpy(rng.integers(1, 255, (6, 1200, 1600, 3), dtype=np.uint8)).to(device)
+        model = V.ViTS14(V.random_weights(seed), 1200, 1600, device=device)
+        _VIT_GRIDS.clear()
+        _VIT_GRIDS[key] = (imgs, model.forward(imgs))
+    return _VIT_GRIDS[key]
+
+
+def lift_vit_features(points: int, seed: int = 0, device="cuda", vit_seed: int = 0):
+    """``points`` rows of the ViT's own features lifted (ops.LiftPlan, prepare_scenes.py:85-104) from a 6-camera rig (90 x 74 deg
+    each, 60 deg apart) onto points 6 - 45 m around it: every returned row was seen by a camera (non-zero)."""
+    import torch
+    from . import ops
+    imgs, grids = _vit_grids(vit_seed, device)
+    H, W = imgs.shape[1], imgs.shape[2]
+    K = np.array([[800.0, 0, 800], [0, 800, 600], [0, 0, 1]])
+    cams = []
+    for c in range(6):
+        y = np.deg2rad(60 * c)
+        R = np.stack([[np.sin(y), -np.cos(y), 0], [0, 0, -1], [np.cos(y), np.sin(y), 0]])
+        cams.append(dict(mode=ops.PROJ_KITTI, mats=[K @ np.c_[R, np.zeros(3)]], fc=None, subsample=1.0, win=None, H=H, W=W,
+                         proj_image=None, grid=grids[c], Hup=H, Wup=W, rot_mode=0, raw_image=imgs[c]))
+    plan = ops.LiftPlan(cams, grids.shape[-1])
+    rng = np.random.default_rng(seed + 1)
+    total = points + points // 4 + 64            # (the few points no camera sees are dropped)
+    r, az = rng.uniform(6.0, 45.0, total), rng.uniform(-np.pi, np.pi, total)
+    xyz = np.c_[r * np.cos(az), r * np.sin(az), rng.uniform(-2.0, 3.0, total)]
+    pcl = torch.from_numpy(np.ascontiguousarray(np.insert(xyz, 3, 1, axis=1).T)).to(device)
+    desc = torch.zeros((total, grids.shape[-1]), dtype=torch.float32, device=device)
+    filled = torch.zeros(total, dtype=torch.uint8, device=device)
+    plan(pcl, desc, filled)
+    seen = torch.nonzero((filled != 0) & (desc != 0).any(dim=1)).flatten()
+    if len(seen) < points:
+        raise RuntimeError(f"lift_vit_features: {len(seen)} of {total} points seen, {points} wanted")
+    return desc[seen[:points]].contiguous()
+
+
+def make_all_lifted_pair_device(n: int, m: int, d: int = 384, seed: int = 42, device="cuda", views: int = 10, view_noise: float = 0.05,
+                                scan_noise: float = 0.05, zero_rows: float = 0.0, outlier: float = 0.5):
+    """A D.2 pair (``make_pair_device``'s geometry: b_xyz, q_xyz, match, T_gt) whose descriptors are ALL lifted ViT features, as the
+    reference's maps are (registration_node.py:562 keeps only rows with a descriptor; prepare_scenes.py:85-104 lifts every one of them
+    from the same ViT): ``lift_vit_features`` on ceil(m / views) points; every map row is one of those rows + ``view_noise`` rms of
+    noise per view (``views`` near-duplicates per point, spread over the map); a matched scan row is its planted map row +
+    ``scan_noise`` rms; an outlier scan row is the lifted row of a point the map does not hold (+ the same noise).  A ``zero_rows``
+    fraction of the scan rows carries the all-zero descriptor of a point no camera saw (their ``match`` is -1); map rows never do.
+    The rows share the large common component of the ViT's patch tokens: |mean of the normalised rows| ~ 0.7.  One ViT (random weights
+    and images of seed 0) serves every pair; the ViT is only a data source -- tests compare against the oracle on the rows it gives."""
+    import torch
+    if d != 384:
+        raise ValueError("the ViT-S/14 features are 384 wide")
+    base = make_pair_device(n, m, d, seed=seed, device=device, outlier=outlier)
+    pts = -(-m // views)
+    n_out = max(1, min(n, pts))
+    lifted = lift_vit_features(pts + n_out, seed=seed, device=device)
+    g = torch.Generator(device=device)
+    g.manual_seed(seed + 5)
+    rms = lifted.pow(2).mean().sqrt()
+    point = torch.randperm(m, generator=g, device=device) % pts
+    b = lifted[point] + view_noise * rms * torch.randn((m, d), generator=g, device=device)
+    match = base["match"]
+    q = b[match.clamp(min=0)] + scan_noise * rms * torch.randn((n, d), generator=g, device=device)
+    other = lifted[pts + torch.randint(0, n_out, (n,), generator=g, device=device)]
+    other = other + scan_noise * rms * torch.randn((n, d), generator=g, device=device)
+    q = torch.where((match < 0)[:, None], other, q)
+    if zero_rows > 0:
+        z = torch.rand(n, generator=g, device=device) < zero_rows
+        q[z] = 0.0
+        base["match"] = torch.where(z, torch.full_like(match, -1), match)
+    base["b_desc"], base["q_desc"] = b.contiguous(), q.contiguous()
+    return base
