@@ -520,6 +520,45 @@ int vfm_icp_step_nearest_desc(const double *src, int64_t n, const double *T_host
 int vfm_icp_build_system(const double *src, const double *tgt, const uint8_t *valid, int64_t n,
                          double kernel, double *out43, vfm_stream_t stream);
 
+/* ------------------------------------------------------------------ FPFH descriptors (Open3D 0.18 baseline) */
+
+/* The CPU work of extract_fpfh_features (src/vfm-reg/src/vfm_reg/descriptors.py:19-44), which the reference runs in Open3D 0.18.
+ * Points are n x 3 fp64 (n <= 2^26), fp64 arithmetic in Open3D's operation order.  Nothing here synchronises `stream`.
+ * vfm_fpfh_workspace_bytes: the workspace of vfm_fpfh_grid_build and vfm_fpfh_voxel_down_sample for n points. */
+size_t vfm_fpfh_workspace_bytes(int64_t n);
+/* The search structure of geometry::KDTreeFlann(cloud), as a sorted-key CSR grid whose cell is the radius: keys_out (int64[n]) the
+ * cell keys ascending, order_out (int32[n]) the point indices in that order (ascending within a cell). */
+int vfm_fpfh_grid_build(const double *pts, int64_t n, double radius, int64_t *keys_out, int32_t *order_out, void *ws,
+                        size_t ws_bytes, vfm_stream_t stream);
+/* KDTreeFlann::SearchHybrid(point i, radius, max_nn) for every point of the cloud (geometry/KDTreeFlann.cpp): the points with
+ * d2 < radius^2 (d2 = dx*dx + dy*dy + dz*dz, left to right), ascending by (d2, index) -- equal distances by index, a convention of
+ * this library --, the first max_nn (1 <= max_nn <= 1024) of them.  Rows of max_nn: nbr_idx (int32, -1 past the count), nbr_d2
+ * (fp64), nbr_cnt (int32[n]).  Any number of candidates is searched exactly.  scanned_out (nullable, int32[n]): the grid points
+ * each query read. */
+int vfm_fpfh_search_hybrid(const double *pts, int64_t n, const int64_t *keys, const int32_t *order, double radius,
+                           int32_t max_nn, int32_t *nbr_idx, double *nbr_d2, int32_t *nbr_cnt, int32_t *scanned_out,
+                           vfm_stream_t stream);
+/* PointCloud::EstimateNormals(search_param, fast_normal_computation = true) on a cloud without normals
+ * (geometry/EstimateNormals.cpp): ComputeCovariance's one-pass cumulants over the neighbour rows (identity below 3 neighbours),
+ * FastEigen3x3, a zero vector replaced by (0, 0, 1); no orientation step. */
+int vfm_fpfh_normals(const double *pts, int64_t n, const int32_t *nbr_idx, const int32_t *nbr_cnt, int32_t max_nn,
+                     double *normals_out, vfm_stream_t stream);
+/* PointCloud::VoxelDownSample(voxel_size) (geometry/PointCloud.cpp): voxel = floor((p - (min_bound - voxel_size / 2)) / voxel_size),
+ * output = per-voxel mean of the points and (normals non-NULL) of the normals, not renormalised, summed in input order.  Voxels in
+ * ascending (ix, iy, iz) order (Open3D: unordered_map order).  pts_out / normals_out: n rows of room; *count_out (device int32): the
+ * number of voxels, -1 if a voxel index reaches 2^21 on some axis. */
+int vfm_fpfh_voxel_down_sample(const double *pts, const double *normals, int64_t n, double voxel_size, double *pts_out,
+                               double *normals_out, int32_t *count_out, void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* ComputeSPFHFeature (pipelines/registration/Feature.cpp): per point the 33-bin histogram of ComputePairFeatures over neighbour rows
+ * 1 .. count-1, each pair adding 100 / (count - 1); rows of fewer than 2 neighbours are zero.  spfh_out: n x 33 fp64, row-major. */
+int vfm_fpfh_spfh(const double *pts, const double *normals, int64_t n, const int32_t *nbr_idx, const int32_t *nbr_cnt,
+                  int32_t max_nn, double *spfh_out, vfm_stream_t stream);
+/* ComputeFPFHFeature (pipelines/registration/Feature.cpp): sum over neighbour rows 1 .. count-1 with d2 != 0 of spfh[nb] / d2, each
+ * group of 11 bins scaled by 100 / its sum where non-zero, plus the point's own SPFH.  fpfh_out: n x 33 fp64 (Feature::data_ is its
+ * transpose). */
+int vfm_fpfh_fpfh(const double *spfh, int64_t n, const int32_t *nbr_idx, const double *nbr_d2, const int32_t *nbr_cnt,
+                  int32_t max_nn, double *fpfh_out, vfm_stream_t stream);
+
 /* ------------------------------------------------------------------ DINOv2 ViT-S/14 (row A1) */
 
 /* self.model.model(img) of IF:101 incl. the transform of IF:67-77: bilinear resize (antialias

@@ -2,7 +2,9 @@
 (registration_node.py:312-328): ``o3d.geometry.PointCloud``, ``o3d.utility.Vector3dVector`` /
 ``Vector2iVector``, ``o3d.utility.random.seed`` and
 ``o3d.pipelines.registration.registration_ransac_based_on_correspondence`` with
-``TransformationEstimationPointToPoint`` and ``RANSACConvergenceCriteria``.  Usage:
+``TransformationEstimationPointToPoint`` and ``RANSACConvergenceCriteria``; for the FPFH baseline
+(vfm_reg/descriptors.py:19-44) ``PointCloud.estimate_normals`` / ``voxel_down_sample``,
+``o3d.geometry.KDTreeSearchParamHybrid`` and ``o3d.pipelines.registration.compute_fpfh_feature``.  Usage:
 
     from vfmreg import o3d            # instead of: import open3d as o3d
 
@@ -27,11 +29,6 @@ def _seed_fn(s: int):
     _seed[0] = int(s)
 
 
-class PointCloud:
-    def __init__(self, points=None):
-        self.points = np.zeros((0, 3)) if points is None else points
-
-
 class DeviceArray:
     """An array that already lives on the GPU (N x 3 fp64 points / C x 2 int32 correspondences), accepted wherever the stand-ins
     take a numpy array.  ``np.asarray()`` downloads it once, on demand; ``registration_ransac_based_on_correspondence`` reads the
@@ -53,6 +50,105 @@ class DeviceArray:
     @property
     def shape(self):
         return tuple(self.device_tensor.shape)
+
+
+class KDTreeSearchParamHybrid:
+    """geometry::KDTreeSearchParamHybrid: the points within ``radius`` (strictly closer), the nearest ``max_nn`` of them."""
+
+    def __init__(self, radius: float, max_nn: int):
+        self.radius = float(radius)
+        self.max_nn = int(max_nn)
+
+    def __repr__(self):
+        return f"KDTreeSearchParamHybrid with radius = {self.radius:f} and max_nn = {self.max_nn:d}"
+
+
+def _device_rows(a) -> torch.Tensor:
+    """N x 3 fp64 rows on the device: a DeviceArray's tensor as it is, a host array uploaded."""
+    if isinstance(a, DeviceArray):
+        return Vector3dVector(a).device_tensor.contiguous()
+    return torch.from_numpy(Vector3dVector(np.asarray(a))).cuda()
+
+
+def _hybrid(search_param) -> KDTreeSearchParamHybrid:
+    if not isinstance(search_param, KDTreeSearchParamHybrid):
+        raise NotImplementedError("only KDTreeSearchParamHybrid is supported (descriptors.py:27, 35)")
+    return search_param
+
+
+class PointCloud:
+    """geometry::PointCloud with points and normals.  The FPFH steps (csrc/fpfh.hip) keep their results on the device
+    (``DeviceArray``); ``np.asarray(pcd.points)`` downloads them on demand."""
+
+    def __init__(self, points=None):
+        self.points = np.zeros((0, 3)) if points is None else points
+        self.normals = np.zeros((0, 3))
+
+    def has_normals(self) -> bool:
+        return len(self.normals) > 0 and len(self.normals) == len(self.points)
+
+    def estimate_normals(self, search_param=None, fast_normal_computation: bool = True) -> None:
+        """PointCloud::EstimateNormals on a cloud without normals (FastEigen3x3; no orientation step; fewer than 3 neighbours or a
+        degenerate covariance give (0, 0, 1))."""
+        if not fast_normal_computation:
+            raise NotImplementedError("fast_normal_computation=False is not implemented (the reference uses the default, True)")
+        if self.has_normals():
+            raise NotImplementedError("re-estimating normals of a cloud that has them (Open3D orients them to the old ones) is not "
+                                      "implemented")
+        prm = _hybrid(search_param)
+        pts = _device_rows(self.points)
+        nbrs = ops.fpfh_search(pts, prm.radius, prm.max_nn)
+        self.normals = DeviceArray(ops.fpfh_normals(pts, nbrs))
+
+    def voxel_down_sample(self, voxel_size: float) -> "PointCloud":
+        """PointCloud::VoxelDownSample: per-voxel means of the points (and normals, not renormalised); voxels in ascending
+        (ix, iy, iz) order instead of Open3D's hash-map order."""
+        if voxel_size <= 0.0:
+            raise RuntimeError("voxel_size <= 0.")
+        out = PointCloud()
+        if len(self.points) == 0:
+            return out
+        pts = _device_rows(self.points)
+        nrm = _device_rows(self.normals) if self.has_normals() else None
+        p, nv = ops.fpfh_voxel_down_sample(pts, float(voxel_size), nrm)
+        out.points = DeviceArray(p)
+        if nv is not None:
+            out.normals = DeviceArray(nv)
+        return out
+
+
+class Feature:
+    """pipelines::registration::Feature: ``data`` is dimension() x num() fp64 (downloaded on demand); ``device_tensor`` holds the
+    num() x 33 rows on the device."""
+
+    def __init__(self, rows: torch.Tensor):
+        self.device_tensor = rows
+        self._host = None
+
+    @property
+    def data(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self.device_tensor.cpu().numpy().T
+        return self._host
+
+    def dimension(self) -> int:
+        return int(self.device_tensor.shape[1])
+
+    def num(self) -> int:
+        return int(self.device_tensor.shape[0])
+
+
+def compute_fpfh_feature(input, search_param) -> Feature:
+    """pipelines::registration::ComputeFPFHFeature: SPFH then FPFH over the same SearchHybrid rows (csrc/fpfh.hip)."""
+    if not input.has_normals():
+        raise RuntimeError("Failed because input point cloud has no normal.")
+    prm = _hybrid(search_param)
+    pts = _device_rows(input.points)
+    nrm = _device_rows(input.normals)
+    if len(pts) == 0:
+        return Feature(torch.zeros((0, 33), dtype=torch.float64, device=pts.device))
+    nbrs = ops.fpfh_search(pts, prm.radius, prm.max_nn)
+    return Feature(ops.fpfh_fpfh(ops.fpfh_spfh(pts, nrm, nbrs), nbrs))
 
 
 def Vector3dVector(a):
@@ -161,10 +257,11 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
     return res
 
 
-geometry = SimpleNamespace(PointCloud=PointCloud)
+geometry = SimpleNamespace(PointCloud=PointCloud, KDTreeSearchParamHybrid=KDTreeSearchParamHybrid)
 utility = SimpleNamespace(Vector3dVector=Vector3dVector, Vector2iVector=Vector2iVector, DeviceArray=DeviceArray,
                           random=SimpleNamespace(seed=_seed_fn))
 pipelines = SimpleNamespace(registration=SimpleNamespace(
     registration_ransac_based_on_correspondence=registration_ransac_based_on_correspondence,
     TransformationEstimationPointToPoint=TransformationEstimationPointToPoint,
-    RANSACConvergenceCriteria=RANSACConvergenceCriteria, RegistrationResult=RegistrationResult))
+    RANSACConvergenceCriteria=RANSACConvergenceCriteria, RegistrationResult=RegistrationResult,
+    compute_fpfh_feature=compute_fpfh_feature, Feature=Feature))

@@ -481,3 +481,103 @@ def voxel_robin(xyz: torch.Tensor, voxel_size: float, max_per_voxel: int = 1, re
     vals = info.tolist()
     out = keep[:vals[1] if max_per_voxel == 1 else int(count.item())]
     return (out, vals) if return_info else out
+
+
+# ------------------------------------------------------------------------------------- FPFH (csrc/fpfh.hip)
+FPFH_MAX_NN = 1024
+
+
+def fpfh_grid(pts: torch.Tensor, radius: float, ws: Optional[torch.Tensor] = None):
+    """The search structure of KDTreeFlann(cloud): (sorted cell keys int64[n], point indices in that order int32[n])."""
+    _chk(pts, torch.float64, "pts")
+    lib = _lib.load()
+    n = pts.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=pts.device)
+    order = torch.empty(n, dtype=torch.int32, device=pts.device)
+    need = lib.vfm_fpfh_workspace_bytes(n)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, pts.device)
+    _lib.check(lib.vfm_fpfh_grid_build(pts.data_ptr(), n, float(radius), keys.data_ptr(), order.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream()), "fpfh_grid_build")
+    return keys, order
+
+
+def fpfh_search(pts: torch.Tensor, radius: float, max_nn: int, grid=None, want_scanned: bool = False):
+    """KDTreeFlann::SearchHybrid(radius, max_nn) for every point of the cloud: dict(idx int32[n, max_nn] (-1 padded), d2 fp64[n, max_nn],
+    count int32[n]; scanned int32[n], the grid points each query read, if asked)."""
+    _chk(pts, torch.float64, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    if not 1 <= int(max_nn) <= FPFH_MAX_NN:
+        raise ValueError(f"max_nn must be in 1..{FPFH_MAX_NN}")
+    lib = _lib.load()
+    n = pts.shape[0]
+    keys, order = grid if grid is not None else fpfh_grid(pts, radius)
+    idx = torch.empty((n, max_nn), dtype=torch.int32, device=pts.device)
+    d2 = torch.empty((n, max_nn), dtype=torch.float64, device=pts.device)
+    cnt = torch.empty(n, dtype=torch.int32, device=pts.device)
+    scanned = torch.empty(n, dtype=torch.int32, device=pts.device) if want_scanned else None
+    _lib.check(lib.vfm_fpfh_search_hybrid(pts.data_ptr(), n, keys.data_ptr(), order.data_ptr(), float(radius), int(max_nn), idx.data_ptr(),
+                                          d2.data_ptr(), cnt.data_ptr(), _ptr(scanned), _stream()), "fpfh_search_hybrid")
+    out = dict(idx=idx, d2=d2, count=cnt)
+    if want_scanned:
+        out["scanned"] = scanned
+    return out
+
+
+def fpfh_normals(pts: torch.Tensor, nbrs: dict) -> torch.Tensor:
+    """EstimateNormals(fast_normal_computation=True) from SearchHybrid rows (``fpfh_search``): n x 3 fp64."""
+    _chk(pts, torch.float64, "pts")
+    lib = _lib.load()
+    n = pts.shape[0]
+    out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
+    _lib.check(lib.vfm_fpfh_normals(pts.data_ptr(), n, nbrs["idx"].data_ptr(), nbrs["count"].data_ptr(), nbrs["idx"].shape[1],
+                                    out.data_ptr(), _stream()), "fpfh_normals")
+    return out
+
+
+def fpfh_voxel_down_sample(pts: torch.Tensor, voxel_size: float, normals: Optional[torch.Tensor] = None):
+    """PointCloud::VoxelDownSample: (points m x 3, normals m x 3 or None), voxels in ascending (ix, iy, iz) order.  Reads the voxel
+    count back (synchronises the stream)."""
+    _chk(pts, torch.float64, "pts")
+    if normals is not None:
+        _chk(normals, torch.float64, "normals")
+        if normals.shape != pts.shape:
+            raise ValueError("normals must match points")
+    if not voxel_size > 0:
+        raise ValueError("voxel_size must be positive")
+    lib = _lib.load()
+    n = pts.shape[0]
+    out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
+    nout = torch.empty((n, 3), dtype=torch.float64, device=pts.device) if normals is not None else None
+    count = torch.empty(1, dtype=torch.int32, device=pts.device)
+    ws = _ws(lib.vfm_fpfh_workspace_bytes(n), pts.device)
+    _lib.check(lib.vfm_fpfh_voxel_down_sample(pts.data_ptr(), _ptr(normals), n, float(voxel_size), out.data_ptr(), _ptr(nout),
+                                              count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "fpfh_voxel_down_sample")
+    m = int(count.item())
+    if m < 0:
+        raise ValueError("voxel_size is too small for the extent of the point cloud (2^21 voxels per axis)")
+    return out[:m], (nout[:m] if nout is not None else None)
+
+
+def fpfh_spfh(pts: torch.Tensor, normals: torch.Tensor, nbrs: dict) -> torch.Tensor:
+    """ComputeSPFHFeature from SearchHybrid rows: n x 33 fp64."""
+    _chk(pts, torch.float64, "pts")
+    _chk(normals, torch.float64, "normals")
+    lib = _lib.load()
+    n = pts.shape[0]
+    out = torch.empty((n, 33), dtype=torch.float64, device=pts.device)
+    _lib.check(lib.vfm_fpfh_spfh(pts.data_ptr(), normals.data_ptr(), n, nbrs["idx"].data_ptr(), nbrs["count"].data_ptr(),
+                                 nbrs["idx"].shape[1], out.data_ptr(), _stream()), "fpfh_spfh")
+    return out
+
+
+def fpfh_fpfh(spfh: torch.Tensor, nbrs: dict) -> torch.Tensor:
+    """ComputeFPFHFeature from the SPFH rows and the same SearchHybrid rows: n x 33 fp64 (Open3D's Feature.data is its transpose)."""
+    _chk(spfh, torch.float64, "spfh")
+    lib = _lib.load()
+    n = spfh.shape[0]
+    out = torch.empty((n, 33), dtype=torch.float64, device=spfh.device)
+    _lib.check(lib.vfm_fpfh_fpfh(spfh.data_ptr(), n, nbrs["idx"].data_ptr(), nbrs["d2"].data_ptr(), nbrs["count"].data_ptr(),
+                                 nbrs["idx"].shape[1], out.data_ptr(), _stream()), "fpfh_fpfh")
+    return out

@@ -2,9 +2,10 @@
 
   compute_vfm_correspondences  RN:396-425      ransac_registration('vfm')  RN:273-357
   find_correspondences         RN:482-538      compute_errors              RN:997-1019
+  compute_correspondences      RN:427-547 (the FPFH baseline; the learned baselines raise NotImplementedError)
   rotation re-orthogonalisation RN:331-336
 
-Same names, argument meaning and return values; numpy in / numpy out.  The ROS node, the baseline
+Same names, argument meaning and return values; numpy in / numpy out.  The ROS node, the learned baseline
 descriptors, TEASER and PointDSC are out of scope.  ``run_icp=True`` runs the point-to-point ICP
 refinement of registration_node.py:338-344 (row F2, vfmreg/icp.py).
 """
@@ -19,6 +20,7 @@ import torch
 
 from . import o3d, ops
 from .config import load_config
+from .descriptors import extract_fpfh_features
 from .icp import register_frame
 from .mapping import get_voxel_hash_map
 from .utils import transform_pcl
@@ -113,6 +115,8 @@ class RegistrationNode:
         self._map_cache = None   # (weakref to the array, (shape, dtype, fingerprint), VoxelHashMap)
         self._pose_cache = None  # (bytes of the last initial pose, its device copy): the node passes the identity in every call
         self._chain_host = None  # page-locked landing area of the voxel chain's one read-back
+        self.map_descriptor_cache = {}   # RN:67: method -> (down_map, feats_map)
+        self._map_descriptor_keys = {}   # method -> (shape, dtype, fingerprint) of the map those features were computed from
 
     def invalidate_map(self) -> None:
         """Forget the kept map (``cache_map=True``): the next call rebuilds it from the array it is handed."""
@@ -273,3 +277,33 @@ class RegistrationNode:
             return ransac_pose, pose
         return ransac_pose, None
 
+    _LEARNED = ("dip", "gedi", "fcgf", "gcl", "spinnet")
+
+    def compute_correspondences(self, voxel_map, raw_scan, method: str, mutual_filter: bool = False):
+        """RN:427-547: baseline descriptors of the scan and of the map, matched by find_correspondences(n_points=5000); returns
+        (down_scan[i0], down_map[i1]).  'fpfh' runs extract_fpfh_features(., 0.1) on the GPU (csrc/fpfh.hip).  The map's features
+        are kept in ``map_descriptor_cache[method]`` as in the reference, and reused only for a map of the same shape, dtype and
+        ``_fingerprint`` (a non-contiguous map is not cached)."""
+        if method in self._LEARNED:
+            raise NotImplementedError(f"{method}: the learned baselines need their trained weights and are out of scope")
+        if method != "fpfh":
+            raise ValueError(f"Invalid method: {method}")
+        vm = np.asarray(voxel_map)
+        if vm.ndim != 2 or vm.shape[1] < 3:
+            raise ValueError("Invalid shape")
+        fp = _fingerprint(vm)
+        key = (vm.shape, vm.dtype.str, fp) if fp is not None else None
+        down_map = feats_map = None
+        if key is not None and method in self.map_descriptor_cache and self._map_descriptor_keys.get(method) == key:
+            down_map, feats_map = self.map_descriptor_cache[method]
+        down_scan, feats_scan = extract_fpfh_features(raw_scan, .1)
+        if down_map is None:
+            down_map, feats_map = extract_fpfh_features(vm, .1)
+        if key is not None:
+            self.map_descriptor_cache[method] = (down_map, feats_map)
+            self._map_descriptor_keys[method] = key
+        else:
+            self.map_descriptor_cache.pop(method, None)
+            self._map_descriptor_keys.pop(method, None)
+        corrs_scan, corrs_map = find_correspondences(feats_scan, feats_map, n_points=5000, mutual_filter=mutual_filter)
+        return down_scan[corrs_scan], down_map[corrs_map]

@@ -212,3 +212,77 @@ def make_all_lifted_pair_device(n: int, m: int, d: int = 384, seed: int = 42, de
         base["match"] = torch.where(z, torch.full_like(match, -1), match)
     base["b_desc"], base["q_desc"] = b.contiguous(), q.contiguous()
     return base
+
+
+def make_structured_scene(n_scan: int = 20000, n_map: int = 200000, seed: int = 0, extent: float = 30.0, scan_range: float = 15.0,
+                          boxes: int = 24, cylinders: int = 16, noise_m: float = 0.01, yaw_deg: float = 30.0, shift_m: float = 2.0):
+    """A seeded scene with surfaces (the FPFH baseline needs real normals; Gaussian blobs have none): a ground plane over
+    [-extent, extent]^2, axis-aligned boxes (four walls and a roof) and vertical cylinders (mantle and top), sampled uniformly by area.
+    The map samples the whole scene; the scan is an independent sample of the surfaces within ``scan_range`` (in x / y) of the origin,
+    moved into the scan frame: map = T_gt (scan) + noise.  Both get N(0, noise_m) noise.  T_gt: yaw ~ U(+-yaw_deg), roll / pitch
+    ~ N(0, 1 deg), t ~ U(+-shift_m) in x / y, N(0, 0.1 m) in z.  Returns dict(scan [n_scan, 3] f64, map [n_map, 3] f64, T_gt)."""
+    rng = np.random.default_rng(seed)
+    surf = []   # (kind, params, area)
+    surf.append(("plane", (-extent, extent, -extent, extent), (2 * extent) ** 2))
+    for _ in range(boxes):
+        cx, cy = rng.uniform(-extent + 3, extent - 3, 2)
+        sx, sy = rng.uniform(0.8, 4.0, 2)
+        h = rng.uniform(1.0, 5.0)
+        surf.append(("box", (cx, cy, sx, sy, h), 2 * h * (sx + sy) + sx * sy))
+    for _ in range(cylinders):
+        cx, cy = rng.uniform(-extent + 2, extent - 2, 2)
+        r = rng.uniform(0.2, 1.2)
+        h = rng.uniform(1.5, 6.0)
+        surf.append(("cyl", (cx, cy, r, h), 2 * math.pi * r * h + math.pi * r * r))
+
+    def sample(count, region):
+        out = []
+        area = np.array([s[2] for s in surf])
+        got = 0
+        while got < count:
+            want = int((count - got) * 1.3) + 64
+            k = rng.choice(len(surf), size=want, p=area / area.sum())
+            pts = np.empty((want, 3))
+            for si in np.unique(k):
+                sel = np.flatnonzero(k == si)
+                kind, prm, _ = surf[si]
+                u, v, w = rng.random(len(sel)), rng.random(len(sel)), rng.random(len(sel))
+                if kind == "plane":
+                    x0, x1, y0, y1 = prm
+                    pts[sel] = np.c_[x0 + u * (x1 - x0), y0 + v * (y1 - y0), np.zeros(len(sel))]
+                elif kind == "box":
+                    cx, cy, sx, sy, h = prm
+                    face_area = np.array([sx * h, sx * h, sy * h, sy * h, sx * sy])
+                    f = rng.choice(5, size=len(sel), p=face_area / face_area.sum())
+                    x = cx + (u - 0.5) * sx
+                    y = cy + (v - 0.5) * sy
+                    z = w * h
+                    x = np.where(f == 2, cx - sx / 2, np.where(f == 3, cx + sx / 2, x))
+                    y = np.where(f == 0, cy - sy / 2, np.where(f == 1, cy + sy / 2, y))
+                    z = np.where(f == 4, h, z)
+                    pts[sel] = np.c_[x, y, z]
+                else:
+                    cx, cy, r, h = prm
+                    top = rng.random(len(sel)) < (math.pi * r * r) / (2 * math.pi * r * h + math.pi * r * r)
+                    th = 2 * math.pi * u
+                    rr = np.where(top, r * np.sqrt(v), r)
+                    pts[sel] = np.c_[cx + rr * np.cos(th), cy + rr * np.sin(th), np.where(top, h, w * h)]
+            if region is not None:
+                pts = pts[(np.abs(pts[:, 0]) <= region) & (np.abs(pts[:, 1]) <= region)]
+            out.append(pts)
+            got += len(pts)
+        pts = np.concatenate(out)[:count]
+        return pts + rng.normal(0.0, noise_m, pts.shape)
+
+    world_map = sample(n_map, None)
+    world_scan = sample(n_scan, scan_range)
+    yaw = math.radians(rng.uniform(-yaw_deg, yaw_deg))
+    roll, pitch = np.deg2rad(rng.normal(0.0, 1.0, 2))
+    cr, sr, cp, sp, cy_, sy_ = math.cos(roll), math.sin(roll), math.cos(pitch), math.sin(pitch), math.cos(yaw), math.sin(yaw)
+    R = np.array([[cy_, -sy_, 0], [sy_, cy_, 0], [0, 0, 1]]) @ np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]]) @ \
+        np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = [rng.uniform(-shift_m, shift_m), rng.uniform(-shift_m, shift_m), rng.normal(0.0, 0.1)]
+    scan = (world_scan - T[:3, 3]) @ R   # R^T (p - t)
+    return dict(scan=np.ascontiguousarray(scan), map=np.ascontiguousarray(world_map), T_gt=T)
