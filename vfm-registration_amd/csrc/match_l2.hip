@@ -871,6 +871,9 @@ VFM_EXPORT int vfm_match_mutual_l2(const float* a, int64_t n, const float* b, in
     VFM_CHECK_ARG(n > 0 && m > 0 && d > 0 && a && b && nn_ab, "mutual_l2: bad arguments");
     VFM_CHECK_ARG(prec_mode == VFM_MATCH_FAST || prec_mode == VFM_MATCH_EXACT, "mutual_l2: unknown prec_mode %d", prec_mode);
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "mutual_l2: more than 2^31 rows");
+    // (checked on every path, the all-pairs one included: a caller sizes the workspace by vfm_match_mutual_l2_workspace_bytes alone)
+    if (ws_bytes < vfm_match_mutual_l2_workspace_bytes(n, m, d, prec_mode, nn_ba != nullptr))
+        return vfm_fail(VFM_EWORKSPACE, "mutual_l2: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int kp = l2_padded_k(d);
     if (prec_mode == VFM_MATCH_EXACT || kp == 0) {
@@ -885,8 +888,6 @@ VFM_EXPORT int vfm_match_mutual_l2(const float* a, int64_t n, const float* b, in
         return VFM_OK;
     }
     VFM_CHECK_ARG(ws, "mutual_l2: workspace required in FAST mode");
-    if (ws_bytes < vfm_match_mutual_l2_workspace_bytes(n, m, d, prec_mode, nn_ba != nullptr))
-        return vfm_fail(VFM_EWORKSPACE, "mutual_l2: workspace too small");
     L2Ws w = carve_l2(ws, n, m, d, nn_ba != nullptr);
     VFM_CHECK_HIP(hipMemsetAsync(w.max_bits, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(l2_maxnorm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, a, n, d, w.max_bits);
