@@ -553,7 +553,7 @@ ORC_API int64_t orc_project(int mode, const double *pcl, int64_t n, const double
 /* ------------------------------------------------------------------------ */
 static inline void orc_src_index(float scale, int64_t dst, int64_t in_size, int64_t *i0, int64_t *i1,
                                  float *l0, float *l1) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    float src = fmaf(scale, (float)dst + 0.5f, -0.5f); /* one rounding, as torch's upsample kernels */
     if (src < 0.0f) src = 0.0f;
     int64_t a = (int64_t)src;
     if (a > in_size - 1) a = in_size - 1;

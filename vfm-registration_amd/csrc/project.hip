@@ -152,9 +152,12 @@ __global__ __launch_bounds__(1024) void project_compact_kernel(const int32_t* __
     if (threadIdx.x == 0) *count = base_s;
 }
 
-// torch upsample_bilinear2d(align_corners=False) source index / weights, fp32
+// torch upsample_bilinear2d(align_corners=False) source index / weights, fp32.  The source index is scale * (dst + 0.5) - 0.5
+// rounded ONCE: torch's CPU kernels (built with FMA) and its CUDA kernel (nvcc contracts by default) both evaluate it as one
+// fused multiply-add, and a separately rounded product moves the lambda of ~8 % of rows by an ulp of the source index
+// (tests/test_gpu_lift.py: up to 2^-19.5 of the corner rows at 1232 x 1616)
 __device__ __forceinline__ void src_index(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
     if (src < 0.0f) src = 0.0f;
     int a = (int)src;
     if (a > in_size - 1) a = in_size - 1;
