@@ -50,6 +50,14 @@ int vfm_debug_mx6_half_err(const void *prepared, int64_t rows, int d, float *err
  * list, [1] = the list overflowed (every hypothesis scored in fp64), [2] = the point-wise fp32 pass was needed.  Synchronises. */
 int vfm_debug_ransac_counts(const void *ws, int64_t c_max, int32_t n_iter, int32_t *out_host);
 
+/* tests: where vfm_vit_forward(cfg, ..., B, ...) keeps its buffers inside the caller's workspace, in the order x (fp32 [M][dim] residual
+ * stream), a (fp16 fragment tiles: im2col, then the attention output), xh (fp16 fragment copy of x), stats (fp32 [M][dim / 32][2]), h (fp16
+ * fragment tiles [M][mlp_dim]), q, k (fp16 fragments per (image, head): [Tp][64]), vt (per (image, head): [64][Tp]); M = B * Tp, Tp = tokens
+ * padded to 32.  offsets_host / bytes_host: HOST int64[8]; bytes = the extent up to the next buffer (padding to 256 bytes included).  Computed
+ * by the forward's own carving routine.  After a forward the buffers hold what the LAST block left: q / k / vt are not written under
+ * "vit_fused_qkv", h is not written under "vit_fused_mlp".  Does not touch the device. */
+int vfm_debug_vit_workspace_layout(const vfm_vit_config *cfg, int B, int64_t *offsets_host, int64_t *bytes_host);
+
 #ifdef __cplusplus
 }
 #endif

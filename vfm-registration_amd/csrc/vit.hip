@@ -1902,6 +1902,23 @@ VFM_EXPORT size_t vfm_vit_workspace_bytes(const vfm_vit_config* cfg, int B) {
     return carve_vit(nullptr, make_dims(cfg, B, 1, 1)).bytes;
 }
 
+// (include/vfmreg_debug.h) where vfm_vit_forward keeps x, a, xh, stats, h, q, k, vt inside its workspace: carve_vit itself, run on a base
+// address that is never dereferenced, so the table cannot drift from what the forward uses
+VFM_EXPORT int vfm_debug_vit_workspace_layout(const vfm_vit_config* cfg, int B, int64_t* offsets_host, int64_t* bytes_host) {
+    VFM_CHECK_ARG(cfg && offsets_host && bytes_host && B >= 1, "vit_workspace_layout: bad argument");
+    VFM_CHECK_ARG(cfg->dim >= 64 && cfg->dim % 64 == 0 && cfg->mlp_dim >= 64 && cfg->patch == 14 && cfg->patch_h >= 1 && cfg->patch_w >= 1,
+                  "vit_workspace_layout: bad config");
+    const uintptr_t base = (uintptr_t)1 << 30;
+    const VitWs w = carve_vit(reinterpret_cast<void*>(base), make_dims(cfg, B, 1, 1));
+    const uintptr_t at[9] = {(uintptr_t)w.x, (uintptr_t)w.a, (uintptr_t)w.xh, (uintptr_t)w.stats, (uintptr_t)w.h,
+                             (uintptr_t)w.q, (uintptr_t)w.k, (uintptr_t)w.vt, base + w.bytes};
+    for (int i = 0; i < 8; ++i) {
+        offsets_host[i] = (int64_t)(at[i] - base);
+        bytes_host[i] = (int64_t)(at[i + 1] - at[i]);   // up to the next buffer: the carver's padding to 256 bytes included
+    }
+    return VFM_OK;
+}
+
 VFM_EXPORT int vfm_vit_forward(const vfm_vit_config* cfg, const void* weights, const uint8_t* img, int B, int H, int W,
                                float* tokens_out, void* ws, size_t ws_bytes, vfm_stream_t stream) {
     VFM_CHECK_ARG(cfg && weights && img && tokens_out && ws, "vit: null pointer");

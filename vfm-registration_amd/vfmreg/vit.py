@@ -187,18 +187,19 @@ def to_frag_f16(W: np.ndarray, k_multiple: int = 16) -> np.ndarray:
 class ViTS14:
     """Device-resident DINOv2 ViT-S/14 + ChannelNorm for one input resolution."""
 
-    def __init__(self, weights: Dict[str, np.ndarray], img_h: int, img_w: int, device="cuda"):
+    def __init__(self, weights: Dict[str, np.ndarray], img_h: int, img_w: int, device="cuda", patch_h: int = PATCH_H):
         lib = _lib.load()
         self.device = torch.device(device)
         self.img_h, self.img_w = img_h, img_w
-        scale = (PATCH * PATCH_H) / img_h            # image_features.py:68
+        self.patch_h = int(patch_h)                  # patch rows the image is resized to (the reference: 16)
+        scale = (PATCH * self.patch_h) / img_h       # image_features.py:68
         self.patch_w = int(scale * img_w / PATCH)    # image_features.py:69
         dim = weights["patch_embed.proj.weight"].shape[0]
         depth = 0
         while f"blocks.{depth}.norm1.weight" in weights:
             depth += 1
         mlp = weights["blocks.0.mlp.fc1.weight"].shape[0]
-        self.cfg = _lib.VitConfig(dim, depth, dim // 64, mlp, PATCH, PATCH_H, self.patch_w)
+        self.cfg = _lib.VitConfig(dim, depth, dim // 64, mlp, PATCH, self.patch_h, self.patch_w)
         self.dim = dim
         nseg = 3 + 12 * depth + 4
         offs = (C.c_int64 * nseg)()
@@ -214,7 +215,7 @@ class ViTS14:
             blob[offs[i]:offs[i] + raw.size] = raw
 
         g = lambda k: np.asarray(weights[k], dtype=np.float32)
-        pos = interpolate_pos_embed(g("pos_embed"), PATCH_H, self.patch_w)
+        pos = interpolate_pos_embed(g("pos_embed"), self.patch_h, self.patch_w)
         cls_pos = pos.copy()
         cls_pos[0] += g("cls_token").reshape(-1)
         put(0, to_frag_f16(g("patch_embed.proj.weight").reshape(dim, -1), 32))   # (588 -> 608 columns: whole stages of two k-steps, csrc/vit.hip)
@@ -256,7 +257,7 @@ class ViTS14:
     SPLIT_FROM = 0
 
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None, _slot: int = 0) -> torch.Tensor:
-        """images: [B, H, W, 3] uint8 on the device -> [B, 16, pw, dim] fp32 patch features (written into ``out`` when given:
+        """images: [B, H, W, 3] uint8 on the device -> [B, patch_h (16), pw, dim] fp32 patch features (written into ``out`` when given:
         a consumer that holds pointers into it -- ops.LiftPlan -- then needs no re-marshalling)."""
         ops._chk(images, torch.uint8, "images")
         B, H, W, _ = images.shape
@@ -264,10 +265,10 @@ class ViTS14:
             raise ValueError("Invalid shape")
         lib = _lib.load()
         if out is None:
-            out = torch.empty((B, PATCH_H, self.patch_w, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((B, self.patch_h, self.patch_w, self.dim), dtype=torch.float32, device=self.device)
         else:
             ops._chk(out, torch.float32, "out")
-            if tuple(out.shape) != (B, PATCH_H, self.patch_w, self.dim):
+            if tuple(out.shape) != (B, self.patch_h, self.patch_w, self.dim):
                 raise ValueError("Invalid shape")
         if self.SPLIT_FROM and B >= self.SPLIT_FROM and _slot == 0:
             if self._side is None:
