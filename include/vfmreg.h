@@ -496,6 +496,19 @@ int vfm_icp_nearest(const double *src, int64_t n, const int64_t *keys, const int
                     const double *pts, int32_t n_voxels, double voxel_size, double max_dist,
                     double *tgt_out, uint8_t *valid_out, vfm_stream_t stream);
 
+/* That grid, built on the device from n points (xyz: n x 3 fp64, device memory, in insertion order) in one enqueue without a host
+ * synchronisation: the keys above, a STABLE sort of (key, input index), and of every voxel the first max_points_per_voxel points in
+ * input order (0 = all of them) -- VoxelBlock::AddPoint's cap (VoxelHashMap.hpp:55-62), so a cloud goes in as VoxelHashMap::AddPoints
+ * would take it.  The caller sizes keys_out for n, start_out for n + 1 and pts_out for 3 n; written are keys_out[0, n_voxels),
+ * start_out[0, n_voxels] and pts_out[0, n_kept)[3], and info_out (int32[3], device memory) = {n_voxels, n_kept, status}.  status != 0:
+ * a voxel coordinate with |v| >= 2^20 - 1 (the key holds 21 bits per axis, the search reaches v +- 1) -- the grid is then not to be
+ * used.  n == 0 is an empty grid (start_out[0] = 0; xyz, keys_out, pts_out and ws may be NULL).  n <= 2^30.
+ * vfm_icp_grid_workspace_bytes: the scratch the build needs for n points; nothing outside ws[0, ws_bytes) is touched. */
+size_t vfm_icp_grid_workspace_bytes(int64_t n);
+int vfm_icp_grid_build(const double *xyz, int64_t n, double voxel_size, int32_t max_points_per_voxel, int64_t *keys_out,
+                       int32_t *start_out, double *pts_out, int32_t *info_out, void *ws, size_t ws_bytes,
+                       vfm_stream_t stream);
+
 /* One Gauss-Newton iteration's device work in one launch: src_out = T[:3,:] @ [src; 1] (Registration.cpp:178-179 -- the
  * arithmetic of vfm_transform_xyz_f64; T_host: 16 fp64 in HOST memory, row-major, read at the call) followed by
  * vfm_icp_nearest on the moved points.  src_out may equal src. */

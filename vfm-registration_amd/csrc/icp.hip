@@ -15,6 +15,8 @@
 // as in oracle/vfm_oracle.c; the reduction is a fixed tree (thread t owns pairs i = t mod 256 in
 // ascending order, then a stride-halving tree), which the oracle replays, so every iterate is
 // bit-identical to the oracle's (TBB's reduction order in the reference is unspecified).
+#include <hipcub/hipcub.hpp>
+
 #include "common.h"
 
 namespace {
@@ -288,7 +290,162 @@ __global__ __launch_bounds__(256) void icp_system_kernel(const double* __restric
     if (t == 0) out[k] = red[0];
 }
 
+// ---- The grid itself, built on the device (vfm_icp_grid_build): key of every point -> stable radix sort of (key, input index) -> run
+// starts and "among the first `cap` of its run" flags -> two prefix sums -> one compaction.  A point's place in the output is a pure
+// function of the sorted sequence (no atomic decides an order); the one atomic raises the out-of-range flag.
+constexpr int64_t ICP_GRID_MAX_POINTS = (int64_t)1 << 30;   // int32 positions and prefix sums
+
+__global__ __launch_bounds__(256) void icp_grid_keys_kernel(const double* __restrict__ xyz, int64_t n, double voxel_size,
+                                                            long long* __restrict__ keys, int* __restrict__ idx, int* __restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    // v = trunc(xyz / voxel_size), a true division; the key holds 21 bits per axis and the 27-neighbour scan reaches v +- 1
+    const double lim = (double)((1 << 20) - 1);
+    int v[3];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double t = trunc(xyz[3 * i + c] / voxel_size);
+        const bool ok = fabs(t) < lim;   // (false for NaN too)
+        bad = bad || !ok;
+        v[c] = ok ? (int)t : 0;
+    }
+    if (bad) atomicOr(status, 1);
+    keys[i] = voxel_key(v[0], v[1], v[2]);
+    idx[i] = (int)i;
+}
+
+// head[i]: sorted position i opens a run of equal keys; keep[i]: it is among the first `cap` positions of its run (cap 0: all) --
+// position i - cap carries another key, or does not exist
+__global__ __launch_bounds__(256) void icp_grid_flags_kernel(const long long* __restrict__ ks, int64_t n, int cap, int* __restrict__ head,
+                                                             int* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long k = ks[i];
+    head[i] = (i == 0 || ks[i - 1] != k) ? 1 : 0;
+    keep[i] = (cap <= 0 || i < cap || ks[i - cap] != k) ? 1 : 0;
+}
+
+// vid / kpos: inclusive sums of head / keep.  A run's first point is always kept, so its voxel starts at kpos - 1.
+__global__ __launch_bounds__(256) void icp_grid_compact_kernel(const double* __restrict__ xyz, int64_t n, const long long* __restrict__ ks,
+                                                               const int* __restrict__ order, const int* __restrict__ head,
+                                                               const int* __restrict__ keep, const int* __restrict__ vid,
+                                                               const int* __restrict__ kpos, const int* __restrict__ status,
+                                                               long long* __restrict__ keys_out, int* __restrict__ start_out,
+                                                               double* __restrict__ pts_out, int* __restrict__ info_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int v = vid[i], k = kpos[i];
+    if (head[i]) {
+        keys_out[v - 1] = ks[i];
+        start_out[v - 1] = k - 1;
+    }
+    if (keep[i]) {
+        const int64_t s = order[i];
+        const int64_t j = k - 1;
+        pts_out[3 * j] = xyz[3 * s];
+        pts_out[3 * j + 1] = xyz[3 * s + 1];
+        pts_out[3 * j + 2] = xyz[3 * s + 2];
+    }
+    if (i == n - 1) {
+        start_out[v] = k;
+        info_out[0] = v;
+        info_out[1] = k;
+        info_out[2] = *status;
+    }
+}
+
+__global__ void icp_grid_empty_kernel(int* __restrict__ start_out, int* __restrict__ info_out) {
+    if (threadIdx.x == 0) {
+        start_out[0] = 0;
+        info_out[0] = 0;
+        info_out[1] = 0;
+        info_out[2] = 0;
+    }
+}
+
+size_t icp_grid_cub_bytes(int64_t n) {
+    const int ni = (int)(n > 0 ? n : 1);
+    size_t best = 0, b = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (long long*)nullptr, (long long*)nullptr, (int*)nullptr, (int*)nullptr, ni, 0, 63);
+    best = b > best ? b : best;
+    b = 0;
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, (int*)nullptr, (int*)nullptr, ni);
+    best = b > best ? b : best;
+    return best + 1024;
+}
+
+struct IcpGridWs {
+    long long* keys_in;
+    int* idx_in;
+    long long* keys;   // sorted
+    int* order;        // input index of every sorted position
+    int* head;
+    int* keep;
+    int* vid;
+    int* kpos;
+    int* status;
+    void* cub;
+    size_t cub_bytes;
+};
+
+IcpGridWs carve_icp_grid(void* p, int64_t n, size_t* used = nullptr) {
+    VfmCarver c(p);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    IcpGridWs w{};
+    w.keys_in = c.take<long long>(nn);
+    w.idx_in = c.take<int>(nn);
+    w.keys = c.take<long long>(nn);
+    w.order = c.take<int>(nn);
+    w.head = c.take<int>(nn);
+    w.keep = c.take<int>(nn);
+    w.vid = c.take<int>(nn);
+    w.kpos = c.take<int>(nn);
+    w.status = c.take<int>(1);
+    w.cub_bytes = icp_grid_cub_bytes(n);
+    w.cub = c.take<unsigned char>(w.cub_bytes);
+    if (used) *used = c.used();
+    return w;
+}
+
 }  // namespace
+
+VFM_EXPORT size_t vfm_icp_grid_workspace_bytes(int64_t n) {
+    size_t used = 0;
+    (void)carve_icp_grid(nullptr, n < 0 ? 0 : (n > ICP_GRID_MAX_POINTS ? ICP_GRID_MAX_POINTS : n), &used);   // (a null base: only the offsets)
+    return used;
+}
+
+VFM_EXPORT int vfm_icp_grid_build(const double* xyz, int64_t n, double voxel_size, int32_t max_points_per_voxel, int64_t* keys_out,
+                                  int32_t* start_out, double* pts_out, int32_t* info_out, void* ws, size_t ws_bytes, vfm_stream_t stream) {
+    VFM_CHECK_ARG(n >= 0 && n <= ICP_GRID_MAX_POINTS && voxel_size > 0.0 && max_points_per_voxel >= 0, "icp_grid_build: bad arguments");
+    VFM_CHECK_ARG(start_out && info_out, "icp_grid_build: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        hipLaunchKernelGGL(icp_grid_empty_kernel, dim3(1), dim3(64), 0, st, start_out, info_out);
+        VFM_CHECK_LAUNCH("icp_grid_empty_kernel");
+        return VFM_OK;
+    }
+    VFM_CHECK_ARG(xyz && keys_out && pts_out && ws, "icp_grid_build: null pointer");
+    VFM_CHECK_ARG(ws_bytes >= vfm_icp_grid_workspace_bytes(n), "icp_grid_build: workspace too small");
+    IcpGridWs w = carve_icp_grid(ws, n);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    VFM_CHECK_HIP(hipMemsetAsync(w.status, 0, sizeof(int), st));
+    hipLaunchKernelGGL(icp_grid_keys_kernel, grid, block, 0, st, xyz, n, voxel_size, w.keys_in, w.idx_in, w.status);
+    VFM_CHECK_LAUNCH("icp_grid_keys_kernel");
+    size_t tb = w.cub_bytes;
+    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, w.keys, w.idx_in, w.order, (int)n, 0, 63, st));
+    hipLaunchKernelGGL(icp_grid_flags_kernel, grid, block, 0, st, w.keys, n, (int)max_points_per_voxel, w.head, w.keep);
+    VFM_CHECK_LAUNCH("icp_grid_flags_kernel");
+    tb = w.cub_bytes;
+    VFM_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, tb, w.head, w.vid, (int)n, st));
+    tb = w.cub_bytes;
+    VFM_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, tb, w.keep, w.kpos, (int)n, st));
+    hipLaunchKernelGGL(icp_grid_compact_kernel, grid, block, 0, st, xyz, n, w.keys, w.order, w.head, w.keep, w.vid, w.kpos, w.status,
+                       reinterpret_cast<long long*>(keys_out), start_out, pts_out, info_out);
+    VFM_CHECK_LAUNCH("icp_grid_compact_kernel");
+    return VFM_OK;
+}
 
 VFM_EXPORT int vfm_icp_nearest(const double* src, int64_t n, const int64_t* keys, const int32_t* start, const double* pts,
                                int32_t n_voxels, double voxel_size, double max_dist, double* tgt_out, uint8_t* valid_out,

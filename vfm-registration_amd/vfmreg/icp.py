@@ -58,18 +58,88 @@ class VoxelGridDevice:
         uniq, first = np.unique(ks, return_index=True)
         self.voxel_size = float(voxel_size)
         self.n_voxels = len(uniq)
+        self.n_kept = len(ks)
         self.keys = torch.from_numpy(np.ascontiguousarray(uniq)).cuda()
         self.start = torch.from_numpy(np.r_[first, len(ks)].astype(np.int32)).cuda()
         self.pts = torch.from_numpy(np.ascontiguousarray(pts[order])).cuda()
+
+    @classmethod
+    def from_device(cls, xyz64: torch.Tensor, voxel_size: float, max_points_per_voxel: int = 0) -> "VoxelGridDevice":
+        """The same grid from points that are on the device already, in insertion order (csrc/icp.hip vfm_icp_grid_build: keys, a stable
+        radix sort, run starts by a scan, compaction; nothing is downloaded but the three counters).  ``max_points_per_voxel`` > 0 keeps
+        the first that many points of every voxel -- VoxelHashMap::AddPoints' cap -- so a raw cloud gives the grid of the map built from
+        it: "cap, then stable sort by key" and "stable sort by key, then the first K of every run" select the same points in the same
+        order, and the container's iteration order (voxel-contiguous, insertion order inside a voxel) sorts to that order as well."""
+        xyz64 = ops._chk(xyz64, torch.float64, "xyz64")
+        if xyz64.dim() != 2 or xyz64.shape[1] != 3:
+            raise ValueError("Invalid shape")
+        lib = _lib.load()
+        n = xyz64.shape[0]
+        dev = xyz64.device
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        start = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        pts = torch.empty((max(n, 1), 3), dtype=torch.float64, device=dev)
+        info = torch.empty(3, dtype=torch.int32, device=dev)
+        ws = ops._ws(lib.vfm_icp_grid_workspace_bytes(n), dev)
+        _lib.check(lib.vfm_icp_grid_build(xyz64.data_ptr(), n, float(voxel_size), int(max_points_per_voxel), keys.data_ptr(), start.data_ptr(),
+                                          pts.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "icp_grid_build")
+        info_h = getattr(ops._tls, "icp_grid_info", None)   # page-locked: the build's one read-back
+        if info_h is None:
+            info_h = ops._tls.icp_grid_info = torch.zeros(3, dtype=torch.int32).pin_memory()
+        info_h.copy_(info, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        n_voxels, n_kept, status = info_h.tolist()
+        if status:
+            raise ValueError("voxel coordinate outside +-2^20 voxels: shift the clouds towards the origin "
+                             "(the ICP grid key holds 21 bits per axis)")
+        g = cls.__new__(cls)
+        g.voxel_size = float(voxel_size)
+        g.n_voxels = n_voxels
+        g.n_kept = n_kept
+        g.keys = keys[:n_voxels]
+        g.start = start[:n_voxels + 1]
+        g.pts = pts[:n_kept]
+        return g
+
+
+def _map_xyz_in_insertion_order(voxel_map):
+    """(kept-row count, the map's kept 3-D points on the device) of the cloud ``point_cloud()`` returns (map_, else map_n_:
+    VoxelHashMap.cpp:631-659) -- in container order where the map has computed it, else in insertion order: both sort to the same grid,
+    and the second does not need the container's replay (ops.voxel_robin)."""
+    for kind in ("3", "n"):
+        chunks = voxel_map._chunks.get(kind)
+        if not chunks:
+            continue
+        if kind in voxel_map._ordered:
+            xyz = voxel_map._ordered[kind][1]
+        else:
+            xyz = torch.cat([x for _, x in chunks], dim=0) if len(chunks) > 1 else chunks[0][1]
+        return xyz.shape[0], xyz
+    return 0, None
 
 
 def _grid_of(voxel_map) -> "VoxelGridDevice":
     """the sorted-key CSR of the map's 3-D points, kept with the map (VoxelHashMap.add_points drops it)"""
     grid = getattr(voxel_map, "_icp_grid", None)
-    if grid is None or grid[0] != len(voxel_map.point_cloud()):
-        grid = (len(voxel_map.point_cloud()), VoxelGridDevice(voxel_map.point_cloud(), voxel_map.voxel_size))
+    count, xyz = _map_xyz_in_insertion_order(voxel_map)
+    if grid is None or grid[0] != count:
+        if xyz is None:
+            xyz = torch.zeros((0, 3), dtype=torch.float64, device="cuda")
+        # (every stored row is a kept one: the cap has been applied by add_points)
+        grid = (count, VoxelGridDevice.from_device(xyz.contiguous(), voxel_map.voxel_size))
         voxel_map._icp_grid = grid
     return grid[1]
+
+
+def register_frame_on_grid(src: torch.Tensor, grid: "VoxelGridDevice", initial_guess: np.ndarray, max_correspondance_distance: float,
+                           kernel: float) -> np.ndarray:
+    """RegisterFrame on 3-D points (Registration.cpp:145-195) that are on the device, against a grid built before: what
+    ``register_frame`` runs for 3 columns once it has the map's grid."""
+    initial_guess = np.ascontiguousarray(initial_guess, dtype=np.float64)
+    if grid.n_kept == 0:
+        return initial_guess  # Registration.cpp:150
+    T_icp, _, _ = _icp_loop(src, grid, initial_guess, max_correspondance_distance, kernel, MAX_NUM_ITERATIONS)
+    return T_icp @ initial_guess
 
 
 def _icp_loop(cur: torch.Tensor, g: "VoxelGridDevice", first_step, max_correspondance_distance: float, kernel: float,

@@ -3,7 +3,7 @@
   compute_vfm_correspondences  RN:396-425      ransac_registration('vfm')  RN:273-357
   find_correspondences         RN:482-538      compute_errors              RN:997-1019
   compute_correspondences      RN:427-547 (the FPFH baseline; the learned baselines raise NotImplementedError)
-  rotation re-orthogonalisation RN:331-336
+  rotation re-orthogonalisation RN:331-336     icp_registration            RN:359-394
 
 Same names, argument meaning and return values; numpy in / numpy out.  The ROS node, the learned baseline
 descriptors, TEASER and PointDSC are out of scope.  ``run_icp=True`` runs the point-to-point ICP
@@ -234,6 +234,25 @@ class RegistrationNode:
         raw_idx5 = h[24:24 + n3].copy() if n3 <= head else l3["keep"][:n3].cpu().numpy()
         return raw_xyz[raw_of_voxel_scan], raw_of_voxel_scan, l3["local"][:n3], raw_idx5
 
+    def _voxel_scan(self, raw_xyz: torch.Tensor, vs: float) -> torch.Tensor:
+        """RN:361-362 / 399-400 on device-resident 3-D points: VoxelDownsample at vs / 2, then at vs on its survivors in ITS order --
+        two launches of the chain's kernel and one read-back, or level by level where that kernel does not reproduce a level."""
+        n = raw_xyz.shape[0]
+        if n == 0:
+            return raw_xyz
+        if n <= (1 << 18):
+            l1 = ops.voxel_robin_level(raw_xyz, vs * 0.5)
+            l2 = ops.voxel_robin_level(raw_xyz, vs * 1.0, idx=l1["keep"], n_dev=l1["count"], n_max=n)
+            if self._chain_host is None:
+                self._chain_host = torch.empty(24 + self._CHAIN_HEAD, dtype=torch.int64).pin_memory()
+            self._chain_host[:16].copy_(torch.cat((l1["info"], l2["info"])), non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            h = self._chain_host.numpy()
+            if all(h[8 * k + 5] == 1 and h[8 * k + 1] > 0 for k in range(2)):
+                return raw_xyz[l2["keep"][:int(h[9])]]
+        xyz = raw_xyz[ops.voxel_robin(raw_xyz, vs * 0.5)]
+        return xyz[ops.voxel_robin(xyz, vs * 1.0)]
+
     _CHAIN_HEAD = 8192   # rows of the 5 m level read back together with the levels' infos (more: a second read-back)
 
     @staticmethod
@@ -276,6 +295,60 @@ class RegistrationNode:
                                   max_correspondance_distance=3 * sigma, kernel=sigma / 3)   # RN:340-344
             return ransac_pose, pose
         return ransac_pose, None
+
+    def icp_registration(self, voxel_map, raw_scan, initial_pose=None, dist=3):
+        """RN:359-394: point-to-point ICP of a scan against a map, both voxelised the way the node does it -- the ground truth of the
+        evaluation loop (RN:646) and its vanilla-ICP row (RN:929, ``dist=7``).  The scan is down-sampled at 0.5 x and then 1.0 x the
+        map's voxel size (RN:361-362); the map is a fresh ``get_voxel_hash_map(config)`` filled with ``voxel_map`` (RN:364-365).
+
+        3-column clouds never build that container: the map goes from the upload into ``vfm_icp_grid_build`` with the config's
+        points-per-voxel cap (the grid ``register_frame`` would build from the container's ``point_cloud()``: same voxels, same kept
+        points, same order inside a voxel), the scan's two levels run on the device, and the 3-D loop of ``vfmreg.icp`` does the rest.
+        Other widths call ``register_frame`` with ``src_`` / ``tgt_`` as RN:382-389 does and return the pose (the correspondence
+        publisher of RN:392 is out of scope).  A ``MapHandle`` is taken wherever an array is; its grid stays with it between calls."""
+        from .icp import VoxelGridDevice, _grid_of, register_frame_on_grid
+        from .mapping import VoxelHashMap
+        vs = self.config.mapping.voxel_size
+        scan = np.asarray(raw_scan)
+        if scan.ndim != 2 or scan.shape[1] < 3:
+            raise ValueError("Invalid shape")
+        handle = voxel_map if isinstance(voxel_map, MapHandle) else None
+        vm = None if handle is not None else np.asarray(voxel_map)
+        if vm is not None and (vm.ndim != 2 or vm.shape[1] < 3):
+            raise ValueError("Invalid shape")
+        map_cols = handle.cols if handle is not None else vm.shape[1]
+        sigma = self.config.adaptive_threshold.initial_threshold                          # RN:372
+        if initial_pose is None:
+            initial_pose = np.eye(4)                                                      # RN:373-374
+        initial_pose = np.ascontiguousarray(initial_pose, dtype=np.float64)
+        if scan.shape[1] == 3 and map_cols == 3:
+            raw_xyz = torch.from_numpy(np.ascontiguousarray(scan, dtype=np.float64)).cuda()
+            xyz = self._voxel_scan(raw_xyz, vs)                                           # RN:361-362
+            if handle is not None:
+                grid = _grid_of(handle.voxel_hash_map)
+            else:                                                                         # RN:364-365 without the container
+                m_xyz = torch.from_numpy(np.ascontiguousarray(vm, dtype=np.float64)).cuda()
+                grid = VoxelGridDevice.from_device(m_xyz, vs, self.config.mapping.max_points_per_voxel)
+            if not VoxelHashMap.quiet:
+                print(f"Map size: {grid.n_kept}, Scan size: {xyz.shape[0]}")             # RN:368
+            return register_frame_on_grid(xyz, grid, initial_pose, dist * sigma, sigma / dist)   # RN:376-380
+        downsample_scan = voxel_down_sample(scan, vs * 0.5)                               # RN:361
+        voxel_scan = voxel_down_sample(downsample_scan, vs * 1.0)                         # RN:362
+        if handle is not None:
+            voxel_hash_map = handle.voxel_hash_map
+        else:
+            voxel_hash_map = get_voxel_hash_map(self.config)                              # RN:364-365
+            voxel_hash_map.add_points(vm)
+        if not VoxelHashMap.quiet:
+            kept = sum(len(x) for _, x in (voxel_hash_map._chunks.get("3") or voxel_hash_map._chunks.get("n") or []))
+            print(f"Map size: {kept}, Scan size: {voxel_scan.shape[0]}")                  # RN:367-368 (the kept rows: no download)
+        if scan.shape[1] == 3:
+            return register_frame(points=voxel_scan, voxel_map=voxel_hash_map, initial_guess=initial_pose,
+                                  max_correspondance_distance=dist * sigma, kernel=sigma / dist)     # RN:376-380
+        src_, tgt_ = np.array([[0, 0, 0]]), np.array([[0, 0, 0]])                         # RN:382
+        out = register_frame(points=voxel_scan, voxel_map=voxel_hash_map, initial_guess=initial_pose,
+                             max_correspondance_distance=dist * sigma, kernel=sigma / dist, src_=src_, tgt_=tgt_)   # RN:383-389
+        return out[0] if isinstance(out, tuple) else out
 
     _LEARNED = ("dip", "gedi", "fcgf", "gcl", "spinnet")
 
