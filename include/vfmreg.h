@@ -572,6 +572,27 @@ int vfm_fpfh_spfh(const double *pts, const double *normals, int64_t n, const int
 int vfm_fpfh_fpfh(const double *spfh, int64_t n, const int32_t *nbr_idx, const double *nbr_d2, const int32_t *nbr_cnt,
                   int32_t max_nn, double *fpfh_out, vfm_stream_t stream);
 
+/* ------------------------------------------------------------------ exact 1-NN in 3-D (row recovery of the baselines) */
+
+/* sklearn.neighbors.KDTree(X, metric="euclidean").query(Q, k=1) of src/vfm-reg/src/registration_node.py:295-298: the row of the
+ * nearest point of a cloud for every query, over ALL n points (no radius), exact wherever the query lies.  Points and queries are
+ * rows of 3 fp64 with finite coordinates; d2 = (dx*dx + dy*dy) + dz*dz in fp64 without contraction, dist = sqrt(d2), equal d2 to
+ * the lower index (a convention of this library).  An empty cloud has no nearest point: n == 0 is VFM_EINVAL in all three.
+ * Nothing here synchronises `stream` or keeps state between calls.
+ * vfm_nn3_workspace_bytes: the workspace of vfm_nn3_build for n points. */
+size_t vfm_nn3_workspace_bytes(int64_t n);
+/* The search structure: a sorted-key CSR grid of cubic cells of edge `cell` (the caller's choice: it changes the time, never the
+ * answer).  keys_out (int64[n]) the cell keys ascending, order_out (int32[n]) the point indices in that order, sorted_out
+ * (fp64[3 n]) the points in that order. */
+int vfm_nn3_build(const double *pts, int64_t n, double cell, int64_t *keys_out, int32_t *order_out, double *sorted_out, void *ws,
+                  size_t ws_bytes, vfm_stream_t stream);
+/* nq queries against a structure built with the same n and cell: idx_out (int64[nq]), dist_out (fp64[nq]).  A query reads the 27
+ * cells around its own, then shell after shell of cells until its best d2 is below anything outside the searched cube; after 8
+ * shells it reads every point instead.  fallback_count_out (nullable, device int32[1]): set to the number of queries that did.
+ * nq == 0 writes nothing but that count. */
+int vfm_nn3_query(const int64_t *keys, const int32_t *order, const double *sorted, int64_t n, double cell, const double *queries,
+                  int64_t nq, int64_t *idx_out, double *dist_out, int32_t *fallback_count_out, vfm_stream_t stream);
+
 /* ------------------------------------------------------------------ DINOv2 ViT-S/14 (row A1) */
 
 /* self.model.model(img) of IF:101 incl. the transform of IF:67-77: bilinear resize (antialias

@@ -1,0 +1,221 @@
+// nn3.hip -- exact 1-nearest-neighbour search in 3-D on MI355X (gfx950): the two sklearn.neighbors.KDTree(X, metric="euclidean")
+// .query(Q, k=1) calls of registration_node.py:295-298, which recover the row of every correspondence point in the voxelised clouds.
+//   nn3_keys_kernel / nn3_gather_kernel  a sorted-key CSR grid over the cloud (cell = the caller's), points copied in cell order
+//   nn3_query_kernel                     one wave per query: the 27 cells around the query, then shells of cells, until the best d2
+//                                        is below anything a cell outside the searched cube can hold; past NN3_MAX_RINGS shells a scan
+//                                        of every point (queries far from the cloud, or in its empty regions)
+// fp64, -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, dist = sqrt(d2) (correctly rounded), equal d2 to the lower index (a
+// convention of this library; sklearn leaves it unspecified).  tests/nn3_oracle.py repeats it in numpy.
+#include <hipcub/hipcub.hpp>
+
+#include "common.h"
+
+namespace {
+
+constexpr int64_t NN3_MAX_POINTS = (int64_t)1 << 26;
+constexpr int NN3_MAX_RINGS = 8;                 // shells searched around the query's cell before the scan of all points
+constexpr int NN3_LIM = (1 << 20) - 16;          // cells are clamped to +-NN3_LIM: cell +- NN3_MAX_RINGS still fits the key's 21 bits
+// Points in a cell more than r cells from the query's (in some axis) are, in that axis, more than r - 2^-31 cells away (the two
+// products x * inv_cell are rounded; clamped cells only move closer together), and rounding is monotone, so their computed d2 is at
+// least that squared.  The bound used is r cells shortened by 1e-6 relative: far more than every rounding on the way.
+constexpr double NN3_RING_SLACK = 1.0 - 1e-6;
+
+__device__ __forceinline__ long long nn3_cell(double x, double inv_cell) {
+    double c = floor(x * inv_cell);
+    c = fmin(fmax(c, (double)-NN3_LIM), (double)NN3_LIM);   // (NaN -> -NN3_LIM)
+    return (long long)c;
+}
+__device__ __forceinline__ long long nn3_key(long long cx, long long cy, long long cz) {
+    return ((cx + (1 << 20)) << 42) | ((cy + (1 << 20)) << 21) | (cz + (1 << 20));
+}
+
+__global__ __launch_bounds__(256) void nn3_keys_kernel(const double* __restrict__ pts, int64_t n, double inv_cell,
+                                                       long long* __restrict__ keys, int* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = nn3_key(nn3_cell(pts[3 * i], inv_cell), nn3_cell(pts[3 * i + 1], inv_cell), nn3_cell(pts[3 * i + 2], inv_cell));
+    idx[i] = (int)i;
+}
+
+__global__ __launch_bounds__(256) void nn3_gather_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ order,
+                                                         double* __restrict__ sorted) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = order[i];
+    sorted[3 * i] = pts[3 * j];
+    sorted[3 * i + 1] = pts[3 * j + 1];
+    sorted[3 * i + 2] = pts[3 * j + 2];
+}
+
+__device__ __forceinline__ int nn3_lower_bound(const long long* __restrict__ a, int n, long long key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct Nn3Best {
+    double d2;
+    int idx;
+};
+
+__device__ __forceinline__ void nn3_take(Nn3Best& b, double d2, int j) {
+    if (d2 < b.d2 || (d2 == b.d2 && j < b.idx)) {
+        b.d2 = d2;
+        b.idx = j;
+    }
+}
+
+// the points sorted[lo, lo + len) against the query, a lane per point
+__device__ __forceinline__ void nn3_scan_run(Nn3Best& b, const double* __restrict__ sorted, const int* __restrict__ order, int lo, int len,
+                                             double qx, double qy, double qz, int lane) {
+    for (int t = lane; t < len; t += 64) {
+        const int64_t s = lo + t;
+        const double dx = sorted[3 * s] - qx, dy = sorted[3 * s + 1] - qy, dz = sorted[3 * s + 2] - qz;
+        nn3_take(b, (dx * dx + dy * dy) + dz * dz, order[s]);
+    }
+}
+
+__device__ __forceinline__ Nn3Best nn3_wave_best(Nn3Best b) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double od = __shfl_xor(b.d2, off);
+        const int oi = __shfl_xor(b.idx, off);
+        nn3_take(b, od, oi);
+    }
+    return b;   // the same in every lane
+}
+
+// One wave (= one workgroup) per query.  Shell r is walked by columns (ax, ay) of the (2r + 1)^2 square: the z-cells of a column are
+// consecutive keys, so a column on the square's border is ONE run of keys (cz - r .. cz + r) and a column inside it two single
+// cells (cz - r and cz + r).  64 columns at a time find their runs with two binary searches per lane; the wave then reads each
+// non-empty run together, a lane per point, from the copy of the cloud kept in cell order.
+__global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict__ sorted, const long long* __restrict__ keys,
+                                                       const int* __restrict__ order, int n, double inv_cell, double cell,
+                                                       const double* __restrict__ q, int64_t nq, int64_t* __restrict__ idx_out,
+                                                       double* __restrict__ dist_out, int* __restrict__ fallback_count) {
+    const int64_t qi = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
+    const long long cx = nn3_cell(qx, inv_cell), cy = nn3_cell(qy, inv_cell), cz = nn3_cell(qz, inv_cell);
+    Nn3Best best{INFINITY, 0x7FFFFFFF};
+    bool done = false;
+    for (int r = 1; r <= NN3_MAX_RINGS && !done; ++r) {
+        const int side = 2 * r + 1;
+        const int columns = side * side;
+        for (int base = 0; base < columns; base += 64) {
+            const int t = base + lane;
+            int lo_a = 0, len_a = 0, lo_b = 0, len_b = 0;
+            if (t < columns) {
+                const int dx = t / side - r, dy = t % side - r;
+                const long long ax = cx + dx, ay = cy + dy;
+                const bool whole = r == 1 || dx == -r || dx == r || dy == -r || dy == r;
+                if (whole) {
+                    lo_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r));
+                    len_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r) + 1) - lo_a;
+                } else {
+                    lo_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r));
+                    len_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r) + 1) - lo_a;
+                    lo_b = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r));
+                    len_b = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r) + 1) - lo_b;
+                }
+            }
+            unsigned long long ma = __ballot(len_a > 0);
+            while (ma) {
+                const int src = __ffsll((long long)ma) - 1;
+                ma &= ma - 1;
+                nn3_scan_run(best, sorted, order, __shfl(lo_a, src), __shfl(len_a, src), qx, qy, qz, lane);
+            }
+            unsigned long long mb = __ballot(len_b > 0);
+            while (mb) {
+                const int src = __ffsll((long long)mb) - 1;
+                mb &= mb - 1;
+                nn3_scan_run(best, sorted, order, __shfl(lo_b, src), __shfl(len_b, src), qx, qy, qz, lane);
+            }
+        }
+        best = nn3_wave_best(best);
+        const double reach = ((double)r * cell) * NN3_RING_SLACK;
+        done = best.d2 < reach * reach;
+    }
+    if (!done) {
+        // more shells than the cap: every point (the shells already searched are read again -- the best of all is the best)
+        nn3_scan_run(best, sorted, order, 0, n, qx, qy, qz, lane);
+        best = nn3_wave_best(best);
+        if (fallback_count && lane == 0) atomicAdd(fallback_count, 1);
+    }
+    if (lane == 0) {
+        const bool found = best.idx != 0x7FFFFFFF;   // (not found: every d2 is a NaN)
+        idx_out[qi] = found ? (int64_t)best.idx : (int64_t)-1;
+        dist_out[qi] = found ? sqrt(best.d2) : NAN;
+    }
+}
+
+size_t nn3_cub_bytes(int64_t n) {
+    size_t b = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (long long*)nullptr, (long long*)nullptr, (int*)nullptr, (int*)nullptr,
+                                             (int)(n > 0 ? n : 1), 0, 64);
+    return b + 1024;
+}
+
+struct Nn3Ws {
+    long long* keys_in;
+    int* idx_in;
+    void* cub;
+    size_t cub_bytes;
+};
+
+Nn3Ws carve_nn3(void* p, int64_t n, size_t* used = nullptr) {
+    VfmCarver c(p);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    Nn3Ws w{};
+    w.keys_in = c.take<long long>(nn);
+    w.idx_in = c.take<int>(nn);
+    w.cub_bytes = nn3_cub_bytes(n);
+    w.cub = c.take<unsigned char>(w.cub_bytes);
+    if (used) *used = c.used();
+    return w;
+}
+
+}  // namespace
+
+VFM_EXPORT size_t vfm_nn3_workspace_bytes(int64_t n) {
+    size_t used = 0;
+    (void)carve_nn3(nullptr, n < 0 ? 0 : n, &used);   // (a null base: only the offsets are computed)
+    return used;
+}
+
+VFM_EXPORT int vfm_nn3_build(const double* pts, int64_t n, double cell, int64_t* keys_out, int32_t* order_out, double* sorted_out, void* ws,
+                             size_t ws_bytes, vfm_stream_t stream) {
+    VFM_CHECK_ARG(n >= 1 && n <= NN3_MAX_POINTS, "nn3_build: n must be in 1..2^26 (an empty cloud has no nearest point)");
+    VFM_CHECK_ARG(cell > 0.0 && cell < INFINITY, "nn3_build: the cell size must be positive and finite");
+    VFM_CHECK_ARG(pts && keys_out && order_out && sorted_out && ws, "nn3_build: null pointer");
+    VFM_CHECK_ARG(ws_bytes >= vfm_nn3_workspace_bytes(n), "nn3_build: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    Nn3Ws w = carve_nn3(ws, n);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(nn3_keys_kernel, dim3(blocks), dim3(256), 0, st, pts, n, 1.0 / cell, w.keys_in, w.idx_in);
+    VFM_CHECK_LAUNCH("nn3_keys_kernel");
+    size_t tb = w.cub_bytes;
+    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, reinterpret_cast<long long*>(keys_out), w.idx_in, order_out, (int)n,
+                                                     0, 64, st));
+    hipLaunchKernelGGL(nn3_gather_kernel, dim3(blocks), dim3(256), 0, st, pts, n, order_out, sorted_out);
+    VFM_CHECK_LAUNCH("nn3_gather_kernel");
+    return VFM_OK;
+}
+
+VFM_EXPORT int vfm_nn3_query(const int64_t* keys, const int32_t* order, const double* sorted, int64_t n, double cell, const double* queries,
+                             int64_t nq, int64_t* idx_out, double* dist_out, int32_t* fallback_count_out, vfm_stream_t stream) {
+    VFM_CHECK_ARG(n >= 1 && n <= NN3_MAX_POINTS, "nn3_query: n must be in 1..2^26 (an empty cloud has no nearest point)");
+    VFM_CHECK_ARG(cell > 0.0 && cell < INFINITY, "nn3_query: the cell size must be positive and finite");
+    VFM_CHECK_ARG(nq >= 0 && nq <= 0x7FFFFFFF, "nn3_query: nq must be in 0..2^31-1");
+    hipStream_t st = (hipStream_t)stream;
+    if (fallback_count_out) VFM_CHECK_HIP(hipMemsetAsync(fallback_count_out, 0, sizeof(int32_t), st));
+    if (nq == 0) return VFM_OK;
+    VFM_CHECK_ARG(keys && order && sorted && queries && idx_out && dist_out, "nn3_query: null pointer");
+    hipLaunchKernelGGL(nn3_query_kernel, dim3((unsigned)nq), dim3(64), 0, st, sorted, reinterpret_cast<const long long*>(keys), order, (int)n,
+                       1.0 / cell, cell, queries, nq, idx_out, dist_out, fallback_count_out);
+    VFM_CHECK_LAUNCH("nn3_query_kernel");
+    return VFM_OK;
+}

@@ -167,25 +167,32 @@ class Evaluation:
 
 def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = None,
                    evaluation: Optional[Evaluation] = None, run_icp: bool = True, icp_ground_truth: bool = False,
-                   icp_baseline: bool = False) -> Evaluation:
+                   icp_baseline: bool = False, baselines=()) -> Evaluation:
     """The VFM + RANSAC (+ ICP) branch of make_step for one scene (RN:587-589, 593, 860-882, 943-951):
     every scan is registered against the accumulated map with the identity as initial guess and
     compared with its ground-truth pose.  ``icp_ground_truth``: that pose is the stored one refined by ICP against the map, as the
     reference does it (RN:645-646), for every row; ``icp_baseline``: the vanilla-ICP row ``icp`` of RN:929 (``dist=7``) joins the
-    table.  Both are off by default (the stored pose, no ``icp`` row)."""
-    node = node or RegistrationNode(cache_map=True)   # local_map below is built here and never edited: one map per scene (RN:556-589)
+    table.  Both are off by default (the stored pose, no ``icp`` row).  ``baselines`` (default ``()``): the baseline descriptors of
+    RN:867-874 to run before ``vfm`` -- ``("fpfh",)`` adds the rows ``fpfh_ransac`` and, with ``run_icp``, ``fpfh_ransac_icp``; the node
+    must have been created with the same ``baseline_methods``.  The map's baseline features are computed at the first scan of the
+    scene and kept for the others (RN:876-877)."""
+    node = node or RegistrationNode(cache_map=True, baseline_methods=tuple(baselines))   # local_map below is built here and never edited: one map per scene (RN:556-589)
     ev = evaluation or Evaluation()
     n_desc = scene["map_point_clouds"][0].shape[1] - 3
     local_map = build_local_map(scene["map_poses"], scene["map_point_clouds"], n_descriptors=n_desc)
     # the 3-D map both ICP calls register against: built once per scene and kept with the handle (the reference rebuilds it per call)
     icp_map = node.set_map(np.ascontiguousarray(local_map[:, :3])) if (icp_ground_truth or icp_baseline) else None
-    for gt_pose, point_cloud in zip(scene["scene_poses"], scene["scene_point_clouds"]):
+    for i, (gt_pose, point_cloud) in enumerate(zip(scene["scene_poses"], scene["scene_point_clouds"])):
         point_cloud = voxel_down_sample(point_cloud, .1).astype(point_cloud.dtype)   # RN:593
         if icp_ground_truth:
             gt_pose = node.icp_registration(icp_map, point_cloud[:, :3], np.asarray(gt_pose))   # RN:645-646
         initial_pose = np.eye(4)                                                     # RN:858
         point_cloud = transform_pcl(point_cloud, initial_pose)                       # RN:863
         results = {}
+        if i == 0:
+            node.clear_map_descriptors()                                             # RN:876-877
+        for method in baselines:                                                     # RN:867-883, in the reference's order
+            results[f"{method}_ransac"], results[f"{method}_ransac_icp"] = node.ransac_registration(local_map, point_cloud, method, run_icp)
         results["vfm_ransac"], results["vfm_ransac_icp"] = node.ransac_registration(local_map, point_cloud, "vfm", run_icp)
         if icp_baseline:
             results["icp"] = node.icp_registration(icp_map, point_cloud[:, :3], dist=7)          # RN:929

@@ -581,3 +581,52 @@ def fpfh_fpfh(spfh: torch.Tensor, nbrs: dict) -> torch.Tensor:
     _lib.check(lib.vfm_fpfh_fpfh(spfh.data_ptr(), n, nbrs["idx"].data_ptr(), nbrs["d2"].data_ptr(), nbrs["count"].data_ptr(),
                                  nbrs["idx"].shape[1], out.data_ptr(), _stream()), "fpfh_fpfh")
     return out
+
+
+# ------------------------------------------------------------------------------------- exact 1-NN in 3-D (csrc/nn3.hip)
+class Nn3Grid:
+    """The search structure of ``nn3_build``: sorted cell keys int64[n], point indices in that order int32[n], the points in that
+    order fp64[n, 3], and the cell size they were built with."""
+
+    __slots__ = ("keys", "order", "sorted", "cell", "n")
+
+    def __init__(self, keys, order, sorted_pts, cell, n):
+        self.keys, self.order, self.sorted, self.cell, self.n = keys, order, sorted_pts, float(cell), int(n)
+
+
+def nn3_build(pts: torch.Tensor, cell: float, ws: Optional[torch.Tensor] = None) -> Nn3Grid:
+    """vfm_nn3_build: the grid of cubic cells of edge ``cell`` over an n x 3 fp64 cloud (n >= 1).  The cell size changes the time of
+    a query, never its answer; ``vfmreg.neighbors.choose_cell`` picks one from the cloud."""
+    _chk(pts, torch.float64, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    n = pts.shape[0]
+    if n == 0:
+        raise ValueError("Found array with 0 sample(s) while a minimum of 1 is required")
+    lib = _lib.load()
+    keys = torch.empty(n, dtype=torch.int64, device=pts.device)
+    order = torch.empty(n, dtype=torch.int32, device=pts.device)
+    sorted_pts = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
+    need = lib.vfm_nn3_workspace_bytes(n)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, pts.device)
+    _lib.check(lib.vfm_nn3_build(pts.data_ptr(), n, float(cell), keys.data_ptr(), order.data_ptr(), sorted_pts.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream()), "nn3_build")
+    return Nn3Grid(keys, order, sorted_pts, cell, n)
+
+
+def nn3_query(grid: Nn3Grid, q: torch.Tensor, want_fallbacks: bool = False):
+    """vfm_nn3_query: (idx int64[nq], dist fp64[nq]) of the nearest point of the cloud for every row of ``q`` (nq x 3 fp64) --
+    ``KDTree.query(k=1)`` of registration_node.py:297-298; with ``want_fallbacks`` also int32[1], the number of queries that read every
+    point instead of cells.  No read-back."""
+    _chk(q, torch.float64, "q")
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    lib = _lib.load()
+    nq = q.shape[0]
+    idx = torch.empty(nq, dtype=torch.int64, device=q.device)
+    dist = torch.empty(nq, dtype=torch.float64, device=q.device)
+    fb = torch.empty(1, dtype=torch.int32, device=q.device) if want_fallbacks else None
+    _lib.check(lib.vfm_nn3_query(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), nq,
+                                 idx.data_ptr(), dist.data_ptr(), _ptr(fb), _stream()), "nn3_query")
+    return (idx, dist, fb) if want_fallbacks else (idx, dist)

@@ -4,6 +4,7 @@
   find_correspondences         RN:482-538      compute_errors              RN:997-1019
   compute_correspondences      RN:427-547 (the FPFH baseline; the learned baselines raise NotImplementedError)
   rotation re-orthogonalisation RN:331-336     icp_registration            RN:359-394
+  ransac_registration('fpfh')  RN:282-357 (opt-in: ``baseline_methods``; the row recovery of RN:295-310 is vfmreg.neighbors)
 
 Same names, argument meaning and return values; numpy in / numpy out.  The ROS node, the learned baseline
 descriptors, TEASER and PointDSC are out of scope.  ``run_icp=True`` runs the point-to-point ICP
@@ -20,7 +21,7 @@ import torch
 
 from . import o3d, ops
 from .config import load_config
-from .descriptors import extract_fpfh_features
+from .descriptors import extract_fpfh_features_device
 from .icp import register_frame
 from .mapping import get_voxel_hash_map
 from .utils import transform_pcl
@@ -53,17 +54,38 @@ def find_correspondences(feats0: np.ndarray, feats1: np.ndarray, n_points: int =
     near-ties differently); the decision among float32 rows is the oracle's fp64 distance, ties to the lowest index."""
     f0 = torch.from_numpy(np.ascontiguousarray(feats0, dtype=np.float32)).cuda()
     f1 = torch.from_numpy(np.ascontiguousarray(feats1, dtype=np.float32)).cuda()
+    i0, i1 = find_correspondences_device(f0, f1, n_points, mutual_filter)
+    return i0.cpu().numpy(), i1.cpu().numpy()
+
+
+def find_correspondences_device(f0: torch.Tensor, f1: torch.Tensor, n_points: int = 5000, mutual_filter: bool = True):
+    """``find_correspondences`` on float32 rows that are on the device: the two index lists as device tensors, in the same order."""
     if mutual_filter:   # RN:520-532 in one call: the reverse direction is searched only at the matched rows of feats1
         i0, i1, count = ops.match_mutual_pairs(f0, f1)
         k = int(count.item())
-        return i0[:k].cpu().numpy(), i1[:k].cpu().numpy()
-    # RN:505-518: the n_points pairs with the smallest distance
+        return i0[:k], i1[:k]
+    # RN:505-518: the n_points pairs with the smallest distance (numpy's argpartition decides which and in what order: on the host)
     nn01, d2, _ = ops.match_mutual_l2(f0, f1, mutual=False)
-    nns01 = nn01.cpu().numpy()
     dists = np.sqrt(d2.cpu().numpy())
     n = min(n_points, len(dists) - 1)
-    top = np.argpartition(dists, n)[:n]
-    return np.arange(len(nns01))[top], nns01[top]
+    top = torch.from_numpy(np.argpartition(dists, n)[:n]).to(nn01.device)
+    return top, nn01[top]
+
+
+def filter_recovered_rows(src_idx: torch.Tensor, src_dist: torch.Tensor, tgt_idx: torch.Tensor, tgt_dist: torch.Tensor) -> torch.Tensor:
+    """RN:301-310 on the two ``KDTree.query`` results (K-element tensors, any device): if no distance of either side is above 1 mm
+    every pair is kept (a distance of exactly 0.001 included); otherwise the pairs with ``src_dist < .001`` survive and of those the
+    ones with ``tgt_dist < .001`` (exactly 0.001 is dropped), order preserved.  Returns the surviving (source row, target row) pairs
+    as K' x 2 int64 -- in BOTH branches: the (K, 1) arrays sklearn returns make the reference's unfiltered branch stack to (K, 2, 1),
+    which Vector2iVector flattens to the same pairs.  One read-back (the count).  K = 0 gives 0 pairs (the reference's ``.max()`` of
+    an empty array raises)."""
+    src_idx, src_dist, tgt_idx, tgt_dist = (t.reshape(-1) for t in (src_idx, src_dist, tgt_idx, tgt_dist))
+    pairs = torch.stack((src_idx, tgt_idx), dim=1)
+    if pairs.shape[0] == 0:
+        return pairs
+    over = (src_dist.max() > .001) | (tgt_dist.max() > .001)                        # RN:301
+    keep = ~over | ((src_dist < .001) & (tgt_dist < .001))                          # RN:302-308
+    return pairs[keep]
 
 
 def _fingerprint(a: np.ndarray) -> Optional[int]:
@@ -106,17 +128,28 @@ class RegistrationNode:
     builds the scene's map itself and never edits it -- opts in."""
 
     def __init__(self, config=None, ransac_iterations: int = 50000, max_correspondence_distance: float = 10000.0,
-                 min_cosine_similarity: float = 0.8, cache_map: bool = False):
+                 min_cosine_similarity: float = 0.8, cache_map: bool = False, baseline_methods=()):
         self.config = config or load_config(None, None)  # RN:85
         self.ransac_iterations = ransac_iterations       # RN:326
         self.max_correspondence_distance = max_correspondence_distance  # RN:323
         self.min_cosine_similarity = min_cosine_similarity              # RN:418
         self.cache_map = bool(cache_map)
+        self.baseline_methods = tuple(baseline_methods)   # the baseline rows of RN:867-874 ransac_registration answers to (opt-in)
+        for m in self.baseline_methods:
+            if m != "fpfh" and m not in self._LEARNED:
+                raise ValueError(f"Invalid method: {m}")
         self._map_cache = None   # (weakref to the array, (shape, dtype, fingerprint), VoxelHashMap)
         self._pose_cache = None  # (bytes of the last initial pose, its device copy): the node passes the identity in every call
         self._chain_host = None  # page-locked landing area of the voxel chain's one read-back
         self.map_descriptor_cache = {}   # RN:67: method -> (down_map, feats_map)
         self._map_descriptor_keys = {}   # method -> (shape, dtype, fingerprint) of the map those features were computed from
+        self._map_descriptor_device = {}  # method -> (that key, down_map fp64, feats_map fp32) on the device
+
+    def clear_map_descriptors(self) -> None:
+        """RN:876-877: forget the maps' baseline features (the evaluation loop does at the first scan of a scene)."""
+        self.map_descriptor_cache = {}
+        self._map_descriptor_keys = {}
+        self._map_descriptor_device = {}
 
     def invalidate_map(self) -> None:
         """Forget the kept map (``cache_map=True``): the next call rebuilds it from the array it is handed."""
@@ -267,8 +300,15 @@ class RegistrationNode:
         return c["src_xyz"].cpu().numpy(), c["map_xyz"][c["tgt_rows"]].cpu().numpy()
 
     def ransac_registration(self, voxel_map, raw_scan, method: str = "vfm", run_icp: bool = False):
+        """RN:273-357.  ``'vfm'`` always; the baseline names of RN:281 only on a node created with ``baseline_methods`` (default
+        ``()``: they raise ValueError as every unknown name does): then ``'fpfh'`` runs where it is listed, and the learned names
+        raise NotImplementedError as ``compute_correspondences`` does."""
         if method != "vfm":
-            raise ValueError(f"Invalid method: {method}")  # baselines are out of scope
+            if self.baseline_methods and method in self._LEARNED:
+                raise NotImplementedError(f"{method}: the learned baselines need their trained weights and are out of scope")
+            if method == "fpfh" and method in self.baseline_methods:
+                return self._ransac_registration_baseline(voxel_map, raw_scan, method, run_icp)
+            raise ValueError(f"Invalid method: {method}")
         c = self._correspond(voxel_map, raw_scan, np.eye(4))
         # correspondence indices (RN:288-317).  The reference re-voxelises the scan and the map in 3-D and recovers the
         # rows with two KD-trees (distance < 1e-3); the containers are the same ones (same hash, same order), so the rows
@@ -293,6 +333,53 @@ class RegistrationNode:
             voxel_scan = np.asarray(pcd_src.points)
             pose = register_frame(points=voxel_scan, voxel_map=vhm if not vhm.empty() else vhm.xyz_map(), initial_guess=ransac_pose,
                                   max_correspondance_distance=3 * sigma, kernel=sigma / 3)   # RN:340-344
+            return ransac_pose, pose
+        return ransac_pose, None
+
+    def baseline_row_pairs(self, voxel_map, raw_scan, method: str = "fpfh") -> dict:
+        """RN:282-310 on the device: the baseline's correspondences, the scan's two voxel levels, the 3-D hash map of
+        ``voxel_map[:, :3]`` in its ``point_cloud()`` order, the two 1-NN queries and the 1 mm filter.  Returns dict(voxel_scan [S, 3],
+        voxel_map_3d [M, 3], pairs [K', 2] int64 (rows of the two), voxel_hash_map) -- device tensors."""
+        from .neighbors import KDTree
+        vm, scan = np.asarray(voxel_map), np.asarray(raw_scan)
+        if vm.ndim != 2 or vm.shape[1] < 3 or scan.ndim != 2 or scan.shape[1] < 3:
+            raise ValueError("Invalid shape")
+        vs = self.config.mapping.voxel_size
+        map_xyz = np.ascontiguousarray(vm[:, :3])
+        raw_xyz = torch.from_numpy(np.ascontiguousarray(scan[:, :3], dtype=np.float64)).cuda()
+        src, tgt = self._baseline_correspondences_device(map_xyz, raw_xyz, method, False)         # RN:282
+        voxel_scan = self._voxel_scan(raw_xyz, vs)                                                 # RN:289-290
+        voxel_hash_map = get_voxel_hash_map(self.config)                                           # RN:291-292
+        voxel_hash_map.add_points(map_xyz)
+        voxel_map_3d = voxel_hash_map.point_cloud_device()                                         # RN:293
+        if voxel_map_3d is None or voxel_scan.shape[0] == 0:
+            raise ValueError("Found array with 0 sample(s) while a minimum of 1 is required")      # (sklearn's, from RN:295-296)
+        src_idx, src_dist = KDTree(voxel_scan, metric="euclidean").query_device(src)               # RN:295, 297
+        tgt_idx, tgt_dist = KDTree(voxel_map_3d, metric="euclidean").query_device(tgt)             # RN:296, 298
+        pairs = filter_recovered_rows(src_idx, src_dist, tgt_idx, tgt_dist)                        # RN:301-310
+        return dict(voxel_scan=voxel_scan, voxel_map_3d=voxel_map_3d, pairs=pairs, voxel_hash_map=voxel_hash_map)
+
+    def _ransac_registration_baseline(self, voxel_map, raw_scan, method: str, run_icp: bool):
+        """RN:282-357 for a baseline descriptor, line for line, with the clouds on the device between the steps.  The correspondence
+        points are voxel MEANS (``extract_fpfh_features``), so the row recovery of RN:295-310 does real work here: only a mean over a
+        single point is a row of the voxelised cloud.  Fewer than 3 surviving pairs give Open3D's default result (the identity)."""
+        from .icp import _grid_of, register_frame_on_grid
+        r = self.baseline_row_pairs(voxel_map, raw_scan, method)
+        voxel_scan, voxel_map_3d, voxel_hash_map, pairs = r["voxel_scan"], r["voxel_map_3d"], r["voxel_hash_map"], r["pairs"]
+        pcd_src = o3d.geometry.PointCloud()
+        pcd_src.points = o3d.utility.Vector3dVector(o3d.utility.DeviceArray(voxel_scan))
+        pcd_tgt = o3d.geometry.PointCloud()
+        pcd_tgt.points = o3d.utility.Vector3dVector(o3d.utility.DeviceArray(voxel_map_3d))
+        coors = o3d.utility.Vector2iVector(o3d.utility.DeviceArray(pairs.to(torch.int32)))
+        result = o3d.pipelines.registration.registration_ransac_based_on_correspondence(
+            pcd_src, pcd_tgt, coors, self.max_correspondence_distance,
+            o3d.pipelines.registration.TransformationEstimationPointToPoint(False), ransac_n=3,
+            criteria=o3d.pipelines.registration.RANSACConvergenceCriteria(self.ransac_iterations, 1))      # RN:319-327
+        ransac_pose = np.array(result.transformation)
+        if run_icp:
+            ransac_pose = orthogonalize_rotation(ransac_pose)                                      # RN:331-336
+            sigma = self.config.adaptive_threshold.initial_threshold                               # RN:339
+            pose = register_frame_on_grid(voxel_scan, _grid_of(voxel_hash_map), ransac_pose, 3 * sigma, sigma / 3)   # RN:340-344
             return ransac_pose, pose
         return ransac_pose, None
 
@@ -357,26 +444,39 @@ class RegistrationNode:
         (down_scan[i0], down_map[i1]).  'fpfh' runs extract_fpfh_features(., 0.1) on the GPU (csrc/fpfh.hip).  The map's features
         are kept in ``map_descriptor_cache[method]`` as in the reference, and reused only for a map of the same shape, dtype and
         ``_fingerprint`` (a non-contiguous map is not cached)."""
+        vm = np.asarray(voxel_map)
+        if method == "fpfh" and (vm.ndim != 2 or vm.shape[1] < 3):
+            raise ValueError("Invalid shape")
+        scan = np.asarray(raw_scan)
+        raw_xyz = torch.from_numpy(np.ascontiguousarray(scan[:, :3], dtype=np.float64)).cuda() if method == "fpfh" else None
+        src, tgt = self._baseline_correspondences_device(vm, raw_xyz, method, mutual_filter)
+        return src.cpu().numpy(), tgt.cpu().numpy()
+
+    def _baseline_correspondences_device(self, vm: np.ndarray, raw_xyz: torch.Tensor, method: str, mutual_filter: bool):
+        """``compute_correspondences`` with the scan's coordinates (n x 3 fp64) on the device and both results left there.  The map's
+        features are kept twice: as numpy in ``map_descriptor_cache`` (the reference's attribute) and on the device for the matching."""
         if method in self._LEARNED:
             raise NotImplementedError(f"{method}: the learned baselines need their trained weights and are out of scope")
         if method != "fpfh":
             raise ValueError(f"Invalid method: {method}")
-        vm = np.asarray(voxel_map)
-        if vm.ndim != 2 or vm.shape[1] < 3:
-            raise ValueError("Invalid shape")
         fp = _fingerprint(vm)
         key = (vm.shape, vm.dtype.str, fp) if fp is not None else None
-        down_map = feats_map = None
-        if key is not None and method in self.map_descriptor_cache and self._map_descriptor_keys.get(method) == key:
-            down_map, feats_map = self.map_descriptor_cache[method]
-        down_scan, feats_scan = extract_fpfh_features(raw_scan, .1)
-        if down_map is None:
-            down_map, feats_map = extract_fpfh_features(vm, .1)
-        if key is not None:
-            self.map_descriptor_cache[method] = (down_map, feats_map)
-            self._map_descriptor_keys[method] = key
-        else:
+        kept = self._map_descriptor_device.get(method)
+        if not (key is not None and kept is not None and kept[0] == key and method in self.map_descriptor_cache
+                and self._map_descriptor_keys.get(method) == key):
+            kept = None
+        down_scan, feats_scan = extract_fpfh_features_device(raw_xyz, .1)
+        if kept is None:
+            m_xyz = torch.from_numpy(np.ascontiguousarray(vm[:, :3], dtype=np.float64)).cuda()
+            down_map, feats_map = extract_fpfh_features_device(m_xyz, .1)
+            kept = (key, down_map, feats_map.float())
+            if key is not None:
+                self.map_descriptor_cache[method] = (down_map.cpu().numpy(), feats_map.cpu().numpy())
+                self._map_descriptor_keys[method] = key
+                self._map_descriptor_device[method] = kept
+        if key is None:
             self.map_descriptor_cache.pop(method, None)
             self._map_descriptor_keys.pop(method, None)
-        corrs_scan, corrs_map = find_correspondences(feats_scan, feats_map, n_points=5000, mutual_filter=mutual_filter)
-        return down_scan[corrs_scan], down_map[corrs_map]
+            self._map_descriptor_device.pop(method, None)
+        corrs_scan, corrs_map = find_correspondences_device(feats_scan.float(), kept[2], n_points=5000, mutual_filter=mutual_filter)
+        return down_scan[corrs_scan], kept[1][corrs_map]
