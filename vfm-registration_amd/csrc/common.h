@@ -31,6 +31,13 @@ int vfm_fail(int code, const char *fmt, ...);
         if (e__ != hipSuccess) return vfm_fail(VFM_EHIP, "%s: %s", #call, hipGetErrorString(e__)); \
     } while (0)
 
+// pass a helper's failure on (the helper has already set the error text)
+#define VFM_TRY(call)                    \
+    do {                                 \
+        const int rc__ = (call);         \
+        if (rc__ != VFM_OK) return rc__; \
+    } while (0)
+
 static inline size_t vfm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // carve consecutive 256-byte aligned regions out of a caller-provided workspace

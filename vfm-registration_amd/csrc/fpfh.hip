@@ -1,6 +1,6 @@
 // fpfh.hip -- FPFH descriptors on MI355X (gfx950): the CPU work of extract_fpfh_features (vfm_reg/descriptors.py:19-44), which the
 // reference runs inside Open3D 0.18:
-//   fpfh_grid_*        a sorted-key CSR grid (cell = the search radius) built on the device, for KDTreeFlann
+//   FpfhCells          a sorted-key CSR grid (grid3.h; cell = the search radius) built on the device, for KDTreeFlann
 //   fpfh_search_kernel KDTreeFlann::SearchHybrid (KDTreeSearchParamHybrid(radius, max_nn)): the points with d2 < radius^2, ascending by
 //                      (d2, index), the first max_nn of them
 //   fpfh_normal_kernel PointCloud::EstimateNormals(param, fast_normal_computation = true): ComputeCovariance (one pass) + FastEigen3x3
@@ -10,9 +10,7 @@
 // fp64 throughout, -ffp-contract=off, operation order as Open3D writes it (tests/fpfh_oracle.py repeats it in numpy).  Deviations, all in
 // equal distances are ordered by index (nanoflann leaves them unspecified); the down-sample emits voxels in ascending
 // (ix, iy, iz) order (Open3D: std::unordered_map iteration order).
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "grid3.h"
 
 namespace {
 
@@ -24,32 +22,15 @@ constexpr int GRID_LIM = (1 << 20) - 2;
 // are rounded (coordinates up to 2^20 cells)
 constexpr double CELL_SLACK = 1.0 + 1e-6;
 
-__device__ __forceinline__ long long grid_cell(double x, double inv_cell) {
-    // clamped cells stay 1-Lipschitz, so the 27-cell cover stays complete (far-out points only share cells)
-    double c = floor(x * inv_cell);
-    c = fmin(fmax(c, (double)-GRID_LIM), (double)GRID_LIM);
-    return (long long)c;
-}
-__device__ __forceinline__ long long grid_key(long long cx, long long cy, long long cz) {
-    return ((cx + (1 << 20)) << 42) | ((cy + (1 << 20)) << 21) | (cz + (1 << 20));
-}
-
-__global__ __launch_bounds__(256) void fpfh_grid_keys_kernel(const double* __restrict__ pts, int64_t n, double inv_cell,
-                                                             long long* __restrict__ keys, int* __restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = grid_key(grid_cell(pts[3 * i], inv_cell), grid_cell(pts[3 * i + 1], inv_cell), grid_cell(pts[3 * i + 2], inv_cell));
-    idx[i] = (int)i;
-}
-
-__device__ __forceinline__ int lower_bound64(const long long* __restrict__ a, int n, long long key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
+// clamped cells stay 1-Lipschitz, so the 27-cell cover stays complete (far-out points only share cells)
+__device__ __forceinline__ long long grid_cell(double x, double inv_cell) { return grid3::cell(x, inv_cell, GRID_LIM); }
+struct FpfhCells {   // the quantiser of grid3::keys_kernel
+    static constexpr const char* kernel_name = "grid3::keys_kernel<FpfhCells>";
+    double inv_cell;
+    __device__ long long operator()(double x, double y, double z, bool&) const {
+        return grid3::key(grid_cell(x, inv_cell), grid_cell(y, inv_cell), grid_cell(z, inv_cell));
     }
-    return lo;
-}
+};
 
 __device__ __forceinline__ unsigned long long lanes_below() {
     return (1ull << (threadIdx.x & 63)) - 1ull;
@@ -105,10 +86,6 @@ __device__ __forceinline__ void for_each_cached(const SearchLds& s, int count, F
     }
 }
 
-__device__ __forceinline__ bool key_less(double a2, int ai, double b2, int bi) {
-    return a2 < b2 || (a2 == b2 && ai < bi);
-}
-
 __global__ __launch_bounds__(64) void fpfh_search_kernel(const double* __restrict__ pts, int64_t n, const long long* __restrict__ keys,
                                                          const int* __restrict__ order, double inv_cell, double r2, int max_nn,
                                                          int* __restrict__ nbr_idx, double* __restrict__ nbr_d2, int* __restrict__ nbr_cnt,
@@ -121,8 +98,8 @@ __global__ __launch_bounds__(64) void fpfh_search_kernel(const double* __restric
     int run_lo = 0, run_len = 0;
     if (lane < 9) {
         const long long ax = cx - 1 + lane / 3, ay = cy - 1 + lane % 3;
-        run_lo = lower_bound64(keys, (int)n, grid_key(ax, ay, cz - 1));
-        run_len = lower_bound64(keys, (int)n, grid_key(ax, ay, cz + 1) + 1) - run_lo;
+        run_lo = grid3::lower_bound(keys, (int)n, grid3::key(ax, ay, cz - 1));
+        run_len = grid3::lower_bound(keys, (int)n, grid3::key(ax, ay, cz + 1) + 1) - run_lo;
         s.rlo[lane] = run_lo;
     }
     __syncthreads();
@@ -239,7 +216,7 @@ __global__ __launch_bounds__(64) void fpfh_search_kernel(const double* __restric
         const double ed = s.d2[e];
         const int ei = s.idx[e];
         int rank = 0;
-        for (int f = 0; f < k; ++f) rank += key_less(s.d2[f], s.idx[f], ed, ei) ? 1 : 0;
+        for (int f = 0; f < k; ++f) rank += grid3::closer(s.d2[f], s.idx[f], ed, ei) ? 1 : 0;
         oi[rank] = ei;
         od[rank] = ed;
     }
@@ -459,6 +436,7 @@ __global__ __launch_bounds__(256) void fpfh_normal_kernel(const double* __restri
 
 // ---- VoxelDownSample: bounds -> voxel keys -> stable sort -> run starts -> one thread per voxel
 constexpr int VDS_BITS = 21;
+static_assert(3 * VDS_BITS <= grid3::KEY_BITS, "the down-sample's keys go through grid3::sort_pairs");
 __global__ __launch_bounds__(1024) void fpfh_bounds_kernel(const double* __restrict__ pts, int64_t n, double* __restrict__ bounds) {
     __shared__ double red[6][1024];
     const int t = threadIdx.x;
@@ -502,12 +480,6 @@ __global__ __launch_bounds__(256) void fpfh_vds_keys_kernel(const double* __rest
     }
     keys[i] = key;
     idx[i] = (int)i;
-}
-
-__global__ __launch_bounds__(256) void fpfh_vds_heads_kernel(const long long* __restrict__ keys, int64_t n, int* __restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void fpfh_vds_starts_kernel(const int* __restrict__ head, const int* __restrict__ vid, int64_t n,
@@ -654,20 +626,8 @@ __global__ __launch_bounds__(64) void fpfh_fpfh_kernel(const double* __restrict_
     }
 }
 
-size_t fpfh_cub_bytes(int64_t n) {
-    const int ni = (int)(n > 0 ? n : 1);
-    size_t best = 0, b = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (long long*)nullptr, (long long*)nullptr, (int*)nullptr, (int*)nullptr, ni, 0, 64);
-    best = b > best ? b : best;
-    b = 0;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, (int*)nullptr, (int*)nullptr, ni);
-    best = b > best ? b : best;
-    return best + 1024;
-}
-
 struct FpfhWs {
-    long long* keys_in;
-    int* idx_in;
+    grid3::SortWs<true> s;
     long long* keys;   // sorted (down-sample)
     int* order;        // sorted (down-sample)
     int* head;
@@ -675,16 +635,13 @@ struct FpfhWs {
     int* starts;       // [n + 1]
     double* bounds;    // [6]
     int* overflow;
-    void* cub;
-    size_t cub_bytes;
 };
 
 FpfhWs carve_fpfh(void* p, int64_t n, size_t* used = nullptr) {
     VfmCarver c(p);
     const size_t nn = (size_t)(n > 0 ? n : 1);
     FpfhWs w{};
-    w.keys_in = c.take<long long>(nn);
-    w.idx_in = c.take<int>(nn);
+    w.s = grid3::carve_sort<true>(c, n);
     w.keys = c.take<long long>(nn);
     w.order = c.take<int>(nn);
     w.head = c.take<int>(nn);
@@ -692,13 +649,11 @@ FpfhWs carve_fpfh(void* p, int64_t n, size_t* used = nullptr) {
     w.starts = c.take<int>(nn + 1);
     w.bounds = c.take<double>(6);
     w.overflow = c.take<int>(1);
-    w.cub_bytes = fpfh_cub_bytes(n);
-    w.cub = c.take<unsigned char>(w.cub_bytes);
     if (used) *used = c.used();
     return w;
 }
 
-inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
+using grid3::blocks256;
 
 }  // namespace
 
@@ -716,12 +671,7 @@ VFM_EXPORT int vfm_fpfh_grid_build(const double* pts, int64_t n, double radius, 
     VFM_CHECK_ARG(ws_bytes >= vfm_fpfh_workspace_bytes(n), "fpfh_grid_build: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     FpfhWs w = carve_fpfh(ws, n);
-    hipLaunchKernelGGL(fpfh_grid_keys_kernel, dim3(blocks256(n)), dim3(256), 0, st, pts, n, 1.0 / (radius * CELL_SLACK), w.keys_in, w.idx_in);
-    VFM_CHECK_LAUNCH("fpfh_grid_keys_kernel");
-    size_t tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, reinterpret_cast<long long*>(keys_out), w.idx_in, order_out, (int)n,
-                                                     0, 64, st));
-    return VFM_OK;
+    return grid3::build(pts, n, FpfhCells{1.0 / (radius * CELL_SLACK)}, nullptr, w.s, reinterpret_cast<long long*>(keys_out), order_out, st);
 }
 
 VFM_EXPORT int vfm_fpfh_search_hybrid(const double* pts, int64_t n, const int64_t* keys, const int32_t* order, double radius, int32_t max_nn,
@@ -761,15 +711,11 @@ VFM_EXPORT int vfm_fpfh_voxel_down_sample(const double* pts, const double* norma
     VFM_CHECK_HIP(hipMemsetAsync(w.overflow, 0, sizeof(int), st));
     hipLaunchKernelGGL(fpfh_bounds_kernel, dim3(1), dim3(1024), 0, st, pts, n, w.bounds);
     VFM_CHECK_LAUNCH("fpfh_bounds_kernel");
-    hipLaunchKernelGGL(fpfh_vds_keys_kernel, dim3(blocks256(n)), dim3(256), 0, st, pts, n, w.bounds, voxel_size, w.keys_in, w.idx_in,
+    hipLaunchKernelGGL(fpfh_vds_keys_kernel, dim3(blocks256(n)), dim3(256), 0, st, pts, n, w.bounds, voxel_size, w.s.keys_in, w.s.idx_in,
                        w.overflow);
     VFM_CHECK_LAUNCH("fpfh_vds_keys_kernel");
-    size_t tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, w.keys, w.idx_in, w.order, (int)n, 0, 3 * VDS_BITS, st));
-    hipLaunchKernelGGL(fpfh_vds_heads_kernel, dim3(blocks256(n)), dim3(256), 0, st, w.keys, n, w.head);
-    VFM_CHECK_LAUNCH("fpfh_vds_heads_kernel");
-    tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, tb, w.head, w.vid, (int)n, st));
+    VFM_TRY(grid3::sort_pairs(w.s, n, w.keys, w.order, st));
+    VFM_TRY(grid3::run_ids(w.s, n, w.keys, w.head, w.vid, st));
     hipLaunchKernelGGL(fpfh_vds_starts_kernel, dim3(blocks256(n)), dim3(256), 0, st, w.head, w.vid, n, w.overflow, w.starts, count_out);
     VFM_CHECK_LAUNCH("fpfh_vds_starts_kernel");
     hipLaunchKernelGGL(fpfh_vds_average_kernel, dim3(blocks256(n)), dim3(256), 0, st, pts, normals, n, w.order, w.starts, count_out, pts_out,

@@ -4,26 +4,23 @@
 // register_frame, kiss_icp/registration.py:28-73, from registration_node.py:338-344):
 //   icp_nearest_kernel   VoxelHashMap::GetCorrespondences (VoxelHashMap.cpp:76-168): nearest map point
 //                        among the 27 voxels around each source point (<= 20 points per voxel),
-//                        accepted if closer than max_correspondence_distance
+//                        accepted if closer than max_correspondence_distance; <true>: the form for
+//                        rows that carry descriptors
 //   icp_system_kernel    BuildLinearSystem (Registration.cpp:96-141): sum of J^T w J (6x6) and J^T w r
 //                        with J = [I | -hat(s)], w = k^2 / (k + |r|^2)^2
 // The 6x6 LDLT solve and SE3::exp (Registration.cpp:176-177) stay on the host (vfmreg/icp.py).
 //
-// The voxel grid is a sorted-key CSR (keys ascending, points of a voxel in insertion order), so the
+// The voxel grid is a sorted-key CSR (grid3.h; keys ascending, points of a voxel in insertion order), so the
 // scan order over neighbours equals the reference's (voxel loops i, j, k ascending, then insertion
 // order, strict '<' keeps the first minimum).  fp64, -ffp-contract=off, operation order spelled out
 // as in oracle/vfm_oracle.c; the reduction is a fixed tree (thread t owns pairs i = t mod 256 in
 // ascending order, then a stride-halving tree), which the oracle replays, so every iterate is
 // bit-identical to the oracle's (TBB's reduction order in the reference is unspecified).
-#include <hipcub/hipcub.hpp>
+#include <type_traits>
 
-#include "common.h"
+#include "grid3.h"
 
 namespace {
-
-__device__ __forceinline__ long long voxel_key(int vx, int vy, int vz) {
-    return ((long long)(vx + (1 << 20)) << 42) | ((long long)(vy + (1 << 20)) << 21) | (long long)(vz + (1 << 20));
-}
 
 // step: the Gauss-Newton update of the previous iteration (Registration.cpp:178-179, "Equation (12)") applied in the same
 // launch -- T by value, the arithmetic of vfm_transform_xyz_f64 -- and the moved points written to src_out
@@ -31,87 +28,6 @@ struct IcpStep {
     double T[12];
     int apply;
 };
-// 32 lanes per source point, lane l < 27 takes neighbour voxel l = 9 (a - kx + 1) + 3 (b - ky + 1) + (c - kz + 1) -- the
-// reference's loop order -- : one binary search and at most a voxel's points per lane instead of 27 searches in a row (a
-// point's chain of ~460 dependent loads was the whole 0.135 ms of an iteration at 20 000 points).  The lanes' candidates are
-// merged by (distance, scan position): the first minimum of the reference's scan, the same squared distances.
-constexpr int ICP_LANES = 32;
-// (src and src_out may be the same array -- include/vfmreg.h; icp.py transforms in place from the second iteration on -- so
-// neither is __restrict__; a group reads its point before lane 0 writes it, and no other group touches that point)
-__global__ __launch_bounds__(256) void icp_nearest_kernel(const double* src, int64_t n,
-                                                          const long long* __restrict__ keys,
-                                                          const int* __restrict__ start,
-                                                          const double* __restrict__ pts, int nv, double voxel_size,
-                                                          double max_dist, double* __restrict__ tgt,
-                                                          uint8_t* __restrict__ valid, IcpStep step,
-                                                          double* src_out) {
-    const int l = threadIdx.x & (ICP_LANES - 1);
-    int64_t i = (int64_t)blockIdx.x * (256 / ICP_LANES) + (threadIdx.x / ICP_LANES);
-    const bool live = i < n;
-    // (the shuffles below want every lane of the wave: a group past the end runs on the origin and stores nothing)
-    double px = 0.0, py = 0.0, pz = 0.0;
-    if (live) {
-        px = src[3 * i];
-        py = src[3 * i + 1];
-        pz = src[3 * i + 2];
-    }
-    if (step.apply) {
-        const double* T = step.T;
-        const double qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3] * 1.0;
-        const double qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7] * 1.0;
-        const double qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11] * 1.0;
-        px = qx; py = qy; pz = qz;
-        if (l == 0 && live) {
-            src_out[3 * i] = px;
-            src_out[3 * i + 1] = py;
-            src_out[3 * i + 2] = pz;
-        }
-    }
-    const int kx = (int)(px / voxel_size), ky = (int)(py / voxel_size), kz = (int)(pz / voxel_size);
-    double bx = 0.0, by = 0.0, bz = 0.0, best = 1.7976931348623157e308;
-    unsigned order = 0xFFFFFFFFu;   // scan position of the lane's best point: (neighbour << 20) | index inside the voxel; none yet
-    if (l < 27) {
-        const long long key = voxel_key(kx - 1 + l / 9, ky - 1 + (l / 3) % 3, kz - 1 + l % 3);
-        int lo = 0, hi = nv;  // lower_bound
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        if (lo < nv && keys[lo] == key) {
-            const int j0 = start[lo], j1 = start[lo + 1];
-            for (int j = j0; j < j1; ++j) {
-                const double dx = pts[3 * j] - px, dy = pts[3 * j + 1] - py, dz = pts[3 * j + 2] - pz;
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 < best) {
-                    best = d2;
-                    bx = pts[3 * j];
-                    by = pts[3 * j + 1];
-                    bz = pts[3 * j + 2];
-                    order = ((unsigned)l << 20) | (unsigned)min(j - j0, (1 << 20) - 1);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = ICP_LANES / 2; off >= 1; off >>= 1) {
-        const double ob = __shfl_xor(best, off), ox = __shfl_xor(bx, off), oy = __shfl_xor(by, off), oz = __shfl_xor(bz, off);
-        const unsigned oo = __shfl_xor(order, off);
-        // strict '<' in scan order: the smaller distance, and of equal distances the earlier position (a lane without a point
-        // holds the largest position and never wins against one that has a point: its `best` is the initial value, which no
-        // accepted point carries)
-        const bool take = oo != 0xFFFFFFFFu && (order == 0xFFFFFFFFu || ob < best || (ob == best && oo < order));
-        if (take) {
-            best = ob; bx = ox; by = oy; bz = oz; order = oo;
-        }
-    }
-    if (l != 0 || !live) return;
-    // (closest - point).norm() < max_correspondence_distance (VoxelHashMap.cpp:147)
-    const bool ok = order != 0xFFFFFFFFu && (sqrt(best) < max_dist);
-    tgt[3 * i] = bx;
-    tgt[3 * i + 1] = by;
-    tgt[3 * i + 2] = bz;
-    valid[i] = ok ? 1 : 0;
-}
 
 // ---- RegisterFrame(std::vector<Eigen::VectorXd>, ...) (Registration.cpp:384-423; round 6): the same loop on rows that carry descriptors of
 // any width, with VoxelHashMap::GetCorrespondences(VectorXdVector) (VoxelHashMap.cpp:321-448) as its search: among the points of the 27
@@ -141,13 +57,30 @@ struct IcpDesc {
     const uint8_t* map_has;
     int f;
 };
-__global__ __launch_bounds__(256) void icp_nearest_desc_kernel(const double* src, int64_t n, const long long* __restrict__ keys,
-                                                               const int* __restrict__ start, const double* __restrict__ pts, int nv,
-                                                               double voxel_size, double max_dist, double* __restrict__ tgt,
-                                                               uint8_t* __restrict__ valid, IcpStep step, double* src_out, IcpDesc dd) {
+struct IcpDescStep : IcpStep {   // the step of the search with descriptors carries them: the plain search's arguments stay as they were
+    IcpDesc dd;
+};
+
+// 32 lanes per source point, lane l < 27 takes neighbour voxel l = 9 (a - kx + 1) + 3 (b - ky + 1) + (c - kz + 1) -- the
+// reference's loop order -- : one binary search and at most a voxel's points per lane instead of 27 searches in a row (a
+// point's chain of ~460 dependent loads was the whole 0.135 ms of an iteration at 20 000 points).  The lanes' candidates are
+// merged by (distance, scan position): the first minimum of the reference's scan, the same squared distances.
+constexpr int ICP_LANES = 32;
+constexpr unsigned ICP_NONE = 0xFFFFFFFFu;   // the scan position of a lane that holds no point
+// One kernel for both searches.  DESC = false: the cost of a candidate is its squared distance, and it is accepted on that.  DESC = true:
+// the cost is weighted by the descriptors as above, and acceptance is on the Euclidean distance of the chosen neighbour.
+// (src and src_out may be the same array -- include/vfmreg.h; icp.py transforms in place from the second iteration on -- so
+// neither is __restrict__; a group reads its point before lane 0 writes it, and no other group touches that point)
+template <bool DESC>
+__global__ __launch_bounds__(256) void icp_nearest_kernel(const double* src, int64_t n, const long long* __restrict__ keys,
+                                                          const int* __restrict__ start, const double* __restrict__ pts, int nv,
+                                                          double voxel_size, double max_dist, double* __restrict__ tgt,
+                                                          uint8_t* __restrict__ valid, std::conditional_t<DESC, IcpDescStep, IcpStep> step,
+                                                          double* src_out) {
     const int l = threadIdx.x & (ICP_LANES - 1);
     int64_t i = (int64_t)blockIdx.x * (256 / ICP_LANES) + (threadIdx.x / ICP_LANES);
     const bool live = i < n;
+    // (the shuffles below want every lane of the wave: a group past the end stays on the origin, probes nothing and stores nothing)
     double px = 0.0, py = 0.0, pz = 0.0;
     if (live) {
         px = src[3 * i];
@@ -168,33 +101,36 @@ __global__ __launch_bounds__(256) void icp_nearest_desc_kernel(const double* src
     }
     const int kx = (int)(px / voxel_size), ky = (int)(py / voxel_size), kz = (int)(pz / voxel_size);
     double bx = 0.0, by = 0.0, bz = 0.0, best = 1.7976931348623157e308;
-    unsigned order = 0xFFFFFFFFu;
+    unsigned order = ICP_NONE;   // scan position of the lane's best point: (neighbour << 20) | index inside the voxel
     if (l < 27 && live) {
-        const long long key = voxel_key(kx - 1 + l / 9, ky - 1 + (l / 3) % 3, kz - 1 + l % 3);
-        int lo = 0, hi = nv;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
+        const long long key = grid3::key(kx - 1 + l / 9, ky - 1 + (l / 3) % 3, kz - 1 + l % 3);
+        const int lo = grid3::lower_bound(keys, nv, key);
         if (lo < nv && keys[lo] == key) {
             const int j0 = start[lo], j1 = start[lo + 1];
-            const double* pd = dd.src_desc + i * dd.f;
-            const double pn = dd.src_norm[i];
-            const bool phas = dd.f > 0 && dd.src_has[i] != 0;
+            const double* pd = nullptr;
+            double pn = 0.0;
+            bool phas = false;
+            if constexpr (DESC) {
+                pd = step.dd.src_desc + i * step.dd.f;
+                pn = step.dd.src_norm[i];
+                phas = step.dd.f > 0 && step.dd.src_has[i] != 0;
+            }
             for (int j = j0; j < j1; ++j) {
                 const double dx = pts[3 * j] - px, dy = pts[3 * j + 1] - py, dz = pts[3 * j + 2] - pz;
                 double d = (dx * dx + dy * dy) + dz * dz;
-                if (dd.f > 0) {
-                    double c = 1.0;
-                    if (phas && dd.map_has[j] != 0) {
-                        const double* nd = dd.map_desc + (int64_t)j * dd.f;
-                        double dot = 0.0;
-                        for (int k = 0; k < dd.f; ++k) dot = dot + nd[k] * pd[k];
-                        const double cs = dot / (dd.map_norm[j] * pn + 1e-5);
-                        c = 0.5 * (1.0 - cs);
-                        c = c < 0.01 ? 0.01 : (1.0 < c ? 1.0 : c);   // std::clamp(c, 0.01, 1.0)
+                if constexpr (DESC) {
+                    if (step.dd.f > 0) {
+                        double c = 1.0;
+                        if (phas && step.dd.map_has[j] != 0) {
+                            const double* nd = step.dd.map_desc + (int64_t)j * step.dd.f;
+                            double dot = 0.0;
+                            for (int k = 0; k < step.dd.f; ++k) dot = dot + nd[k] * pd[k];
+                            const double cs = dot / (step.dd.map_norm[j] * pn + 1e-5);
+                            c = 0.5 * (1.0 - cs);
+                            c = c < 0.01 ? 0.01 : (1.0 < c ? 1.0 : c);   // std::clamp(c, 0.01, 1.0)
+                        }
+                        d = d * c;
                     }
-                    d = d * c;
                 }
                 if (d < best) {
                     best = d;
@@ -210,21 +146,29 @@ __global__ __launch_bounds__(256) void icp_nearest_desc_kernel(const double* src
     for (int off = ICP_LANES / 2; off >= 1; off >>= 1) {
         const double ob = __shfl_xor(best, off), ox = __shfl_xor(bx, off), oy = __shfl_xor(by, off), oz = __shfl_xor(bz, off);
         const unsigned oo = __shfl_xor(order, off);
-        const bool take = oo != 0xFFFFFFFFu && (order == 0xFFFFFFFFu || ob < best || (ob == best && oo < order));
+        // strict '<' in scan order: the smaller cost, and of equal costs the earlier position (a lane without a point holds the
+        // largest position and never wins against one that has a point: its `best` is the initial value, which no accepted point
+        // carries)
+        const bool take = oo != ICP_NONE && (order == ICP_NONE || ob < best || (ob == best && oo < order));
         if (take) {
             best = ob; bx = ox; by = oy; bz = oz; order = oo;
         }
     }
     if (l != 0 || !live) return;
-    // (closest_neighbor.head<3>() - point.head<3>()).norm() < max_correspondance_distance (VoxelHashMap.cpp:425-432): the Euclidean
-    // distance of the chosen neighbour, not its weighted one
-    const double ex = bx - px, ey = by - py, ez = bz - pz;
-    const bool ok = order != 0xFFFFFFFFu && (sqrt((ex * ex + ey * ey) + ez * ez) < max_dist);
+    // (closest - point).norm() < max_correspondence_distance (VoxelHashMap.cpp:147); with descriptors
+    // (closest_neighbor.head<3>() - point.head<3>()).norm() (VoxelHashMap.cpp:425-432): the neighbour's Euclidean distance, not its cost
+    double e2 = best;
+    if constexpr (DESC) {
+        const double ex = bx - px, ey = by - py, ez = bz - pz;
+        e2 = (ex * ex + ey * ey) + ez * ez;
+    }
+    const bool ok = order != ICP_NONE && (sqrt(e2) < max_dist);
     tgt[3 * i] = bx;
     tgt[3 * i + 1] = by;
     tgt[3 * i + 2] = bz;
     valid[i] = ok ? 1 : 0;
 }
+inline dim3 icp_nearest_grid(int64_t n) { return dim3((unsigned)((n + 256 / ICP_LANES - 1) / (256 / ICP_LANES))); }
 
 // out[0..35] = J^T W J (row-major 6x6), out[36..41] = J^T W r, out[42] = number of pairs.
 // One workgroup per output value: the 43 sums are independent chains, so workgroup k recomputes w and the two Jacobian columns it
@@ -295,25 +239,24 @@ __global__ __launch_bounds__(256) void icp_system_kernel(const double* __restric
 // function of the sorted sequence (no atomic decides an order); the one atomic raises the out-of-range flag.
 constexpr int64_t ICP_GRID_MAX_POINTS = (int64_t)1 << 30;   // int32 positions and prefix sums
 
-__global__ __launch_bounds__(256) void icp_grid_keys_kernel(const double* __restrict__ xyz, int64_t n, double voxel_size,
-                                                            long long* __restrict__ keys, int* __restrict__ idx, int* __restrict__ status) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    // v = trunc(xyz / voxel_size), a true division; the key holds 21 bits per axis and the 27-neighbour scan reaches v +- 1
-    const double lim = (double)((1 << 20) - 1);
-    int v[3];
-    bool bad = false;
+// v = trunc(xyz / voxel_size), a true division; an axis with |v| >= 2^20 - 1 (or a NaN) is out of range: v = 0 and the status flag
+struct IcpVoxels {   // the quantiser of grid3::keys_kernel
+    static constexpr const char* kernel_name = "grid3::keys_kernel<IcpVoxels>";
+    double voxel_size;
+    __device__ long long operator()(double x, double y, double z, bool& bad) const {
+        const double lim = (double)((1 << 20) - 1);
+        const double p[3] = {x, y, z};
+        int v[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double t = trunc(xyz[3 * i + c] / voxel_size);
-        const bool ok = fabs(t) < lim;   // (false for NaN too)
-        bad = bad || !ok;
-        v[c] = ok ? (int)t : 0;
+        for (int c = 0; c < 3; ++c) {
+            const double t = trunc(p[c] / voxel_size);
+            const bool ok = fabs(t) < lim;   // (false for NaN too)
+            bad = bad || !ok;
+            v[c] = ok ? (int)t : 0;
+        }
+        return grid3::key(v[0], v[1], v[2]);
     }
-    if (bad) atomicOr(status, 1);
-    keys[i] = voxel_key(v[0], v[1], v[2]);
-    idx[i] = (int)i;
-}
+};
 
 // head[i]: sorted position i opens a run of equal keys; keep[i]: it is among the first `cap` positions of its run (cap 0: all) --
 // position i - cap carries another key, or does not exist
@@ -322,7 +265,7 @@ __global__ __launch_bounds__(256) void icp_grid_flags_kernel(const long long* __
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const long long k = ks[i];
-    head[i] = (i == 0 || ks[i - 1] != k) ? 1 : 0;
+    head[i] = grid3::run_head(ks, i) ? 1 : 0;
     keep[i] = (cap <= 0 || i < cap || ks[i - cap] != k) ? 1 : 0;
 }
 
@@ -364,20 +307,8 @@ __global__ void icp_grid_empty_kernel(int* __restrict__ start_out, int* __restri
     }
 }
 
-size_t icp_grid_cub_bytes(int64_t n) {
-    const int ni = (int)(n > 0 ? n : 1);
-    size_t best = 0, b = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (long long*)nullptr, (long long*)nullptr, (int*)nullptr, (int*)nullptr, ni, 0, 63);
-    best = b > best ? b : best;
-    b = 0;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, (int*)nullptr, (int*)nullptr, ni);
-    best = b > best ? b : best;
-    return best + 1024;
-}
-
 struct IcpGridWs {
-    long long* keys_in;
-    int* idx_in;
+    grid3::SortWs<true> s;
     long long* keys;   // sorted
     int* order;        // input index of every sorted position
     int* head;
@@ -385,16 +316,13 @@ struct IcpGridWs {
     int* vid;
     int* kpos;
     int* status;
-    void* cub;
-    size_t cub_bytes;
 };
 
 IcpGridWs carve_icp_grid(void* p, int64_t n, size_t* used = nullptr) {
     VfmCarver c(p);
     const size_t nn = (size_t)(n > 0 ? n : 1);
     IcpGridWs w{};
-    w.keys_in = c.take<long long>(nn);
-    w.idx_in = c.take<int>(nn);
+    w.s = grid3::carve_sort<true>(c, n);
     w.keys = c.take<long long>(nn);
     w.order = c.take<int>(nn);
     w.head = c.take<int>(nn);
@@ -402,8 +330,6 @@ IcpGridWs carve_icp_grid(void* p, int64_t n, size_t* used = nullptr) {
     w.vid = c.take<int>(nn);
     w.kpos = c.take<int>(nn);
     w.status = c.take<int>(1);
-    w.cub_bytes = icp_grid_cub_bytes(n);
-    w.cub = c.take<unsigned char>(w.cub_bytes);
     if (used) *used = c.used();
     return w;
 }
@@ -429,18 +355,13 @@ VFM_EXPORT int vfm_icp_grid_build(const double* xyz, int64_t n, double voxel_siz
     VFM_CHECK_ARG(xyz && keys_out && pts_out && ws, "icp_grid_build: null pointer");
     VFM_CHECK_ARG(ws_bytes >= vfm_icp_grid_workspace_bytes(n), "icp_grid_build: workspace too small");
     IcpGridWs w = carve_icp_grid(ws, n);
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const dim3 grid(grid3::blocks256(n)), block(256);
     VFM_CHECK_HIP(hipMemsetAsync(w.status, 0, sizeof(int), st));
-    hipLaunchKernelGGL(icp_grid_keys_kernel, grid, block, 0, st, xyz, n, voxel_size, w.keys_in, w.idx_in, w.status);
-    VFM_CHECK_LAUNCH("icp_grid_keys_kernel");
-    size_t tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, w.keys, w.idx_in, w.order, (int)n, 0, 63, st));
+    VFM_TRY(grid3::build(xyz, n, IcpVoxels{voxel_size}, w.status, w.s, w.keys, w.order, st));
     hipLaunchKernelGGL(icp_grid_flags_kernel, grid, block, 0, st, w.keys, n, (int)max_points_per_voxel, w.head, w.keep);
     VFM_CHECK_LAUNCH("icp_grid_flags_kernel");
-    tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, tb, w.head, w.vid, (int)n, st));
-    tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(w.cub, tb, w.keep, w.kpos, (int)n, st));
+    VFM_TRY(grid3::inclusive_sum(w.s, n, w.head, w.vid, st));
+    VFM_TRY(grid3::inclusive_sum(w.s, n, w.keep, w.kpos, st));
     hipLaunchKernelGGL(icp_grid_compact_kernel, grid, block, 0, st, xyz, n, w.keys, w.order, w.head, w.keep, w.vid, w.kpos, w.status,
                        reinterpret_cast<long long*>(keys_out), start_out, pts_out, info_out);
     VFM_CHECK_LAUNCH("icp_grid_compact_kernel");
@@ -455,7 +376,7 @@ VFM_EXPORT int vfm_icp_nearest(const double* src, int64_t n, const int64_t* keys
     if (n == 0) return VFM_OK;
     IcpStep step;
     step.apply = 0;
-    hipLaunchKernelGGL(icp_nearest_kernel, dim3((unsigned)((n + 256 / ICP_LANES - 1) / (256 / ICP_LANES))), dim3(256), 0, (hipStream_t)stream, src, n,
+    hipLaunchKernelGGL(icp_nearest_kernel<false>, icp_nearest_grid(n), dim3(256), 0, (hipStream_t)stream, src, n,
                        reinterpret_cast<const long long*>(keys), start, pts, n_voxels, voxel_size, max_dist, tgt_out,
                        valid_out, step, (double*)nullptr);
     VFM_CHECK_LAUNCH("icp_nearest_kernel");
@@ -471,7 +392,7 @@ VFM_EXPORT int vfm_icp_step_nearest(const double* src, int64_t n, const double* 
     IcpStep step;
     for (int k = 0; k < 12; ++k) step.T[k] = T_host[k];
     step.apply = 1;
-    hipLaunchKernelGGL(icp_nearest_kernel, dim3((unsigned)((n + 256 / ICP_LANES - 1) / (256 / ICP_LANES))), dim3(256), 0, (hipStream_t)stream, src, n,
+    hipLaunchKernelGGL(icp_nearest_kernel<false>, icp_nearest_grid(n), dim3(256), 0, (hipStream_t)stream, src, n,
                        reinterpret_cast<const long long*>(keys), start, pts, n_voxels, voxel_size, max_dist, tgt_out,
                        valid_out, step, src_out);
     VFM_CHECK_LAUNCH("icp_nearest_kernel(step)");
@@ -495,14 +416,13 @@ VFM_EXPORT int vfm_icp_step_nearest_desc(const double* src, int64_t n, const dou
                       src_norm && src_has && map_desc && map_norm && map_has && (!T_host || src_out),
                   "icp_step_nearest_desc: bad arguments");
     if (n == 0) return VFM_OK;
-    IcpStep step;
+    IcpDescStep step;
     step.apply = T_host ? 1 : 0;
     for (int k = 0; k < 12; ++k) step.T[k] = T_host ? T_host[k] : 0.0;
-    IcpDesc dd{src_desc, src_norm, src_has, map_desc, map_norm, map_has, (int)f};
-    hipLaunchKernelGGL(icp_nearest_desc_kernel, dim3((unsigned)((n + 256 / ICP_LANES - 1) / (256 / ICP_LANES))), dim3(256), 0, (hipStream_t)stream,
-                       src, n, reinterpret_cast<const long long*>(keys), start, pts, n_voxels, voxel_size, max_dist, tgt_out, valid_out, step,
-                       src_out, dd);
-    VFM_CHECK_LAUNCH("icp_nearest_desc_kernel");
+    step.dd = IcpDesc{src_desc, src_norm, src_has, map_desc, map_norm, map_has, (int)f};
+    hipLaunchKernelGGL(icp_nearest_kernel<true>, icp_nearest_grid(n), dim3(256), 0, (hipStream_t)stream, src, n,
+                       reinterpret_cast<const long long*>(keys), start, pts, n_voxels, voxel_size, max_dist, tgt_out, valid_out, step, src_out);
+    VFM_CHECK_LAUNCH("icp_nearest_kernel<true>");
     return VFM_OK;
 }
 

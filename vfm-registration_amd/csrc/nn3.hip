@@ -1,14 +1,12 @@
 // nn3.hip -- exact 1-nearest-neighbour search in 3-D on MI355X (gfx950): the two sklearn.neighbors.KDTree(X, metric="euclidean")
 // .query(Q, k=1) calls of registration_node.py:295-298, which recover the row of every correspondence point in the voxelised clouds.
-//   nn3_keys_kernel / nn3_gather_kernel  a sorted-key CSR grid over the cloud (cell = the caller's), points copied in cell order
+//   Nn3Cells (grid3.h) / nn3_gather_kernel a sorted-key CSR grid over the cloud (cell = the caller's), points copied in cell order
 //   nn3_query_kernel                     one wave per query: the 27 cells around the query, then shells of cells, until the best d2
 //                                        is below anything a cell outside the searched cube can hold; past NN3_MAX_RINGS shells a scan
 //                                        of every point (queries far from the cloud, or in its empty regions)
 // fp64, -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, dist = sqrt(d2) (correctly rounded), equal d2 to the lower index (a
 // convention of this library; sklearn leaves it unspecified).  tests/nn3_oracle.py repeats it in numpy.
-#include <hipcub/hipcub.hpp>
-
-#include "common.h"
+#include "grid3.h"
 
 namespace {
 
@@ -20,22 +18,14 @@ constexpr int NN3_LIM = (1 << 20) - 16;          // cells are clamped to +-NN3_L
 // least that squared.  The bound used is r cells shortened by 1e-6 relative: far more than every rounding on the way.
 constexpr double NN3_RING_SLACK = 1.0 - 1e-6;
 
-__device__ __forceinline__ long long nn3_cell(double x, double inv_cell) {
-    double c = floor(x * inv_cell);
-    c = fmin(fmax(c, (double)-NN3_LIM), (double)NN3_LIM);   // (NaN -> -NN3_LIM)
-    return (long long)c;
-}
-__device__ __forceinline__ long long nn3_key(long long cx, long long cy, long long cz) {
-    return ((cx + (1 << 20)) << 42) | ((cy + (1 << 20)) << 21) | (cz + (1 << 20));
-}
-
-__global__ __launch_bounds__(256) void nn3_keys_kernel(const double* __restrict__ pts, int64_t n, double inv_cell,
-                                                       long long* __restrict__ keys, int* __restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = nn3_key(nn3_cell(pts[3 * i], inv_cell), nn3_cell(pts[3 * i + 1], inv_cell), nn3_cell(pts[3 * i + 2], inv_cell));
-    idx[i] = (int)i;
-}
+__device__ __forceinline__ long long nn3_cell(double x, double inv_cell) { return grid3::cell(x, inv_cell, NN3_LIM); }
+struct Nn3Cells {   // the quantiser of grid3::keys_kernel
+    static constexpr const char* kernel_name = "grid3::keys_kernel<Nn3Cells>";
+    double inv_cell;
+    __device__ long long operator()(double x, double y, double z, bool&) const {
+        return grid3::key(nn3_cell(x, inv_cell), nn3_cell(y, inv_cell), nn3_cell(z, inv_cell));
+    }
+};
 
 __global__ __launch_bounds__(256) void nn3_gather_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ order,
                                                          double* __restrict__ sorted) {
@@ -47,45 +37,16 @@ __global__ __launch_bounds__(256) void nn3_gather_kernel(const double* __restric
     sorted[3 * i + 2] = pts[3 * j + 2];
 }
 
-__device__ __forceinline__ int nn3_lower_bound(const long long* __restrict__ a, int n, long long key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-struct Nn3Best {
-    double d2;
-    int idx;
-};
-
-__device__ __forceinline__ void nn3_take(Nn3Best& b, double d2, int j) {
-    if (d2 < b.d2 || (d2 == b.d2 && j < b.idx)) {
-        b.d2 = d2;
-        b.idx = j;
-    }
-}
+using grid3::Best;
 
 // the points sorted[lo, lo + len) against the query, a lane per point
-__device__ __forceinline__ void nn3_scan_run(Nn3Best& b, const double* __restrict__ sorted, const int* __restrict__ order, int lo, int len,
+__device__ __forceinline__ void nn3_scan_run(Best& b, const double* __restrict__ sorted, const int* __restrict__ order, int lo, int len,
                                              double qx, double qy, double qz, int lane) {
     for (int t = lane; t < len; t += 64) {
         const int64_t s = lo + t;
         const double dx = sorted[3 * s] - qx, dy = sorted[3 * s + 1] - qy, dz = sorted[3 * s + 2] - qz;
-        nn3_take(b, (dx * dx + dy * dy) + dz * dz, order[s]);
+        grid3::take(b, (dx * dx + dy * dy) + dz * dz, order[s]);
     }
-}
-
-__device__ __forceinline__ Nn3Best nn3_wave_best(Nn3Best b) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double od = __shfl_xor(b.d2, off);
-        const int oi = __shfl_xor(b.idx, off);
-        nn3_take(b, od, oi);
-    }
-    return b;   // the same in every lane
 }
 
 // One wave (= one workgroup) per query.  Shell r is walked by columns (ax, ay) of the (2r + 1)^2 square: the z-cells of a column are
@@ -100,7 +61,7 @@ __global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict_
     const int lane = threadIdx.x;
     const double qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
     const long long cx = nn3_cell(qx, inv_cell), cy = nn3_cell(qy, inv_cell), cz = nn3_cell(qz, inv_cell);
-    Nn3Best best{INFINITY, 0x7FFFFFFF};
+    Best best{INFINITY, 0x7FFFFFFF};
     bool done = false;
     for (int r = 1; r <= NN3_MAX_RINGS && !done; ++r) {
         const int side = 2 * r + 1;
@@ -113,13 +74,13 @@ __global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict_
                 const long long ax = cx + dx, ay = cy + dy;
                 const bool whole = r == 1 || dx == -r || dx == r || dy == -r || dy == r;
                 if (whole) {
-                    lo_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r));
-                    len_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r) + 1) - lo_a;
+                    lo_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r));
+                    len_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r) + 1) - lo_a;
                 } else {
-                    lo_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r));
-                    len_a = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz - r) + 1) - lo_a;
-                    lo_b = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r));
-                    len_b = nn3_lower_bound(keys, n, nn3_key(ax, ay, cz + r) + 1) - lo_b;
+                    lo_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r));
+                    len_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r) + 1) - lo_a;
+                    lo_b = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r));
+                    len_b = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r) + 1) - lo_b;
                 }
             }
             unsigned long long ma = __ballot(len_a > 0);
@@ -135,14 +96,14 @@ __global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict_
                 nn3_scan_run(best, sorted, order, __shfl(lo_b, src), __shfl(len_b, src), qx, qy, qz, lane);
             }
         }
-        best = nn3_wave_best(best);
+        best = grid3::wave_best(best);
         const double reach = ((double)r * cell) * NN3_RING_SLACK;
         done = best.d2 < reach * reach;
     }
     if (!done) {
         // more shells than the cap: every point (the shells already searched are read again -- the best of all is the best)
         nn3_scan_run(best, sorted, order, 0, n, qx, qy, qz, lane);
-        best = nn3_wave_best(best);
+        best = grid3::wave_best(best);
         if (fallback_count && lane == 0) atomicAdd(fallback_count, 1);
     }
     if (lane == 0) {
@@ -152,28 +113,9 @@ __global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict_
     }
 }
 
-size_t nn3_cub_bytes(int64_t n) {
-    size_t b = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (long long*)nullptr, (long long*)nullptr, (int*)nullptr, (int*)nullptr,
-                                             (int)(n > 0 ? n : 1), 0, 64);
-    return b + 1024;
-}
-
-struct Nn3Ws {
-    long long* keys_in;
-    int* idx_in;
-    void* cub;
-    size_t cub_bytes;
-};
-
-Nn3Ws carve_nn3(void* p, int64_t n, size_t* used = nullptr) {
+grid3::SortWs<false> carve_nn3(void* p, int64_t n, size_t* used = nullptr) {
     VfmCarver c(p);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    Nn3Ws w{};
-    w.keys_in = c.take<long long>(nn);
-    w.idx_in = c.take<int>(nn);
-    w.cub_bytes = nn3_cub_bytes(n);
-    w.cub = c.take<unsigned char>(w.cub_bytes);
+    const grid3::SortWs<false> w = grid3::carve_sort<false>(c, n);
     if (used) *used = c.used();
     return w;
 }
@@ -193,14 +135,9 @@ VFM_EXPORT int vfm_nn3_build(const double* pts, int64_t n, double cell, int64_t*
     VFM_CHECK_ARG(pts && keys_out && order_out && sorted_out && ws, "nn3_build: null pointer");
     VFM_CHECK_ARG(ws_bytes >= vfm_nn3_workspace_bytes(n), "nn3_build: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    Nn3Ws w = carve_nn3(ws, n);
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(nn3_keys_kernel, dim3(blocks), dim3(256), 0, st, pts, n, 1.0 / cell, w.keys_in, w.idx_in);
-    VFM_CHECK_LAUNCH("nn3_keys_kernel");
-    size_t tb = w.cub_bytes;
-    VFM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub, tb, w.keys_in, reinterpret_cast<long long*>(keys_out), w.idx_in, order_out, (int)n,
-                                                     0, 64, st));
-    hipLaunchKernelGGL(nn3_gather_kernel, dim3(blocks), dim3(256), 0, st, pts, n, order_out, sorted_out);
+    const grid3::SortWs<false> w = carve_nn3(ws, n);
+    VFM_TRY(grid3::build(pts, n, Nn3Cells{1.0 / cell}, nullptr, w, reinterpret_cast<long long*>(keys_out), order_out, st));
+    hipLaunchKernelGGL(nn3_gather_kernel, dim3(grid3::blocks256(n)), dim3(256), 0, st, pts, n, order_out, sorted_out);
     VFM_CHECK_LAUNCH("nn3_gather_kernel");
     return VFM_OK;
 }

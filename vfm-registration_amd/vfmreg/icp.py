@@ -47,7 +47,7 @@ class VoxelGridDevice:
     def __init__(self, points: np.ndarray, voxel_size: float):
         pts = np.ascontiguousarray(points[:, :3], dtype=np.float64)
         v = np.trunc(pts / voxel_size).astype(np.int64)
-        # the CSR key packs 21 bits per axis (csrc/icp.hip voxel_key); the 27-neighbour scan reaches v +- 1
+        # the CSR key packs 21 bits per axis (csrc/grid3.h: grid3::key); the 27-neighbour scan reaches v +- 1
         if len(v) and (np.abs(v).max() >= (1 << 20) - 1):
             raise ValueError("voxel coordinate outside +-2^20 voxels: shift the clouds towards the origin "
                              "(the ICP grid key holds 21 bits per axis)")
@@ -323,7 +323,7 @@ class _DescGrid:
 
 def _register_frame_xd(points: np.ndarray, voxel_map, initial_guess: np.ndarray, max_correspondance_distance: float, kernel: float):
     """RegisterFrame(std::vector<Eigen::VectorXd> ...) (Registration.cpp:384-423): the 3-D loop with the descriptor-weighted nearest
-    neighbour of VoxelHashMap.cpp:321-448 as its search (csrc/icp.hip icp_nearest_desc_kernel).  Every iterate equals the oracle's
+    neighbour of VoxelHashMap.cpp:321-448 as its search (csrc/icp.hip icp_nearest_kernel<true>).  Every iterate equals the oracle's
     (oracle.register_frame_xd) bit for bit."""
     lib = _lib.load()
     st = ops._stream()
