@@ -100,7 +100,7 @@ def _eigenvector0(A, e):
     return v / s[:, None]
 
 
-def _eigenvector1(A, e0, eval1):
+def _eigenvector1(A, e0, eval1, want_arm: bool = False):
     big = np.abs(e0[:, 0]) > np.abs(e0[:, 1])
     il_a = 1.0 / np.sqrt(e0[:, 0] * e0[:, 0] + e0[:, 2] * e0[:, 2])
     il_b = 1.0 / np.sqrt(e0[:, 1] * e0[:, 1] + e0[:, 2] * e0[:, 2])
@@ -141,11 +141,43 @@ def _eigenvector1(A, e0, eval1):
     a, b = np.where(first, a1, a2), np.where(first, b1, b2)
     ok = np.where(first, ok1, ok2)
     r = a[:, None] * U - b[:, None] * V
-    return _w(ok, r, U)
+    out = _w(ok, r, U)
+    if not want_arm:
+        return out
+    arm = np.where(first, np.where(ok1, np.where(t1, EV1_M00_DIV, EV1_M00_INV), EV1_M00_ZERO),
+                   np.where(ok2, np.where(t2, EV1_M11_DIV, EV1_M11_INV), EV1_M11_ZERO))
+    return out, np.where(big, EV1_U_XZ, EV1_U_YZ), arm
 
 
-def fast_eigen3x3(C: np.ndarray) -> np.ndarray:
-    """Open3D 0.18 FastEigen3x3 for a stack of 3 x 3 matrices: the eigenvector of the smallest eigenvalue (0 for a zero matrix)."""
+# Which exit of csrc/fpfh.hip's fast_eigen3x3 a row took (``fast_eigen3x3(C, branches=True)``), next to the kernel line it mirrors:
+EIG_ZERO = 0        # if (mc == 0.0): the zero vector (fpfh_normal_kernel then writes (0, 0, 1))
+EIG_DIAG_X = 1      # norm == 0:  if (d0 < d1 && d0 < d2) out[0] = 1.0
+EIG_DIAG_Y = 2      #             else if (d1 < d0 && d1 < d2) out[1] = 1.0
+EIG_DIAG_Z = 3      #             else out[2] = 1.0, with d2 strictly the smallest
+EIG_DIAG_TIE = 4    #             else out[2] = 1.0, by the tie rule: no diagonal entry is strictly the smallest
+EIG_POS_EVEC = 5    # half_det >= 0: if (eval2 < eval0 && eval2 < eval1) -> eigenvector0(A, eval2)
+EIG_POS_EVEC1 = 6   #                if (eval1 < eval0 && eval1 < eval2) -> eigenvector1
+EIG_POS_CROSS = 7   #                cross3(e1, e0, out)
+EIG_NEG_EVEC = 8    # half_det < 0:  if (eval0 < eval1 && eval0 < eval2) -> eigenvector0(A, eval0)
+EIG_NEG_EVEC1 = 9   #                if (eval1 < eval0 && eval1 < eval2) -> eigenvector1
+EIG_NEG_CROSS = 10  #                cross3(e0, e1, out)
+EIG_EXITS = tuple(range(11))
+# eigenvector1, for the rows whose exit went through it (EIG_*_EVEC1, EIG_*_CROSS; -1 elsewhere).  The U construction:
+EV1_U_XZ = 0        # if (fabs(evec0[0]) > fabs(evec0[1])): U = (-e2, 0, e0) / length
+EV1_U_YZ = 1        # else:                                 U = (0, e2, -e1) / length
+# and the arm that normalises (m00, m01, m11):
+EV1_M00_DIV = 0     # absM00 >= absM11, absM00 >= absM01: m01 /= m00
+EV1_M00_INV = 1     # absM00 >= absM11, else:             m00 /= m01
+EV1_M00_ZERO = 2    # absM00 >= absM11, !(mx > 0): return U
+EV1_M11_DIV = 3     # else, absM11 >= absM01: m01 /= m11
+EV1_M11_INV = 4     # else, else:             m11 /= m01
+EV1_M11_ZERO = 5    # else, !(mx > 0): return U (absM00 >= absM11 was false with absM11 not above 0: a NaN in m00 or m11)
+EV1_ARMS = tuple(range(6))
+
+
+def fast_eigen3x3(C: np.ndarray, branches: bool = False):
+    """Open3D 0.18 FastEigen3x3 for a stack of 3 x 3 matrices: the eigenvector of the smallest eigenvalue (0 for a zero matrix).
+    With ``branches``: (vectors, exit int[M] (EIG_*), U construction int[M] (EV1_U_*, -1), eigenvector1 arm int[M] (EV1_M*, -1))."""
     C = np.asarray(C, dtype=np.float64).reshape(-1, 3, 3)
     with np.errstate(all="ignore"):
         mc = C.reshape(-1, 9).max(axis=1)
@@ -167,7 +199,7 @@ def fast_eigen3x3(C: np.ndarray) -> np.ndarray:
         pos = half_det >= 0
         ef = _eigenvector0(A, np.where(pos, ev2, ev0))
         c1 = np.where(pos, (ev2 < ev0) & (ev2 < ev1), (ev0 < ev1) & (ev0 < ev2))
-        e1 = _eigenvector1(A, ef, ev1)
+        e1, u_id, arm = _eigenvector1(A, ef, ev1, want_arm=True)
         c2 = (ev1 < ev0) & (ev1 < ev2)
         last = _w(pos, _cross(e1, ef), _cross(ef, e1))
         off = _w(c1, ef, _w(c2, e1, last))
@@ -175,7 +207,16 @@ def fast_eigen3x3(C: np.ndarray) -> np.ndarray:
         ax = np.where((d0 < d1) & (d0 < d2), 0, np.where((d1 < d0) & (d1 < d2), 1, 2))
         diag = np.eye(3)[ax]
         out = _w(norm > 0, off, diag)
-        return _w(mc == 0, np.zeros_like(out), out)
+        out = _w(mc == 0, np.zeros_like(out), out)
+        if not branches:
+            return out
+        ex_off = np.where(pos, np.where(c1, EIG_POS_EVEC, np.where(c2, EIG_POS_EVEC1, EIG_POS_CROSS)),
+                          np.where(c1, EIG_NEG_EVEC, np.where(c2, EIG_NEG_EVEC1, EIG_NEG_CROSS)))
+        strict_z = (d2 < d0) & (d2 < d1)
+        ex_diag = np.where(ax == 0, EIG_DIAG_X, np.where(ax == 1, EIG_DIAG_Y, np.where(strict_z, EIG_DIAG_Z, EIG_DIAG_TIE)))
+        ex = np.where(mc == 0, EIG_ZERO, np.where(norm > 0, ex_off, ex_diag))
+        used1 = (norm > 0) & (mc != 0) & ~c1
+        return out, ex, np.where(used1, u_id, -1), np.where(used1, arm, -1)
 
 
 def covariances(pts: np.ndarray, idx: np.ndarray, cnt: np.ndarray) -> np.ndarray:
@@ -241,9 +282,24 @@ def voxel_down_sample(pts: np.ndarray, voxel_size: float, normals: np.ndarray | 
 
 
 # ------------------------------------------------------------------------------------------------ features
-def pair_features(p1, n1, p2, n2):
+# Which exit of csrc/fpfh.hip's pair_features a pair took (``pair_features(..., branches=True)``):
+PAIR_DN_ZERO = 0       # if (dn == 0.0) return: coincident points, all three features 0
+PAIR_VN_ZERO = 1       # if (vn == 0.0) return, roles kept: n1 parallel to d (or a zero n1)
+PAIR_VN_ZERO_SWAP = 2  # if (vn == 0.0) return, after the swap: n2 parallel to d
+PAIR_KEPT = 3          # acos(fabs(angle1)) < acos(fabs(angle2)): roles kept
+PAIR_KEPT_TIE = 4      # acos(fabs(angle1)) == acos(fabs(angle2)): the strict > keeps the roles on the exact tie
+PAIR_SWAP = 5          # acos(fabs(angle1)) > acos(fabs(angle2)): a = n2, b = n1, d = -d, f2 = -angle2
+PAIR_KEPT_NAN = 6      # a NaN on either side of the > (|angle| > 1 from a normal longer than 1): roles kept
+PAIR_EXITS = tuple(range(7))
+
+
+def pair_features(p1, n1, p2, n2, branches: bool = False, exact_ok: bool = False):
     """ComputePairFeatures for stacks of pairs: (f fp64[M, 3], margin fp64[M]).  margin: the smallest distance of a bin coordinate
-    (11 (f0 + pi) / 2 pi, 11 (f1 + 1) / 2, 11 (f2 + 1) / 2) from an integer, or of the two acos values the swap compares."""
+    (11 (f0 + pi) / 2 pi, 11 (f1 + 1) / 2, 11 (f2 + 1) / 2) from an integer, or of the two acos values the swap compares.
+    ``exact_ok``: what no rounding of a libm call can move is left out of the margin -- a feature that IS an end of its range
+    (f0 = -+pi, which atan2 returns only for a zero of either sign over a negative number; f1, f2 = -+1, which come from sqrt,
+    division, products and sums alone; the bin coordinate follows by products and sums too), and a swap comparison whose two arguments
+    |angle1| and |angle2| are the same number.  ``branches``: also exit int[M] (PAIR_*)."""
     with np.errstate(all="ignore"):
         d = p2 - p1
         dn = np.sqrt(_dot(d, d))
@@ -264,28 +320,51 @@ def pair_features(p1, n1, p2, n2):
         zero = (dn == 0.0) | (vn == 0.0)
         f[zero] = 0.0
         x = _bin_coords(f)
-        margin = np.min(np.abs(x - np.round(x)), axis=1)
-        margin = np.where(zero, np.inf, np.minimum(margin, np.abs(c1 - c2)))
-    return f, margin
+        mx = np.abs(x - np.round(x))
+        gap = np.abs(c1 - c2)
+        if exact_ok:
+            ends = np.stack([np.abs(f[:, 0]) == PI, np.abs(f[:, 1]) == 1.0, np.abs(f[:, 2]) == 1.0], -1)
+            mx = np.where(ends, np.inf, mx)
+            gap = np.where(np.abs(a1) == np.abs(a2), np.inf, gap)
+        margin = np.min(mx, axis=1)
+        margin = np.where(zero, np.inf, (np.fmin if exact_ok else np.minimum)(margin, gap))
+        if not branches:
+            return f, margin
+        full = np.where(swap, PAIR_SWAP, np.where(c1 < c2, PAIR_KEPT, np.where(c1 == c2, PAIR_KEPT_TIE, PAIR_KEPT_NAN)))
+        ex = np.where(dn == 0.0, PAIR_DN_ZERO, np.where(vn == 0.0, np.where(swap, PAIR_VN_ZERO_SWAP, PAIR_VN_ZERO), full))
+    return f, margin, ex
 
 
 def _bin_coords(f):
     return np.stack([11.0 * (f[:, 0] + PI) / (2.0 * PI), 11.0 * (f[:, 1] + 1.0) * 0.5, 11.0 * (f[:, 2] + 1.0) * 0.5], -1)
 
 
-def spfh(pts: np.ndarray, normals: np.ndarray, idx: np.ndarray, cnt: np.ndarray, edge: float = 1e-9):
-    """ComputeSPFHFeature: (spfh fp64[n, 33], near_edge bool[n] -- some pair of the row within `edge` of a bin edge)."""
+def spfh(pts: np.ndarray, normals: np.ndarray, idx: np.ndarray, cnt: np.ndarray, edge: float = 1e-9, exact_ok: bool = False,
+         branches: bool = False):
+    """ComputeSPFHFeature: (spfh fp64[n, 33], near_edge bool[n] -- some pair of the row within `edge` of a bin edge).  ``exact_ok``:
+    see pair_features.  ``branches``: also int[n, len(PAIR_EXITS)], how many pairs of the row took each exit of pair_features, and
+    int[n, 3, 2], how many of its pairs put feature g on or below the lower end of its range (-pi, -1, -1: clamp_bin's bin 0) and on or
+    above the upper end (its bin 10, where h >= 11 is clamped)."""
     n, kmax = idx.shape
     counts = np.zeros((n, 33), dtype=np.int64)
     near = np.zeros(n, dtype=bool)
+    exits = np.zeros((n, len(PAIR_EXITS)), dtype=np.int64)
+    ends = np.zeros((n, 3, 2), dtype=np.int64)
     for k in range(1, kmax):
         live = k < cnt
         if not live.any():
             break
         i = np.flatnonzero(live)
         j = idx[i, k]
-        f, margin = pair_features(pts[i], normals[i], pts[j], normals[j])
-        h = np.clip(np.floor(_bin_coords(f)), -1, 11)
+        f, margin, ex = pair_features(pts[i], normals[i], pts[j], normals[j], branches=True, exact_ok=exact_ok)
+        np.add.at(exits, (i, ex), 1)
+        with np.errstate(all="ignore"):
+            x = _bin_coords(f)
+        top = np.array([PI, 1.0, 1.0])
+        for g in range(3):
+            np.add.at(ends[:, g, 0], i, (f[:, g] <= -top[g]).astype(np.int64))
+            np.add.at(ends[:, g, 1], i, (f[:, g] >= top[g]).astype(np.int64))
+        h = np.clip(np.floor(x), -1, 11)
         h = np.clip(h, 0, 10).astype(np.int64) + np.array([0, 11, 22])
         for g in range(3):
             np.add.at(counts, (i, h[:, g]), 1)
@@ -297,6 +376,8 @@ def spfh(pts: np.ndarray, normals: np.ndarray, idx: np.ndarray, cnt: np.ndarray,
     for t in range(int(counts.max()) if counts.size else 0):
         out = np.where(t < counts, out + incr[:, None], out)
     out[~has] = 0.0
+    if branches:
+        return out, near, exits, ends
     return out, near
 
 

@@ -176,3 +176,106 @@ def test_fpfh_entry_points_are_declared_and_exported():
     assert lib.vfm_fpfh_grid_build(1, 10, -1.0, 1, 1, 1, 1 << 30, None) != 0
     assert lib.vfm_fpfh_voxel_down_sample(1, None, 10, 0.1, 1, None, 1, 1, 16, None) != 0
     assert b"workspace" in lib.vfm_last_error()
+
+
+# ------------------------------------------------------------------------------------ the crafted rows of tests/fpfh_branch_cases.py
+# Exits no finite input reaches, so the census cannot ask rows of them:
+#   EIG_POS_EVEC   eval2 = q + p beta2 with beta2 = 2 cos(angle) >= sqrt(3) and beta0 <= -1: p >= 0 and rounding is monotone, so
+#                  eval2 < eval0 never holds;
+#   EIG_POS_EVEC1, EIG_NEG_EVEC1   want eval1 < eval0, that is beta1 < beta0 after monotone rounding; beta0 <= beta1 over the whole
+#                  range of half_det (test_eigenvalue_order_leaves_three_exits_dead sweeps it, the ends and their neighbours included);
+#   EV1_M11_ZERO   |m00| >= |m11| is false with |m11| not above 0 only if m00 or m11 is a NaN; a NaN covariance has norm > 0 false and
+#                  takes the diagonal branch, and eigenvector0 divides by a length that is 0 only if norm is.
+DEAD_EIG_EXITS = (fo.EIG_POS_EVEC, fo.EIG_POS_EVEC1, fo.EIG_NEG_EVEC1)
+DEAD_EV1_ARMS = (fo.EV1_M11_ZERO,)
+
+
+def test_eigenvalue_order_leaves_three_exits_dead():
+    hd = np.concatenate([np.linspace(-1.0, 1.0, 2000001), np.nextafter(1.0, 0) - np.arange(64) * 2.0 ** -53,
+                         -1.0 + np.arange(64) * 2.0 ** -53, np.arange(-64, 65) * 2.0 ** -1074, np.arange(-64, 65) * 2.0 ** -60])
+    angle = np.arccos(hd) / 3.0
+    beta2 = np.cos(angle) * 2.0
+    beta0 = np.cos(angle + 2.09439510239319549) * 2.0
+    beta1 = -(beta0 + beta2)
+    assert (beta0 <= beta1).all() and (beta0 < beta2).all()
+
+
+@pytest.fixture(scope="module")
+def normal_rows():
+    from tests import fpfh_branch_cases as bc
+    c = bc.normal_cases()
+    C = fo.covariances(c["pts"], c["idx"], c["count"])
+    nv, ex, u, arm = fo.fast_eigen3x3(C, branches=True)
+    return c, C, nv, ex, u, arm
+
+
+def test_branch_census_of_the_crafted_normals(normal_rows):
+    c, C, nv, ex, u, arm = normal_rows
+    assert len(c["pts"]) <= 5000
+    for e in fo.EIG_EXITS:
+        rows = int((ex == e).sum())
+        assert rows == 0 if e in DEAD_EIG_EXITS else rows >= 3, (e, rows)
+    for a in fo.EV1_ARMS:
+        rows = int((arm == a).sum())
+        assert rows == 0 if a in DEAD_EV1_ARMS else rows >= 3, (a, rows)
+    for uc in (fo.EV1_U_XZ, fo.EV1_U_YZ):
+        assert (u == uc).sum() >= 3
+    for k in (0, 1, 2):
+        assert (c["count"] == k).sum() >= 3
+    assert ((c["count"] < 3) == (np.char.startswith(c["kind"], "cnt"))).all()
+    assert (ex[c["count"] < 3] == fo.EIG_DIAG_TIE).all()                       # the identity: a three-way tie
+    # every family of the case list took the exits it was made for
+    want = {"zero": {fo.EIG_ZERO}, "diag_x": {fo.EIG_DIAG_X}, "diag_y": {fo.EIG_DIAG_Y}, "diag_z": {fo.EIG_DIAG_Z},
+            "diag_tie": {fo.EIG_DIAG_TIE}, "isotropic": {fo.EIG_POS_CROSS, fo.EIG_NEG_CROSS}}
+    for kind, exits in want.items():
+        assert set(ex[c["kind"] == kind].tolist()) == exits, kind
+    shifted = np.char.endswith(c["kind"], "_shifted")
+    assert {fo.EIG_POS_CROSS, fo.EIG_NEG_EVEC} <= set(ex[shifted].tolist())
+    assert np.isfinite(nv).all()
+    est = fo.estimate_normals(c["pts"], c["idx"], c["count"])
+    np.testing.assert_array_equal(est[ex == fo.EIG_ZERO], np.tile([0.0, 0.0, 1.0], (int((ex == fo.EIG_ZERO).sum()), 1)))
+
+
+def gapped_rows(C):
+    """rows with a unique smallest eigenvalue: (lambda1 - lambda0) / lambda2 >= 1e-3; and the eigh vectors"""
+    w, V = np.linalg.eigh(C)
+    with np.errstate(all="ignore"):
+        gap = (w[:, 1] - w[:, 0]) / w[:, 2]
+    return gap >= 1e-3, V[:, :, 0]
+
+
+def test_crafted_gapped_normals_are_the_smallest_eigenvector(normal_rows):
+    c, C, nv, ex, u, arm = normal_rows
+    gapped, v0 = gapped_rows(C)
+    rows = np.flatnonzero(gapped & (c["count"] >= 3))
+    assert len(rows) >= 60 and {fo.EIG_DIAG_X, fo.EIG_DIAG_Y, fo.EIG_DIAG_Z, fo.EIG_POS_CROSS, fo.EIG_NEG_EVEC} <= set(ex[rows].tolist())
+    worst = np.abs(np.abs(np.einsum("ij,ij->i", v0[rows], nv[rows])) - 1.0)
+    assert worst.max() < 1e-9, (rows[worst.argmax()], worst.max())
+
+
+def test_crafted_feature_rows_census_and_no_flagged_row():
+    from tests import fpfh_branch_cases as bc
+    f = bc.feature_cases()
+    assert len(f["pts"]) <= 5000
+    sp, near, exits, ends = fo.spfh(f["pts"], f["normals"], f["idx"], f["count"], exact_ok=True, branches=True)
+    _, fnear = fo.fpfh(sp, f["idx"], f["d2"], f["count"], near)
+    assert not near.any() and not fnear.any()
+    # the rows that sit on an edge on purpose are the ones the plain margin flags: every one of them is exact
+    _, plain = fo.spfh(f["pts"], f["normals"], f["idx"], f["count"])
+    assert plain.any()
+    for e in fo.PAIR_EXITS:
+        assert (exits[:, e] > 0).sum() >= 3, e
+    assert (ends.sum(0) >= 3).all(), ends.sum(0)             # clamp_bin's bin 0 and bin 10, for each of the three features
+    kinds = f["kind"]
+    assert exits[kinds == "symmetric"][:, fo.PAIR_KEPT_TIE].sum() >= 9
+    assert (exits[kinds == "coincident"][:, fo.PAIR_DN_ZERO] == 2).all()
+    for k in (0, 1, 2, 64, 65, 1024):
+        assert (f["count"] == k).sum() >= (1 if k == 1024 else 3), k
+    assert (sp[f["count"] <= 1] == 0).all()
+    # s == 0: every weighted neighbour's SPFH row is zero
+    rows = np.flatnonzero(kinds == "zero_spfh_nbrs")
+    assert len(rows) >= 3
+    for r in rows:
+        assert (sp[f["idx"][r, 1:f["count"][r]]] == 0).all() and (f["d2"][r, 1:f["count"][r]] > 0).all()
+    # the dist == 0 skip
+    assert ((f["d2"][:, 1:] == 0) & (np.arange(1, f["idx"].shape[1]) < f["count"][:, None])).sum() >= 3

@@ -20,24 +20,19 @@ def _scene(seed=5, n=3000, m=30000):
     return p, mp
 
 
-def test_icp_kernels_bit_exact():
+def _assert_icp_kernels_bit_exact(src, mp, max_dists, expect=None):
+    """vfm_icp_nearest and vfm_icp_build_system on (src, the grid of mp at voxel 1.0) against the oracle's, bit for bit"""
     import ctypes as C
     from oracle import oracle as orc
     from vfmreg import _lib, ops
     from vfmreg.icp import VoxelGridDevice
     lib = _lib.load()
-    p, mp = _scene()
-    T0 = p["T_gt"].copy()
-    T0[:3, 3] += [0.3, -0.2, 0.1]
-    src = orc.transform_pcl(p["q_xyz"], T0)
-    src[5] = [500.0, 500.0, 500.0]        # far from every voxel: no neighbour -> invalid
-    src[6] = mp[17] + [0.0, 0.0, 1e-9]    # practically on a map point
     keys, start, pts = orc.voxel_grid_csr(mp, 1.0)
     g = VoxelGridDevice(mp, 1.0)
     np.testing.assert_array_equal(g.keys.cpu().numpy(), keys)
     np.testing.assert_array_equal(g.start.cpu().numpy(), start)
     n = len(src)
-    for max_dist in (6.0, 0.4):
+    for max_dist in max_dists:
         tgt_r = np.empty_like(src)
         val_r = np.empty(n, dtype=np.uint8)
         orc.lib().orc_icp_nearest(orc._p(src, orc._f64p), C.c_int64(n), orc._p(keys, orc._i64p), orc._p(start, orc._i32p),
@@ -50,7 +45,8 @@ def test_icp_kernels_bit_exact():
                                        g.n_voxels, 1.0, max_dist, tgt.data_ptr(), val.data_ptr(), ops._stream()))
         np.testing.assert_array_equal(val.cpu().numpy(), val_r)
         np.testing.assert_array_equal(tgt.cpu().numpy()[val_r > 0], tgt_r[val_r > 0])
-        assert val_r[5] == 0 and val_r[6] == 1 and 0 < val_r.sum() <= n
+        if expect is not None:
+            expect(val_r)
         # brute-force check of the neighbour search itself (all map points within reach are in the 27 voxels
         # only if they are closer than one voxel: compare where the true NN is within 1 m)
         d = np.linalg.norm(mp[None, :, :] - src[:200, None, :], axis=2)
@@ -66,6 +62,42 @@ def test_icp_kernels_bit_exact():
         np.testing.assert_array_equal(out.cpu().numpy(), out_r)
         assert out_r[42] == val_r.sum()
         np.testing.assert_allclose(out_r[:36].reshape(6, 6), out_r[:36].reshape(6, 6).T, rtol=1e-12)
+
+
+def test_icp_kernels_bit_exact():
+    from oracle import oracle as orc
+    p, mp = _scene()
+    T0 = p["T_gt"].copy()
+    T0[:3, 3] += [0.3, -0.2, 0.1]
+    src = orc.transform_pcl(p["q_xyz"], T0)
+    src[5] = [500.0, 500.0, 500.0]        # far from every voxel: no neighbour -> invalid
+    src[6] = mp[17] + [0.0, 0.0, 1e-9]    # practically on a map point
+    n = len(src)
+
+    def expect(val_r):
+        assert val_r[5] == 0 and val_r[6] == 1 and 0 < val_r.sum() <= n
+    _assert_icp_kernels_bit_exact(src, mp, (6.0, 0.4), expect)
+
+
+def test_icp_kernels_bit_exact_at_the_last_voxel_of_the_key():
+    """Map and query voxels at +-(2^20 - 2), the largest the ICP quantiser accepts, in one axis and in all three: the 27-voxel probe
+    reaches the field values 2^21 - 1 and 1, the last the 21 bits hold (csrc/grid3.h)."""
+    rng = np.random.default_rng(0)
+    V = (1 << 20) - 2
+    blocks = []
+    for s in (1, -1):
+        b = rng.uniform(0, 1, (300, 3)) * np.array([2, 3, 3]) + np.array([V - 1, -1, -1])
+        c = rng.uniform(0, 1, (300, 3)) * 2 + (V - 1)
+        blocks += [np.minimum(b, V + 0.999) * np.array([s, 1, 1]), np.minimum(c, V + 0.999) * s]
+    mp = np.concatenate(blocks)
+    src = np.clip(mp[::3] + rng.uniform(-0.3, 0.3, (len(mp[::3]), 3)), -(V + 0.999), V + 0.999)
+    src = src[rng.permutation(len(src))]
+    vox = np.trunc(src).astype(np.int64)
+    assert (vox == V).any(0).all() and (vox == -V).any(0).all() and ((vox == V).all(1)).any() and ((vox == -V).all(1)).any()
+
+    def expect(val_r):
+        assert val_r.all()                 # every query lies within 0.52 of a map point
+    _assert_icp_kernels_bit_exact(src, mp, (6.0, 0.6), expect)
 
 
 def test_register_frame_matches_oracle_and_refines_pose():

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64) void fpfh_search_kernel(const double* __restric
     if (lane < 9) {
         const long long ax = cx - 1 + lane / 3, ay = cy - 1 + lane % 3;
         run_lo = grid3::lower_bound(keys, (int)n, grid3::key(ax, ay, cz - 1));
-        run_len = grid3::lower_bound(keys, (int)n, grid3::key(ax, ay, cz + 1) + 1) - run_lo;
+        run_len = grid3::upper_bound(keys, (int)n, grid3::key(ax, ay, cz + 1)) - run_lo;
         s.rlo[lane] = run_lo;
     }
     __syncthreads();

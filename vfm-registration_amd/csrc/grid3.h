@@ -47,6 +47,17 @@ __device__ __forceinline__ int lower_bound(const long long* __restrict__ a, int 
     return lo;
 }
 
+// first position of the ascending a[0, n) that holds more than `key`: the end of the run of keys up to `key`.  (Not lower_bound(key + 1):
+// the key of the last cell of the last column is 2^63 - 1, and the + 1 wraps.)
+__device__ __forceinline__ int upper_bound(const long long* __restrict__ a, int n, long long key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] <= key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // sorted position i opens a run of equal keys
 __device__ __forceinline__ bool run_head(const long long* __restrict__ ks, int64_t i) { return i == 0 || ks[i - 1] != ks[i]; }
 
