@@ -58,11 +58,13 @@ const char *vfm_build_info(void);
  *                        rescan; 30 / 31 = fused fp6 half-width kernel with one (default) / two chunks per barrier; 32 / 33 = ... with two /
  *                        three (default) 32-query tiles per wave at d = 384; 40 / 41 / 42 / 43 = fp6 operand preparation by prep_chunk_kernel
  *                        (a 128-row group in registers) / prep_stream_kernel (rows read twice) / by width / prep_once_kernel (default since
- *                        round 6: one read, a tile's fp16 copy in registers); 50 / 51 = chunk-major rescan as long-lived (default) / short
+ *                        round 6: one read, a tile's fp16 copy in registers); 44 = prep_once_kernel as a persistent grid (two workgroups
+ *                        per compute unit, the next group's loads under a group's second pass: the same bytes as 43); 50 / 51 = chunk-major rescan as long-lived (default) / short
  *                        workgroups; 60 / 61 = the rescan gathers its queries from the int8 fragment tiles / the row-major int8 scan (default)
  *   "match_stats"        1: the searches collect the counters vfm_debug_match_stats reads (they cost same-address atomics)
  *   "i8_min_queries"     the gated family takes the int8 pass for more than this many query rows (default 0: always)
- *   "prep_grid"          workgroups of prep_chunk_kernel: -1 (default) one per 128-row group, 0 one per compute unit, n > 0
+ *   "prep_grid"          workgroups of prep_chunk_kernel: -1 (default) one per 128-row group, 0 one per compute unit, n > 0; of the
+ *                        persistent prep_once_kernel ("coarse_variant" 44): n > 0, otherwise two per compute unit of the stream
  *   "ransac_exact_only"  1: RANSAC scores every hypothesis in fp64 (no bounds)
  *   "ransac_fused"       2 (default): the stage as 8 launches (select state reset by the centring kernel, R* out of the moment pass, the
  *                        point-wise pass from a small grid, final + mask in one workgroup); 1: 5 launches (gather + moments in one workgroup,
@@ -185,6 +187,14 @@ int vfm_match_prepare2_gated(const float *x1, int64_t rows1, void *prepared1, co
 #define VFM_PREPARE_MX6_HALF 16
 int vfm_match_prepare2_gated_p(const float *x1, int64_t rows1, void *prepared1, const float *x2, int64_t rows2,
                                void *prepared2, int d, int schedule, vfm_stream_t stream);
+/* _prepare2_gated_p which also clears, on `stream`, the part of the search workspace `ws` (of an n x m search: ws_bytes >=
+ * vfm_match_search_workspace_bytes(n, m, d)) that vfm_match_search_coarse_gated_g would otherwise fill with zeros in front of its
+ * kernel -- exactly that part.  The coarse call that follows is then told so with VFM_RECORDS_WS_CLEAN and starts with its kernel.
+ * For a caller that prepares a pair on one stream and searches it on another: the two fills leave the one place of the cycle where
+ * nothing else can run.  Nothing may use `ws` between this call and that coarse call (no probe, no other search). */
+int vfm_match_prepare2_gated_z(const float *x1, int64_t rows1, void *prepared1, const float *x2, int64_t rows2,
+                               void *prepared2, int d, int schedule, void *ws, size_t ws_bytes, int64_t n, int64_t m,
+                               vfm_stream_t stream);
 int vfm_match_search_coarse_gated(const void *q_prepared, int64_t n, const void *b_prepared, int64_t m,
                                   int d, void *ws, size_t ws_bytes, vfm_stream_t stream);
 int vfm_match_search_finish_gated(const float *q, const void *q_prepared, int64_t n, const float *b,
@@ -273,6 +283,10 @@ int vfm_match_search_finish_gated(const float *q, const void *q_prepared, int64_
  *                     VFM_PREPARE_MX6, d = 256 / 384, more than 2048 queries and at least four queries per map chunk; elsewhere it
  *                     behaves as VFM_RECORDS_MX6. */
 #define VFM_RECORDS_MX6_FUSED 10
+/*   VFM_RECORDS_WS_CLEAN  not a kind: a flag or-ed into `records` of vfm_match_search_coarse_gated_g ONLY -- the workspace's zeroed
+ *                     region was cleared by vfm_match_prepare2_gated_z and nothing has touched the workspace since; the call issues no
+ *                     fill.  (The matching _finish call takes the kind without the flag.) */
+#define VFM_RECORDS_WS_CLEAN 0x100
 int vfm_match_search_coarse_gated_r(const void *q_prepared, int64_t n, const void *b_prepared, int64_t m,
                                     int d, void *ws, size_t ws_bytes, int records, vfm_stream_t stream);
 /* _coarse_gated_r with the gate of the search (needed by VFM_RECORDS_HALF_FUSED; ignored by the other kinds) */

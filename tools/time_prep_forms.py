@@ -15,7 +15,7 @@ p = synth.make_pair_device(n, m, d, seed=1)
 qb = torch.empty(lib.vfm_match_prepared_bytes(n, d), dtype=torch.uint8, device="cuda")
 bb = torch.empty(lib.vfm_match_prepared_bytes(m, d), dtype=torch.uint8, device="cuda")
 st = torch.cuda.current_stream().cuda_stream
-for variant in (40, 41, 43):
+for variant in (40, 41, 43, 44):
     with _lib.using(_lib.Config(coarse_variant=variant)):
         for _ in range(3):
             _lib.check(lib.vfm_match_prepare2_gated_p(p["b_desc"].data_ptr(), m, bb.data_ptr(), p["q_desc"].data_ptr(), n, qb.data_ptr(), d, 24, st))

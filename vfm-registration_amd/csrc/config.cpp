@@ -46,7 +46,7 @@ const Field k_fields[] = {
 void set_coarse_variant(VfmConfig& c, int v) {
     if (v == 60 || v == 61) { c.rescan_rows = v == 61 ? 1 : 0; return; }
     if (v == 50 || v == 51) { c.finish_short = v == 51 ? 1 : 0; return; }
-    if (v >= 40 && v <= 43) { c.prep_stream = v == 43 ? 3 : v == 42 ? 2 : v == 41 ? 1 : 0; return; }
+    if (v >= 40 && v <= 44) { c.prep_stream = v == 44 ? 4 : v == 43 ? 3 : v == 42 ? 2 : v == 41 ? 1 : 0; return; }
     if (v == 32 || v == 33) { c.mx6_ns3 = v == 33 ? 1 : 0; return; }
     if (v == 30 || v == 31) { c.mx6_t4 = v == 30 ? 1 : 0; return; }
     c.seed_units = v == 7 ? 0 : 1;

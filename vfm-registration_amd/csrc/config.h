@@ -13,13 +13,15 @@ struct VfmConfig {
     int select_variant = 0;    // "coarse_variant" 20 / 21: general select kernel / no chunk-major rescan
     int mx6_t4 = 1;            // "coarse_variant" 30 / 31: fused fp6 half-width kernel with one (default) / two chunks per barrier
     int mx6_ns3 = 1;           // "coarse_variant" 32 / 33: ... with two / three (default) query tiles per wave at d = 384
-    int prep_stream = 3;       // "coarse_variant" 40 .. 43: fp6 operand preparation by prep_chunk_kernel (0) / prep_stream_kernel (1) / by width (2) / prep_once_kernel (3, default)
+    int prep_stream = 3;       // "coarse_variant" 40 .. 44: fp6 operand preparation by prep_chunk_kernel (0) / prep_stream_kernel (1) / by width (2) / prep_once_kernel (3, default) /
+                               // prep_once_kernel as a persistent grid, the next group's loads under a group's second pass (4)
     int finish_short = 0;      // "coarse_variant" 50 / 51: chunk-major rescan as long-lived (default) / short workgroups
     int rescan_rows = 1;       // "coarse_variant" 60 / 61: rescan gathers its queries from the fragment tiles / the row-major int8 scan (default)
     int mx6_tune = 0;          // (A/B) bit 0: s_setprio 1 for waves 4 - 7 of the fp6 coarse kernel; bit 1: its ring five steps deep (headline shape)
     int match_stats = 0;       // per-query counters of a search (they cost same-address atomics)
     int i8_min_queries = 0;    // the gated family takes the int8 pass for more than this many query rows
-    int prep_grid = -1;        // workgroups of prep_chunk_kernel (-1 = one per 128-row group, 0 = one per compute unit, n > 0)
+    int prep_grid = -1;        // workgroups of prep_chunk_kernel (-1 = one per 128-row group, 0 = one per compute unit, n > 0); of the persistent
+                               // prep_once_kernel: n > 0, otherwise two per compute unit of the stream
     // ---- RANSAC (ransac.hip)
     int ransac_exact_only = 0;   // 1 = every hypothesis scored in fp64 (no bounds)
     int ransac_fused = 2;        // 2 (default since round 6) = 8 launches, 1 = the 5-launch chain (slower: its one-workgroup gather), 0 = round 5's 11

@@ -97,8 +97,10 @@ CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, 
 
 // stage 1 of a search: the MFMA coarse pass (fills ws: partials + per-query coarse maxima)
 // records (int8 pass): 0 = best score per (query, chunk), 1 = packed top-2 with the best row's index (VFM_RECORDS_*)
+// ws_clean: the caller states that the region the two fills below cover is zero already (VFM_RECORDS_WS_CLEAN: cleared by
+// vfm_match_prepare2_gated_z, nothing has used the workspace since) -- no fill is issued
 int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, hipStream_t st,
-                     bool bias_from_map_inv, bool inner_product, bool gated, int records, float gate) {
+                     bool bias_from_map_inv, bool inner_product, bool gated, int records, float gate, bool ws_clean) {
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
@@ -119,7 +121,7 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
             a.nslices = choose_slices(a.nqb, a.nchunks - a.seed_parts * a.seed_chunks);
         }
     }
-    VFM_CHECK_HIP(hipMemsetAsync(w.fb_count, 0, search_zero_bytes(n, m), st));  // fb_count | qmax | rec_cnt | bin_cnt
+    if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.fb_count, 0, search_zero_bytes(n, m), st));  // fb_count | qmax | rec_cnt | bin_cnt
     if (i8) {
         if (!gated) records = VFM_RECORDS_TOP2;  // no feedback loop behind an ungated call: the robust record kind
         records = effective_records(records, d, n, m);
@@ -137,7 +139,7 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
             a.cap = w.cap;
             a.survivors = w.fb_count + 5;
             a.surv = reinterpret_cast<unsigned*>(w.partials);   // the fp6 form: one slot per workgroup in the record buffer it does not write
-            VFM_CHECK_HIP(hipMemsetAsync(w.cand_cnt, 0, (size_t)a.npad * sizeof(int), st));  // lengths of the queries' own lists
+            if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.cand_cnt, 0, (size_t)a.npad * sizeof(int), st));  // lengths of the queries' own lists
         }
         const bool half = records == VFM_RECORDS_HALF || records == VFM_RECORDS_HALF_FUSED;   // the image of the first d / 2 columns
         a.Qh = half ? Q.tiles8h : Q.tiles8;
@@ -206,6 +208,24 @@ VFM_EXPORT int vfm_match_prepare2_gated_p(const float* x1, int64_t rows1, void* 
                   "prepare2: unknown schedule %d", schedule);
     const bool want_f16 = !use_i8(d, rows2, rows1, true);
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule);
+}
+
+// ... which also clears, on `stream`, what a coarse pass of n queries in m map rows wants zero in the search workspace `ws` -- the
+// region vfm_match_search_coarse_gated_g fills in front of its kernel, and not a byte more --, so that the coarse call can be told
+// VFM_RECORDS_WS_CLEAN and starts with its kernel.  Inside the preparation kernel where that is prep_once_kernel (no extra launch),
+// by a small kernel behind the other forms.
+VFM_EXPORT int vfm_match_prepare2_gated_z(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2,
+                                          void* prepared2, int d, int schedule, void* ws, size_t ws_bytes, int64_t n, int64_t m,
+                                          vfm_stream_t stream) {
+    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
+    VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2 && ws, "prepare2: null pointer");
+    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) >= VFM_PREPARE_DEFAULT &&
+                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) <= VFM_PREPARE_INTERLEAVED,
+                  "prepare2: unknown schedule %d", schedule);
+    VFM_CHECK_ARG(n > 0 && m > 0 && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "prepare2: bad search size (n=%lld m=%lld)", (long long)n, (long long)m);
+    if (ws_bytes < carve_search(nullptr, n, m).bytes) return vfm_fail(VFM_EWORKSPACE, "prepare2: search workspace too small");
+    const bool want_f16 = !use_i8(d, rows2, rows1, true);
+    return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule, prep_zero(ws, n, m));
 }
 
 // the gated pair with the rows' storage type stated (VFM_ROWS_F32 / VFM_ROWS_F16): fp16 rows are widened to fp32 element by element as
@@ -278,9 +298,11 @@ VFM_EXPORT int vfm_match_search_coarse_gated_g(const void* q_prepared, int64_t n
                                                void* ws, size_t ws_bytes, int records, float gate, vfm_stream_t stream) {
     if (int rc = check_search_args(n, m, d, ws_bytes)) return rc;
     VFM_CHECK_ARG(q_prepared && b_prepared && ws, "search_coarse: null pointer");
+    const bool ws_clean = (records & VFM_RECORDS_WS_CLEAN) != 0;   // (a flag beside the kind, not a kind)
+    records &= ~VFM_RECORDS_WS_CLEAN;
     VFM_CHECK_ARG(records >= VFM_RECORDS_BEST && records <= VFM_RECORDS_MX6_FUSED, "search_coarse: unknown record kind %d", records);
     VFM_CHECK_ARG(gate == gate, "search_coarse: gate is NaN");
-    return do_search_coarse(q_prepared, n, b_prepared, m, d, ws, (hipStream_t)stream, false, true, true, records, gate);
+    return do_search_coarse(q_prepared, n, b_prepared, m, d, ws, (hipStream_t)stream, false, true, true, records, gate, ws_clean);
 }
 
 VFM_EXPORT int vfm_match_search_finish_gated(const float* q, const void* q_prepared, int64_t n, const float* b,

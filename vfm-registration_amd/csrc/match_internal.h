@@ -598,8 +598,25 @@ inline I8Bounds mx6_bounds_half(const Prepared& Q, const Prepared& B) { return I
 CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m, int qblock = QBLOCK);
 
 // match_prep.hip
+// What do_search_coarse clears in front of a coarse pass, as two ranges of whole 16-byte units: a preparation that runs just before on
+// another stream can clear them on its way (vfm_match_prepare2_gated_z) and the coarse call be told so (VFM_RECORDS_WS_CLEAN).
+struct PrepZero {
+    uint4* a = nullptr;   // [fb_count, fb_count + search_zero_bytes)
+    size_t na = 0;
+    uint4* b = nullptr;   // cand_cnt[0 .. npad)
+    size_t nb = 0;
+};
+inline PrepZero prep_zero(void* ws, int64_t n, int64_t m) {
+    const SearchWs w = carve_search(ws, n, m);
+    PrepZero z;
+    z.a = reinterpret_cast<uint4*>(w.fb_count);
+    z.na = search_zero_bytes(n, m) / 16;               // (256 + multiples of npad = 256 k bytes)
+    z.b = reinterpret_cast<uint4*>(w.cand_cnt);
+    z.nb = (size_t)rows_padded(n) * sizeof(int) / 16;
+    return z;
+}
 int do_prepare2(Rows x1, int64_t rows1, void* prepared1, Rows x2, int64_t rows2, void* prepared2, int d,
-                hipStream_t st, bool want_f16 = true, int grid_mode = 0 /* VFM_PREPARE_DEFAULT */);
+                hipStream_t st, bool want_f16 = true, int grid_mode = 0 /* VFM_PREPARE_DEFAULT */, PrepZero zero = PrepZero{});
 int do_prepare(const float* x, int64_t rows, int d, void* prepared, hipStream_t st);
 // int8 image alone of ONE operand whose row r is x[perm[r]] (perm == NULL: identity) -- the Euclidean search prepares its map
 // sorted by norm and the queries of its reverse direction gathered by the forward result
@@ -612,7 +629,7 @@ int mx6_survivor_slot_words();   // words per workgroup slot of the fused half-w
 // match_api.hip
 int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, hipStream_t st,
                      bool bias_from_map_inv = false, bool inner_product = false, bool gated = false, int records = 0,
-                     float gate = -__builtin_inff());
+                     float gate = -__builtin_inff(), bool ws_clean = false);
 // match_finish.hip
 int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* bprep, int64_t m, int d,
                      int64_t* idx_out, float* sim_out, void* ws, hipStream_t st, bool gated = false,

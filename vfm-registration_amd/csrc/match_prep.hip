@@ -833,13 +833,23 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
 // the odd row's, moved there by v_permlane32_swap), 96 in all -- beside a batch of 8 rows in flight; nothing is read twice and no
 // group lives in the LDS (prep_chunk_kernel: 8 waves x 200 registers + 150 KB, one workgroup per compute unit, 0.185 ms alone).
 // Definition of THIS form's int8 image (it is not byte-identical to the other two forms'): with h = fp16(v), v the fp32-normalised
-// element, q = clamp(rint(h * 127 / amax)), amax the group's largest |v| in fp32 as before; E = |h - s q|_2 + |v - h|_2, both terms
-// MEASURED (the second in pass 1, where v and h are both at hand; ~1.4e-4 beside ~1e-2), each rounded up.  The fp6 image, err6 / err6h,
-// 1 / |row|, rest / grest and every group datum are the other forms', bit for bit (same arithmetic on the same values).
+// element, q = rint(h * 127 / amax) (within [-127, 127] by itself, see quant_chunk), amax the group's largest |v| in fp32 as before;
+// E = |h - s q|_2 + |v - h|_2: the first term MEASURED and rounded up, the second BOUNDED by the constant PREP_F16_ROUNDING (the fp16
+// rounding of a unit row: ~1.4e-4 measured beside ~1e-2, 4.9e-4 as the bound).  The fp6 image, err6 / err6h, 1 / |row|, rest / grest and
+// every group datum are the other forms', bit for bit (same arithmetic on the same values).
+//
+// PERSIST (coarse_variant 44): the same kernel as a grid of at most two workgroups per compute unit, each walking the groups blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the concatenated (map, scan) list -- static striding, no workgroup ever waits for another.  What it
+// buys is in the loop's middle: once pass 1 has consumed the last batch, v0 / vp (48 registers) hold nothing, and the NEXT group's
+// first batch is requested into them before pass 2 starts, so the loads that a fresh workgroup would start from cold are in flight
+// under the quantisation and the stores.  Within a group the arithmetic, its order and every byte written are the one-group form's.
+//
+// z: ranges of a search workspace this launch clears for the coarse pass that follows (vfm_match_prepare2_gated_z), 16 bytes per lane,
+// spread over the grid; none (z.na == z.nb == 0) for every other caller.
 // ---------------------------------------------------------------------------------------------
-template <int D, bool HALF>
+template <int D, bool HALF, bool PERSIST>
 __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restrict__ x1, int64_t rows1, PrepOut o1, int groups1,
-                                                           const float* __restrict__ x2, int64_t rows2, PrepOut o2, int groups) {
+                                                           const float* __restrict__ x2, int64_t rows2, PrepOut o2, int groups, PrepZero z) {
     constexpr bool PAIR = D > 256;               // d = 384: a row is one chunk per lane + half a chunk -- the second chunks of TWO rows share a register
     constexpr int NU = D >> 4;                   // 16-byte int8 units per row
     constexpr int NBLK = D >> 5;                 // 32-column blocks per row
@@ -852,20 +862,15 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     __shared__ float l_e6[NBLK][I8_GROUP];
     __shared__ unsigned char l_sc[I8_GROUP][16];
     __shared__ unsigned amax_bits, emax_bits, rmax_bits, e6max_bits, e6hmax_bits;
-    const int wave = threadIdx.x >> 6, lane = lane_id();
-    const bool lo = lane < 32;
-    const int gidx = blockIdx.x;
-    const bool second = gidx >= groups1;
-    const int grp = second ? gidx - groups1 : gidx;
-    const float* x = second ? x2 : x1;
-    const int64_t rows = second ? rows2 : rows1;
-    const PrepOut& o = second ? o2 : o1;
-    if (threadIdx.x == 0) {
-        amax_bits = 0u;
-        emax_bits = 0u;
-        rmax_bits = 0u;
-        e6max_bits = 0u;
-        e6hmax_bits = 0u;
+    const int wave0 = threadIdx.x >> 6, lane0 = lane_id();
+    if (z.na + z.nb) {   // (stores only: nothing below waits for them)
+        const size_t nz = z.na + z.nb;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nz; i += (size_t)gridDim.x * 256)
+            *(i < z.na ? z.a + i : z.b + (i - z.na)) = make_uint4(0u, 0u, 0u, 0u);
+    }
+    int gidx = blockIdx.x;
+    if constexpr (PERSIST) {
+        if (gidx >= groups) return;
     }
     // a batch of 8 rows in flight: v0[j] = the lane's first chunk (columns 4 lane ..) of row j; vp[jp] (d = 384) = the second chunk --
     // columns 256 + 4 (lane & 31) .. -- of row 2 jp (lanes 0 - 31) and of row 2 jp + 1 (lanes 32 - 63): every lane of every load, every
@@ -873,11 +878,10 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     // through a quarter of the kernel's VALU work)
     float4 v0[8];
     float4 vp[PAIR ? 4 : 1];
-    const int64_t row0 = (int64_t)grp * I8_GROUP + wave * 32;   // first row of the wave's tile
-    auto load4 = [&](int64_t r, int c) __attribute__((always_inline)) {
+    auto load4 = [&](const float* x, int64_t rows, int64_t r, int c) __attribute__((always_inline)) {
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
 #ifdef VFM_POABL_NOLOAD   // (timing experiments, tools/build_ablate_prep.sh: results are garbage)
-        if (r < rows) t = make_float4(1.0f + (float)c, 2.0f - (float)(r & 7), 0.5f * (float)lane, 3.0f);
+        if (r < rows) t = make_float4(1.0f + (float)c, 2.0f - (float)(r & 7), 0.5f * (float)lane0, 3.0f);
 #else
         if (r < rows) {
             const float* pc = x + r * (int64_t)D + 4 * c;
@@ -889,8 +893,31 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
 #endif
         return t;
     };
-    auto load_row = [&](int b, int j) __attribute__((always_inline)) { v0[j] = load4(row0 + 8 * b + j, lane); };
-    auto load_pair = [&](int b, int jp) __attribute__((always_inline)) { vp[jp] = load4(row0 + 8 * b + 2 * jp + (lane >> 5), 64 + (lane & 31)); };
+    // the first batch of group g of the concatenated list (the wave's rows 0 .. 7 of it)
+    auto load_first = [&](int g) __attribute__((always_inline)) {
+        const bool sec = g >= groups1;
+        const float* xg = sec ? x2 : x1;
+        const int64_t rg = sec ? rows2 : rows1;
+        const int64_t r0 = (int64_t)(sec ? g - groups1 : g) * I8_GROUP + wave0 * 32;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v0[j] = load4(xg, rg, r0 + j, lane0);
+        if constexpr (PAIR) {
+#pragma unroll
+            for (int jp = 0; jp < 4; ++jp) vp[jp] = load4(xg, rg, r0 + 2 * jp + (lane0 >> 5), 64 + (lane0 & 31));
+        }
+    };
+    load_first(gidx);
+    for (;;) {   // (PERSIST: the workgroup's groups; otherwise once.  The body keeps the kernel's indentation.)
+    // (PERSIST: the thread's coordinates as values of THIS iteration -- as loop invariants, every address and lane pattern of both
+    // passes that derives from them was computed in front of the loop and kept in registers through it: + 87 registers at d = 256,
+    // 41 spilled at d = 384)
+    int tid = threadIdx.x, lane = lane0;
+    if constexpr (PERSIST) {
+        asm volatile("" : "+v"(tid));
+        lane = tid & 63;
+    }
+    const int wave = tid >> 6;
+    const bool lo = lane < 32;
     auto scatter8 = [&](const float* p) __attribute__((always_inline)) {   // (prep_chunk_kernel's: lane l ends with row l >> 3)
         const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
         float q4[4], q2[2];
@@ -913,9 +940,6 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
         return __uint_as_float((unsigned)sw[1]);
     };
-    // the wave's 32 normalised rows as packed halves: hs0[row] = the lane's first chunk; hs1[pair] (d = 384) = the pair's second chunks
-    uint2 hs0[32];
-    uint2 hs1[PAIR ? 16 : 1];
     auto pack4 = [&](const float (&nv)[4]) __attribute__((always_inline)) {
         // (the fp32 product is rounded to fp16 as a value of its own -- see prep_stream_kernel: hidden from the compiler, which otherwise
         // fuses product and conversion into one v_fma_mixlo_f16, a single rounding)
@@ -950,13 +974,28 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         q = t.w * t.w; p = p + q;
         return p;
     };
-    // ---- pass 1: 1 / |row| (oracle order), the group's largest normalised magnitude, |second half|, the fp16 copy
-#pragma unroll
-    for (int j = 0; j < 8; ++j) load_row(0, j);
-    if constexpr (PAIR) {
-#pragma unroll
-        for (int jp = 0; jp < 4; ++jp) load_pair(0, jp);
+    const bool second = gidx >= groups1;
+    const int grp = second ? gidx - groups1 : gidx;
+    const float* x = second ? x2 : x1;
+    const int64_t rows = second ? rows2 : rows1;
+    const PrepOut& o = second ? o2 : o1;
+    const int64_t row0 = (int64_t)grp * I8_GROUP + wave * 32;   // first row of the wave's tile
+    auto load_row = [&](int b, int j) __attribute__((always_inline)) { v0[j] = load4(x, rows, row0 + 8 * b + j, lane); };
+    auto load_pair = [&](int b, int jp) __attribute__((always_inline)) { vp[jp] = load4(x, rows, row0 + 8 * b + 2 * jp + (lane >> 5), 64 + (lane & 31)); };
+    // (thread 0 was the last to read the previous group's maxima, behind that group's last barrier; everyone else meets them again
+    // behind the barrier below)
+    if (tid == 0) {
+        amax_bits = 0u;
+        emax_bits = 0u;
+        rmax_bits = 0u;
+        e6max_bits = 0u;
+        e6hmax_bits = 0u;
     }
+    // the wave's 32 normalised rows as packed halves: hs0[row] = the lane's first chunk; hs1[pair] (d = 384) = the pair's second chunks
+    uint2 hs0[32];
+    uint2 hs1[PAIR ? 16 : 1];
+    // ---- pass 1: 1 / |row| (oracle order), the group's largest normalised magnitude, |second half|, the fp16 copy (its first batch is
+    // in v0 / vp: requested above, or under the previous group's pass 2)
     __syncthreads();   // the maxima are initialised (pass 1 already adds to rmax_bits)
     float lmax = 0.0f;
 #pragma unroll
@@ -1031,6 +1070,11 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     const bool usable = amax > 0.0f && amax < 3.0e38f;
     const float qstep = usable ? amax / 127.0f : 1.0f;
     const float inv_qstep = usable ? 127.0f / amax : 0.0f;
+    const int next = gidx + (int)gridDim.x;
+    if constexpr (PERSIST) {
+        // v0 / vp are free from here to the top of the loop: the next group's first batch travels under this group's pass 2
+        if (next < groups) load_first(next);
+    }
     // ---- pass 2: from the registers
     unsigned char* my8 = l_i8[wave];
     unsigned char* my16 = l_h16[wave];
@@ -1172,7 +1216,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     }
     __syncthreads();
     {   // the d / 64 scales of MFMA lane (hh, p) of tile t: its 8 bytes of the scale plane
-        const int r = threadIdx.x & (I8_GROUP - 1), hh = threadIdx.x >> 7;
+        const int r = tid & (I8_GROUP - 1), hh = tid >> 7;
         unsigned lo4 = 0u, hi4 = 0u;
         for (int s6 = 0; s6 < (nconv >> 1); ++s6) {
             const unsigned bsc = l_sc[r][2 * s6 + hh];
@@ -1182,8 +1226,8 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         unsigned char* t6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + (r >> 5)) * (size_t)tb6;
         *reinterpret_cast<uint2*>(t6 + mx6_scale_at(D >> 6, 0, hh * 32 + (r & 31))) = make_uint2(lo4, hi4);
     }
-    if (threadIdx.x < I8_GROUP) {   // E of the fp6 image per row: blocks in order; rounded up like the int8 one
-        const int r = threadIdx.x;
+    if (tid < I8_GROUP) {   // E of the fp6 image per row: blocks in order; rounded up like the int8 one
+        const int r = tid;
         float acc = 0.0f, acch = 0.0f;
         for (int blk = 0; blk < nconv; ++blk) {
             acc = acc + l_e6[blk][r];
@@ -1201,13 +1245,22 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         if (e6h > 0.0f) atomicMax(&e6hmax_bits, __float_as_uint(e6h));
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
         o.gstep[grp] = qstep;
         o.gerr[grp] = __uint_as_float(emax_bits);
         o.grest[grp] = __uint_as_float(rmax_bits);
         o.gerr6[grp] = __uint_as_float(e6max_bits);
         o.gerr6h[grp] = __uint_as_float(e6hmax_bits);
         o.gstep6[grp] = MX6_FIX_STEP;
+    }
+    if constexpr (!PERSIST) {
+        break;
+    } else {
+        // (the scales and E of this group were read from l_sc / l_e6 before the barrier above, and the next group writes them only
+        // behind three more: no barrier of its own is needed here)
+        if (next >= groups) break;
+        gidx = next;
+    }
     }
 }
 
@@ -1359,6 +1412,14 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x,
     }
 }
 
+// The ranges of PrepZero by a launch of their own: for the preparation forms that do not clear them on the way (every form but
+// prep_once_kernel's two).
+__global__ __launch_bounds__(256) void prep_zero_kernel(PrepZero z) {
+    const size_t nz = z.na + z.nb;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nz; i += (size_t)gridDim.x * 256)
+        *(i < z.na ? z.a + i : z.b + (i - z.na)) = make_uint4(0u, 0u, 0u, 0u);
+}
+
 }  // namespace
 
 inline PrepOut prep_out(const Prepared& p, const int* perm = nullptr, int mx6_half = 0) {
@@ -1384,10 +1445,49 @@ inline int prep_grid(int groups, int mode) {
     return g < groups ? g : groups;
 }
 
+// Workgroups of the persistent one-read form (prep_once_kernel<., ., true>): two per compute unit the stream may use -- what the
+// kernel's registers and LDS admit (__launch_bounds__(256, 2); 2 x 33 KB) --, or vfm_debug_set_prep_grid's n > 0.  The stream's
+// mask is asked for once per (thread, stream): a stale answer costs a badly sized grid, never a wrong result (static striding).
+inline int prep_persist_grid(int groups, hipStream_t st) {
+    static thread_local hipStream_t last_st = nullptr;
+    static thread_local int last_cus = 0;
+    const int knob = vfm_cfg().prep_grid;
+    int g = knob;
+    if (knob <= 0) {
+        if (!last_cus || last_st != st) {
+            int cus = 0, dev = 0;
+            (void)hipGetDevice(&dev);
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+            uint32_t mask[16] = {0};
+            if (hipExtStreamGetCUMask(st, 16, mask) == hipSuccess) {
+                int bits = 0;
+                for (int i = 0; i < 16; ++i) bits += __builtin_popcount(mask[i]);
+                if (bits > 0 && bits < cus) cus = bits;
+            } else {
+                (void)hipGetLastError();
+            }
+            last_st = st;
+            last_cus = cus;
+        }
+        g = 2 * last_cus;
+    }
+    return g < groups ? g : groups;
+}
+
 // one or two operands (x2 may be NULL) in one launch.  want_f16 = false: only the int8 image (d = 256, 384), for operands that
 // will meet in an int8 search (use_i8): a third of the bytes written, a third of the LDS.
+// zero: ranges of a search workspace to clear on `st` with the preparation (none by default) -- inside the preparation kernel where
+// that is prep_once_kernel, by prep_zero_kernel behind the others.
 int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows2, void* prepared2, int d,
-                hipStream_t st, bool want_f16, int grid_mode) {
+                hipStream_t st, bool want_f16, int grid_mode, PrepZero zero) {
+    bool zero_pending = zero.na + zero.nb != 0;   // (cleared where the preparation kernel takes the ranges along)
+    auto zero_behind = [&]() {
+        if (!zero_pending) return VFM_OK;
+        const size_t nz = zero.na + zero.nb;
+        hipLaunchKernelGGL(prep_zero_kernel, dim3((unsigned)((nz + 255) / 256 < 1024 ? (nz + 255) / 256 : 1024)), dim3(256), 0, st, zero);
+        VFM_CHECK_LAUNCH("prep_zero_kernel");
+        return VFM_OK;
+    };
     // fp16 rows (VFM_ROWS_F16): the kernels that widen on load are prep_chunk_kernel and prep_mx6_rows_kernel -- the int8 and fp6
     // images of the gated family; the fp16-tile image (ungated fp16 pass) and the streamed fp6 form read fp32 rows only
     const bool any_f16 = x1r.f16 || (x2r.p && x2r.f16);
@@ -1421,20 +1521,29 @@ int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows
         int pg = prep_grid(groups, grid_mode);
         const dim3 grid((unsigned)pg), block(1024);
         if (want_mx6) {   // int8 + fp6 images from one read of the rows; the fp16 image, if wanted, by its own kernel
-            // Which form: prep_stream_kernel was built to run BESIDE a coarse workgroup of round 4 (332 of a SIMD's 512 registers, 90 KiB).
-            // Since round 5 the d = 384 coarse kernel holds three query tiles per wave (444 registers) and the full-width ones fill the
-            // LDS: nothing runs beside them, and in a LONG pipeline the one-pass form below (rows in registers: 0.185 ms alone against
-            // 0.139, but short fat workgroups that leave the coarse kernel alone) is the better neighbour -- tools/ab_prep_r5.py, 200-step
-            // pipelines on one box: headline + 1.7 %, full width with the fused epilogue + 3.5 %, lifted descriptors + 2.2 %, full width
-            // with records - 0.5 %.  In the driver's 20-step form it LOSES 2.9 % (tools/ab_prep_r5_20.py: 1624 against 1672
-            // registrations/s): the default stays the stream form; vfm_debug_set_coarse_variant(42) selects by width (d = 384: one pass).
+            // Which form (vfm_cfg().prep_stream, "coarse_variant" 40 .. 44).  Default since round 6: prep_once_kernel (3) -- one read of the
+            // rows, the fp16 copy of a wave's tile in registers, two short workgroups per compute unit; 4 is the same kernel as a persistent
+            // grid with the next group's loads under a group's second pass.  Both take d = 256 / 384 in fp32 rows; everything else -- and
+            // the older forms when asked for -- goes on as before: prep_stream_kernel (1; 2 = at d = 256 only) was built to run BESIDE a
+            // coarse workgroup of round 4 (332 of a SIMD's 512 registers, 90 KiB) and reads every row twice; prep_chunk_kernel (0) holds
+            // a group in the registers of 8 fat waves, one workgroup per compute unit.  Since round 5 nothing runs beside a d = 384 coarse
+            // workgroup (444 registers per SIMD), so a preparation form is judged by its own work: tools/ab_prep_r5.py, ab_prep_r6.py,
+            // DESIGN.md R6.2 and the section on the persistent form.
             const bool stream_form = vfm_cfg().prep_stream == 1 || (vfm_cfg().prep_stream == 2 && d == 256);
-            if (vfm_cfg().prep_stream == 3 && (d == 384 || d == 256) && !any_f16) {   // one read of the rows, the fp16 copy of a tile in registers (prep_once_kernel, round 6)
-                const dim3 sg((unsigned)groups), sb(256);
-                if (d == 384 && h6) hipLaunchKernelGGL((prep_once_kernel<384, true>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else if (d == 384) hipLaunchKernelGGL((prep_once_kernel<384, false>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else if (h6) hipLaunchKernelGGL((prep_once_kernel<256, true>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else hipLaunchKernelGGL((prep_once_kernel<256, false>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
+            if ((vfm_cfg().prep_stream == 3 || vfm_cfg().prep_stream == 4) && (d == 384 || d == 256) && !any_f16) {
+                const bool persist = vfm_cfg().prep_stream == 4;
+                const dim3 sg((unsigned)(persist ? prep_persist_grid(groups, st) : groups)), sb(256);
+                const PrepOut po1 = prep_out(p1, nullptr, h6), po2 = prep_out(p2, nullptr, h6);
+#define VFM_PREP_ONCE(D_, H_, P_) hipLaunchKernelGGL((prep_once_kernel<D_, H_, P_>), sg, sb, 0, st, x1, rows1, po1, g1, x2, rows2, po2, groups, zero)
+                if (d == 384) {
+                    if (h6) { if (persist) VFM_PREP_ONCE(384, true, true); else VFM_PREP_ONCE(384, true, false); }
+                    else    { if (persist) VFM_PREP_ONCE(384, false, true); else VFM_PREP_ONCE(384, false, false); }
+                } else {
+                    if (h6) { if (persist) VFM_PREP_ONCE(256, true, true); else VFM_PREP_ONCE(256, true, false); }
+                    else    { if (persist) VFM_PREP_ONCE(256, false, true); else VFM_PREP_ONCE(256, false, false); }
+                }
+#undef VFM_PREP_ONCE
+                zero_pending = false;
             } else
             if (stream_form && (d == 384 || d == 256) && !any_f16) {   // the form that fits beside a coarse workgroup (prep_stream_kernel)
                 const dim3 sg((unsigned)groups), sb(256);
@@ -1476,12 +1585,12 @@ int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows
                                prep_out(p2, nullptr, h6), groups);
             VFM_CHECK_LAUNCH("prep_mx6_rows_kernel");
         }
-        return VFM_OK;
+        return zero_behind();
     }
     hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)(t1 + t2)), dim3(256), (size_t)d * 64, st, x1, rows1, d, p1.inv, p1.tiles,
                        t1, x2, rows2, p2.inv, p2.tiles);
     VFM_CHECK_LAUNCH("prep_rows_kernel");
-    return VFM_OK;
+    return zero_behind();
 }
 
 int do_prepare(const float* x, int64_t rows, int d, void* prepared, hipStream_t st) {

@@ -47,6 +47,7 @@ SIGNATURES = {
     "vfm_match_prepare2": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_int, c_vp]),
     "vfm_match_prepare2_gated": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_int, c_vp]),
     "vfm_match_prepare2_gated_p": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_int, C.c_int, c_vp]),
+    "vfm_match_prepare2_gated_z": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_int, C.c_int, c_vp, C.c_size_t, c_i64, c_i64, c_vp]),
     "vfm_match_prepare2_gated_t": (C.c_int, [c_vp, C.c_int, c_i64, c_vp, c_vp, C.c_int, c_i64, c_vp, C.c_int, C.c_int, c_vp]),
     "vfm_match_search_finish_gated_t": (C.c_int, [c_vp, C.c_int, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp,
                                                   C.c_size_t, C.c_float, C.c_int, c_vp]),

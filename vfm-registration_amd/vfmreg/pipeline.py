@@ -236,6 +236,10 @@ class RegistrationPipeline:
         self.prep_stream = (shared_prep if shared_prep is not None else torch.cuda.Stream(device=dev)) if self.overlap else None
         self._step = 0
         self._prep_schedule = prep_schedule   # None: the rule in register(); 1 / 2 = VFM_PREPARE_PERSISTENT / _INTERLEAVED (A/B runs)
+        # the preparation of a pair clears what its coarse pass wants zero in the set's search workspace (vfm_match_prepare2_gated_z) and
+        # the coarse call is told so (VFM_RECORDS_WS_CLEAN): no fill between "preparation finished" and "coarse kernel starts", the one
+        # place of the cycle where nothing else can run.  False: the coarse call fills for itself, as before (A/B runs)
+        self._ws_clean = True
 
     def prepare_map(self, b_desc: torch.Tensor) -> None:
         """IndexFlatIP.add: normalise + convert the map once (it is immutable per scene); every buffer
@@ -433,6 +437,9 @@ class RegistrationPipeline:
             if r.done is not None:
                 self.prep_stream.wait_event(r.done)     # the solve stage that last read this set has finished
             pst = self.prep_stream.cuda_stream
+        # the half-width probe runs its own coarse pass in r.sws between this pair's preparation and its coarse call
+        probe = bool(i8 and self._probe_due and not self.half and len(self._pending) < 8)
+        ws_clean = 0   # VFM_RECORDS_WS_CLEAN once this pair's preparation has cleared r.sws for its coarse call
         if not (reuse_map and r.map_key == b_desc.data_ptr()):
             # (a map that will be reused keeps both images: the coarse pass may change between registrations)
             if i8 and not reuse_map:
@@ -452,6 +459,12 @@ class RegistrationPipeline:
                 if f16q or f16b:
                     _lib.check(lib.vfm_match_prepare2_gated_t(b_desc.data_ptr(), int(f16b), self.m, r.bprep.data_ptr(), q_desc.data_ptr(), int(f16q),
                                                               self.n, r.qprep.data_ptr(), self.d, schedule, pst), "prepare(map + scan)")
+                elif self._ws_clean and not probe:
+                    # (ordering: `pst` has waited for r.done -- the last reader of r.sws -- and the coarse call's stream waits for `pst`)
+                    _lib.check(lib.vfm_match_prepare2_gated_z(b_desc.data_ptr(), self.m, r.bprep.data_ptr(), q_desc.data_ptr(), self.n,
+                                                              r.qprep.data_ptr(), self.d, schedule, r.sws.data_ptr(), r.sws.numel(),
+                                                              self.n, self.m, pst), "prepare(map + scan)")
+                    ws_clean = 0x100
                 else:
                     _lib.check(lib.vfm_match_prepare2_gated_p(b_desc.data_ptr(), self.m, r.bprep.data_ptr(), q_desc.data_ptr(), self.n,
                                                               r.qprep.data_ptr(), self.d, schedule, pst), "prepare(map + scan)")
@@ -464,7 +477,7 @@ class RegistrationPipeline:
         if self.overlap and pst != st:
             main.wait_stream(self.prep_stream)
         gate = float(np.nextafter(np.float32(self.min_cosine), np.float32(-np.inf))) if self.gate else float("-inf")
-        if i8 and self._probe_due and not self.half and len(self._pending) < 8:
+        if probe:
             self._probe_due = False
             slot = self._slots.pop() if self._slots else torch.zeros(1, dtype=torch.int32).pin_memory()
             _lib.check(lib.vfm_match_search_probe_half(r.qprep.data_ptr(), self.n, r.bprep.data_ptr(), self.m, self.d, r.sws.data_ptr(),
@@ -474,7 +487,7 @@ class RegistrationPipeline:
             self._pending.append((ev, slot, "probe"))
         if i8:
             _lib.check(lib.vfm_match_search_coarse_gated_g(r.qprep.data_ptr(), self.n, r.bprep.data_ptr(), self.m, self.d,
-                                                           r.sws.data_ptr(), r.sws.numel(), records, gate, st), "search(coarse)")
+                                                           r.sws.data_ptr(), r.sws.numel(), records | ws_clean, gate, st), "search(coarse)")
         else:
             # (VFM_RECORDS_F16 = 2: the fp16 pass explicitly -- the ungated calls route large searches to the int8 pass)
             _lib.check(lib.vfm_match_search_coarse_gated_r(r.qprep.data_ptr(), self.n, r.bprep.data_ptr(), self.m, self.d,
