@@ -586,12 +586,12 @@ int vfm_fpfh_spfh(const double *pts, const double *normals, int64_t n, const int
 int vfm_fpfh_fpfh(const double *spfh, int64_t n, const int32_t *nbr_idx, const double *nbr_d2, const int32_t *nbr_cnt,
                   int32_t max_nn, double *fpfh_out, vfm_stream_t stream);
 
-/* ------------------------------------------------------------------ exact 1-NN in 3-D (row recovery of the baselines) */
+/* ------------------------------------------------------------------ exact 1-NN and k-NN in 3-D (row recovery of the baselines, map filter) */
 
 /* sklearn.neighbors.KDTree(X, metric="euclidean").query(Q, k=1) of src/vfm-reg/src/registration_node.py:295-298: the row of the
  * nearest point of a cloud for every query, over ALL n points (no radius), exact wherever the query lies.  Points and queries are
  * rows of 3 fp64 with finite coordinates; d2 = (dx*dx + dy*dy) + dz*dz in fp64 without contraction, dist = sqrt(d2), equal d2 to
- * the lower index (a convention of this library).  An empty cloud has no nearest point: n == 0 is VFM_EINVAL in all three.
+ * the lower index (a convention of this library).  An empty cloud has no nearest point: n == 0 is VFM_EINVAL in all four.
  * Nothing here synchronises `stream` or keeps state between calls.
  * vfm_nn3_workspace_bytes: the workspace of vfm_nn3_build for n points. */
 size_t vfm_nn3_workspace_bytes(int64_t n);
@@ -606,6 +606,17 @@ int vfm_nn3_build(const double *pts, int64_t n, double cell, int64_t *keys_out, 
  * nq == 0 writes nothing but that count. */
 int vfm_nn3_query(const int64_t *keys, const int32_t *order, const double *sorted, int64_t n, double cell, const double *queries,
                   int64_t nq, int64_t *idx_out, double *dist_out, int32_t *fallback_count_out, vfm_stream_t stream);
+/* The k nearest points (1 <= k <= 64: the list is an entry per lane of a wave) of every query, on the same structure: what
+ * faiss.IndexFlatL2.search(X, k) answers in vfm_reg/utils.py:19-44.  Row q of idx_out (int64[nq k]) / d2_out (fp64[nq k]) is
+ * ascending in (d2, index) -- equal d2 to the lower index --; d2_out holds SQUARED distances (faiss returns squares, sklearn roots:
+ * the caller takes the root).  max_d2 is an inclusive cap: only points with d2 <= max_d2 are returned (+inf: no cap; a NaN or a
+ * negative cap is VFM_EINVAL), and a search with a cap ends as soon as the searched cube holds every such point.  count_out
+ * (int32[nq]): the valid entries of the row (fewer than k with n < k, under a cap, or for a query with a NaN coordinate: 0); the
+ * rest of the row is padded with index -1 and d2 +inf.  A point with a NaN coordinate is never returned.  fallback_count_out as in
+ * vfm_nn3_query; nq == 0 writes nothing but that count.  No workspace. */
+int vfm_nn3_knn(const int64_t *keys, const int32_t *order, const double *sorted, int64_t n, double cell, const double *queries,
+                int64_t nq, int k, double max_d2, int64_t *idx_out, double *d2_out, int32_t *count_out,
+                int32_t *fallback_count_out, vfm_stream_t stream);
 
 /* ------------------------------------------------------------------ DINOv2 ViT-S/14 (row A1) */
 

@@ -6,8 +6,8 @@ neighbour search in 3-D on the GPU (csrc/nn3.hip).
 
 numpy in, numpy out; device tensors (N x 3 fp64 on the ROCm device) are taken and returned as such.  Distances are
 ``sqrt((dx*dx + dy*dy) + dz*dz)`` in fp64 -- bit-equal to sklearn's on the inputs tests/test_nn3_oracle.py compares --; among points at
-the same distance the lowest row wins (sklearn leaves that unspecified).  Other metrics, ``k != 1``, other widths than 3:
-NotImplementedError.
+the same distance the lowest row wins (sklearn leaves that unspecified).  ``query`` answers k = 1; the k nearest (k <= 64) are
+``query_knn`` (csrc/nn3.hip, ``nn3_knn_kernel``).  Other metrics, other widths than 3: NotImplementedError.
 """
 from __future__ import annotations
 
@@ -87,8 +87,9 @@ class KDTree:
         return ops.nn3_query(self.grid, Q, want_fallbacks)
 
     def query(self, X, k: int = 1, return_distance: bool = True, **kwargs):
+        """``sklearn.neighbors.KDTree.query`` for k = 1 (registration_node.py:297-298); k > 1 lives in ``query_knn``."""
         if k != 1:
-            raise NotImplementedError("k != 1 is not implemented (registration_node.py:297-298 asks for k=1)")
+            raise NotImplementedError("query answers k = 1 (registration_node.py:297-298); the k nearest are query_knn(X, k)")
         if kwargs:
             raise NotImplementedError(f"unsupported arguments: {sorted(kwargs)}")
         device_in = isinstance(X, torch.Tensor)
@@ -99,6 +100,29 @@ class KDTree:
         Q = X.to(torch.float64).contiguous() if device_in else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
         idx, dist = ops.nn3_query(self.grid, Q)
         idx, dist = idx.reshape(-1, 1), dist.reshape(-1, 1)
+        if not device_in:
+            idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
+        return (dist, idx) if return_distance else idx
+
+    def query_knn(self, X, k: int, return_distance: bool = True):
+        """``sklearn.neighbors.KDTree.query(X, k)`` for 1 <= k <= 64: ``(dist, ind)`` of shape (K, k), fp64 distances (roots) ascending
+        and int64 rows, equal distances by the lower row; numpy or device tensors as ``query``.  ``k`` above the number of points
+        raises ValueError, as sklearn does."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"k must be at least 1, got {k}")
+        if k > self.grid.n:
+            raise ValueError("k must be less than or equal to the number of training points")
+        if k > ops.NN3_KNN_MAX_K:
+            raise NotImplementedError(f"k = {k}: at most {ops.NN3_KNN_MAX_K} neighbours are implemented")
+        device_in = isinstance(X, torch.Tensor)
+        if not device_in:
+            X = np.asarray(X)
+        if len(X.shape) != 2 or X.shape[1] != 3:
+            raise ValueError("query data dimension must match training data dimension")
+        Q = X.to(torch.float64).contiguous() if device_in else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
+        idx, d2, _ = ops.nn3_knn(self.grid, Q, k)
+        dist = torch.sqrt(d2)
         if not device_in:
             idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
         return (dist, idx) if return_distance else idx

@@ -6,6 +6,7 @@ implementation: every function raises if the tensors are not on a GPU.
 """
 from __future__ import annotations
 
+import math
 import threading
 from typing import Optional, Tuple
 
@@ -630,3 +631,26 @@ def nn3_query(grid: Nn3Grid, q: torch.Tensor, want_fallbacks: bool = False):
     _lib.check(lib.vfm_nn3_query(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), nq,
                                  idx.data_ptr(), dist.data_ptr(), _ptr(fb), _stream()), "nn3_query")
     return (idx, dist, fb) if want_fallbacks else (idx, dist)
+
+
+NN3_KNN_MAX_K = 64
+
+
+def nn3_knn(grid: Nn3Grid, q: torch.Tensor, k: int, max_d2: float = math.inf, want_fallbacks: bool = False):
+    """vfm_nn3_knn: (idx int64[nq, k], d2 fp64[nq, k], count int32[nq]) -- the k nearest points (1 <= k <= 64) of the cloud for every
+    row of ``q`` (nq x 3 fp64), rows ascending in (d2, index), SQUARED distances, only points with ``d2 <= max_d2``; entries past
+    ``count`` are (-1, +inf).  ``faiss.IndexFlatL2.search`` of vfm_reg/utils.py:31,40.  With ``want_fallbacks`` also int32[1], the
+    number of queries that read every point.  No read-back."""
+    _chk(q, torch.float64, "q")
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    k = int(k)
+    lib = _lib.load()
+    nq = q.shape[0]
+    idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+    d2 = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
+    count = torch.empty(nq, dtype=torch.int32, device=q.device)
+    fb = torch.empty(1, dtype=torch.int32, device=q.device) if want_fallbacks else None
+    _lib.check(lib.vfm_nn3_knn(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), nq, k,
+                               float(max_d2), idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _ptr(fb), _stream()), "nn3_knn")
+    return (idx, d2, count, fb) if want_fallbacks else (idx, d2, count)

@@ -1,10 +1,13 @@
-"""Mirror of the hot-path helper of vfm_reg.utils: ``transform_pcl`` (vfm_reg/utils.py:47-54)."""
+"""Mirror of the hot-path helpers of vfm_reg.utils: ``transform_pcl`` (vfm_reg/utils.py:47-54) and ``FaissKNeighbors``
+(vfm_reg/utils.py:19-44) with the map filter that uses it (registration_node.py:704-717, ``grow_deletion_set``)."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
 
-from . import ops
+from . import neighbors, ops
 
 
 def transform_pcl(pcl: np.ndarray, transform: np.ndarray) -> np.ndarray:
@@ -16,3 +19,91 @@ def transform_pcl(pcl: np.ndarray, transform: np.ndarray) -> np.ndarray:
     pcl_out = np.c_[out, pcl[:, 3:]]
     assert pcl_out.shape == pcl.shape
     return pcl_out.astype(pcl.dtype)
+
+
+class FaissKNeighbors:
+    """``vfm_reg.utils.FaissKNeighbors`` (utils.py:19-44) on the exact 3-D k-NN search of csrc/nn3.hip instead of a
+    ``faiss.IndexFlatL2``: numpy in, numpy out, N x 3 points, k <= 64.
+
+    ``fit`` casts to float32 as the reference does; the search runs on those float32 coordinates widened to fp64.  The reference's
+    quirks stay: ``r`` is compared with the SQUARED distance; ``query`` keeps ``0 < d2 < r`` and returns ``np.unique(y[...])``;
+    ``n_neighbors_in_radius`` counts ``0 < d2 <= r``; hits at distance zero still occupy their slots among the k, because the cut
+    comes after the search; rows with fewer than k points are padded as faiss pads them (index -1), and the cuts drop the padding.
+
+    Deviation: faiss computes the distances in fp32, and for larger batches as ``|x|^2 + |y|^2 - 2 x.y``; here
+    ``d2 = (dx*dx + dy*dy) + dz*dz`` in fp64.  A point within fp32 rounding of ``r``, or two points within rounding of each other
+    (a ``d2`` that faiss rounds to 0 or to a negative number), may fall on the other side of a cut there.  Equal distances go to the
+    lower index here; faiss leaves them open."""
+
+    def __init__(self):
+        self.index = None      # the grid of the fitted points (None: not fitted, or fitted with no points)
+        self.y = None
+        self._n = None
+
+    def fit(self, X, y):
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f"Invalid shape {X.shape}: only N x 3 points are implemented")
+        y = np.asarray(y)
+        if len(y) != len(X):
+            raise ValueError(f"{len(X)} points but {len(y)} labels")
+        self._n = len(X)
+        self.y = y
+        self.index = None
+        if self._n:
+            pts = torch.from_numpy(np.ascontiguousarray(X.astype(np.float32), dtype=np.float64)).cuda()
+            self.index = neighbors.choose_cell(pts)
+
+    def _search(self, X, k, r):
+        """(idx int64[K, k], d2 fp64[K, k]) on the device: faiss's ``index.search(X.astype(np.float32), k)`` with its (-1, huge)
+        padding.  A cap changes no row that passes the cuts (both cuts drop d2 > r) and ends the search sooner."""
+        if self._n is None:
+            raise RuntimeError("FaissKNeighbors: fit() first")
+        k = int(k)
+        if not 1 <= k <= ops.NN3_KNN_MAX_K:
+            raise NotImplementedError(f"k = {k}: 1..{ops.NN3_KNN_MAX_K} neighbours are implemented")
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f"Invalid shape {X.shape}: only N x 3 points are implemented")
+        if self.index is None:      # an empty index: nothing but padding
+            return torch.full((len(X), k), -1, dtype=torch.int64), torch.full((len(X), k), math.inf, dtype=torch.float64)
+        Q = torch.from_numpy(np.ascontiguousarray(X.astype(np.float32), dtype=np.float64)).cuda()
+        r = float(r)
+        idx, d2, _ = ops.nn3_knn(self.index, Q, k, max_d2=r if r >= 0 else math.inf)
+        return idx, d2
+
+    def query(self, X, k, r):
+        """utils.py:30-37: the labels of the points among the k nearest of any row of X with ``0 < d2 < r``, unique and sorted."""
+        idx, d2 = self._search(X, k, r)
+        hit = torch.unique(idx[(d2 > 0) & (d2 < float(r))]).cpu().numpy()     # (the unique of the labels is the unique over unique rows)
+        return np.unique(self.y[hit])
+
+    def n_neighbors_in_radius(self, X, k, r):
+        """utils.py:39-44: per row of X, how many of its k nearest have ``0 < d2 <= r``."""
+        idx, d2 = self._search(X, k, r)
+        return ((d2 > 0) & (d2 <= float(r))).sum(dim=1).cpu().numpy()
+
+
+def _rows_without(n: int, rows: np.ndarray) -> np.ndarray:
+    mask = np.ones(n, dtype=bool)
+    mask[rows] = False
+    return np.flatnonzero(mask)
+
+
+def grow_deletion_set(local_map_xyz: np.ndarray, del_idx: np.ndarray):
+    """The map filter of registration_node.py:704-717 in one function.  ``del_idx`` are the rows of the map (N x 3, further columns
+    ignored) that might be removed.  Isolated candidates go first: one with fewer than 3 other candidates at 0 < d2 <= .5 among its
+    10 nearest candidates is dropped (RN:705-708).  Then the set grows: every other point of the map that is among the 50 nearest of
+    a remaining candidate at 0 < d2 < .5 joins it (RN:709-715).  Returns ``(del_idx, keep_idx)`` as RN:715-717 leave them: the
+    remaining candidates followed by the joined rows in ascending order, and the rows of the map in neither, ascending."""
+    xyz = np.asarray(local_map_xyz)[:, :3]
+    n = xyz.shape[0]
+    cand = np.asarray(del_idx).astype(np.int64)
+    among = FaissKNeighbors()
+    among.fit(xyz[cand], cand)
+    cand = cand[among.n_neighbors_in_radius(xyz[cand], 10, .5) >= 3]
+    others = _rows_without(n, cand)
+    rest = FaissKNeighbors()
+    rest.fit(xyz[others], others)
+    grown = np.concatenate([cand, rest.query(xyz[cand], 50, .5)])
+    return grown, _rows_without(n, grown)
