@@ -74,6 +74,85 @@ def test_structured_cloud(scene, k):
         assert torch.equal(idx[:, 0], i1) and torch.equal(torch.sqrt(d2[:, 0]), dist1) and bool((count == 1).all())
 
 
+def _lattice():
+    g = np.arange(8, dtype=np.float64)
+    P = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    P = P[np.random.default_rng(3).permutation(len(P))]
+    return P, np.concatenate([P[:150], P[150:300] + 0.5])            # ties on the shells' borders at every cell size below
+
+
+def _scene500():
+    from vfmreg import synth
+    P = synth.make_structured_scene(100, 500, seed=11)["map"]
+    rng = np.random.default_rng(14)
+    return P, P[:300] + rng.normal(0, 0.03, (300, 3))                # centimetres off a row: 8 shells of 0.1 mm hold no point
+
+
+def _border(name):
+    """the first 512 rows of the border cloud (rows are in random order: every sub-cloud is among them) and at most 300 queries of a set"""
+    P = gb.nn3_cloud(1.0)[0][:512]
+    Q = gb.nn3_queries(P, 1.0)[name]
+    return P, Q[np.linspace(0, len(Q) - 1, min(len(Q), 300)).astype(np.int64)]
+
+
+def _one_cell():
+    P, Q = _scene500()
+    shift = 1.0 - P.min(axis=0)
+    return P + shift, Q + shift
+
+
+def _nan_queries():
+    P, Q = _scene500()
+    Q = Q[:20].copy()
+    Q[np.arange(20), np.arange(20) % 3] = np.nan
+    return P, Q
+
+
+# name -> (cloud and queries, cell, queries that read every point: "all", "none" or None for whatever the two kernels agree on)
+ONE_WALK_CASES = {
+    "lattice, cell 0.3": (_lattice, 0.3, None),
+    "lattice, cell 1": (_lattice, 1.0, "none"),
+    "lattice, cell 2.5": (_lattice, 2.5, "none"),
+    "scene, cell 1e-4": (_scene500, 1e-4, "all"),
+    "scene in one cell": (_one_cell, 1000.0, "none"),
+    "border, rows": (lambda: _border("rows"), 1.0, None),
+    "border, near": (lambda: _border("near"), 1.0, None),
+    "border, border": (lambda: _border("border"), 1.0, None),
+    "border, far": (lambda: _border("far"), 1.0, "all"),
+    "border, opposite": (lambda: _border("opposite"), 1.0, None),
+    "NaN queries": (_nan_queries, 0.5, "all"),
+}
+
+
+@pytest.mark.parametrize("case", list(ONE_WALK_CASES))
+def test_one_nearest_and_k_nearest_of_one_agree_bit_for_bit(case):
+    """``ops.nn3_query`` and ``ops.nn3_knn(k = 1)`` walk the same shells: the same row, the same bits of the distance, the same number
+    of queries that read every point -- and both are the oracle's k = 1"""
+    from vfmreg import ops
+    make, cell, fallbacks = ONE_WALK_CASES[case]
+    P, Q = make()
+    assert len(P) <= 512 and len(Q) <= 300
+    grid = ops.nn3_build(dev(P), cell)
+    if case == "scene in one cell":
+        assert len(torch.unique(grid.keys)) == 1
+    idx1, dist1, fb1 = ops.nn3_query(grid, dev(Q), want_fallbacks=True)
+    idx, d2, count, fb = ops.nn3_knn(grid, dev(Q), 1, want_fallbacks=True)
+    assert int(fb1.item()) == int(fb.item())
+    if fallbacks is not None:
+        assert int(fb.item()) == (len(Q) if fallbacks == "all" else 0)
+    want_i, want_d, want_c = knn3_oracle.knn(P, Q, 1)
+    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
+    np.testing.assert_array_equal(d2.cpu().numpy(), want_d)
+    np.testing.assert_array_equal(count.cpu().numpy(), want_c)
+    if case == "NaN queries":
+        assert bool((idx1 == -1).all()) and bool(torch.isnan(dist1).all())
+        assert bool((count == 0).all()) and bool((idx == -1).all()) and bool((d2 == INF).all())
+    else:
+        assert torch.equal(idx[:, 0], idx1) and bool((idx1 >= 0).all())
+        assert torch.equal(torch.sqrt(d2[:, 0]), dist1)              # torch.equal on fp64: the same bits (no NaN here)
+        assert bool((count == 1).all())
+
+
 @pytest.mark.parametrize("n", [1, 5])
 def test_fewer_points_than_k(n):
     rng = np.random.default_rng(20 + n)

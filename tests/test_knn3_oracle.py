@@ -59,6 +59,26 @@ def test_oracle_order_cap_and_padding():
     assert idx.shape == d2.shape == (0, 4) and count.shape == (0,)
 
 
+def test_the_two_oracles_state_one_order_on_exact_ties():
+    """nn3_oracle.nearest(P, Q) is knn3_oracle.knn(P, Q, 1): the same index among equal distances, the same bits of the distance"""
+    g = np.arange(8, dtype=np.float64)
+    P = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    P = P[np.random.default_rng(3).permutation(len(P))]
+    Q = np.concatenate([P[:150], P[150:300] + 0.5])                          # lattice points and cell centres (8 equal distances)
+    rng = np.random.default_rng(4)
+    base = rng.uniform(-3, 3, (300, 3))
+    P3 = np.concatenate([base, base, base])[rng.permutation(900)]            # every point three times
+    Q3 = np.concatenate([base[:200], rng.uniform(-3, 3, (100, 3))])
+    for points, queries in ((P, Q), (P3, Q3)):
+        idx, d2, count = knn3_oracle.knn(points, queries, 1)
+        w_i, w_d = nn3_oracle.nearest(points, queries)
+        tied = (((points[None, :, :] - queries[:, None, :]) ** 2).sum(-1) == d2[:, :1]).sum(1)
+        assert (tied > 1).sum() >= 140                                       # the inputs do hold ties (a centre beyond the last plane: fewer)
+        assert (count == 1).all()
+        np.testing.assert_array_equal(idx[:, 0], w_i)
+        np.testing.assert_array_equal(np.sqrt(d2[:, 0]), w_d)                # bit-equal
+
+
 def test_restated_class_keeps_the_reference_quirks():
     P = np.array([[0.0, 0, 0], [0.5, 0, 0], [0, 0.7, 0], [0, 0, 1.0], [0.0, 0, 0]])           # squared distances from the origin: 0, .25, .49, 1, 0
     y = np.array([40, 30, 20, 10, 50])

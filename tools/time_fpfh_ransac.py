@@ -15,39 +15,17 @@ The driver runs two steps, each a child process of its own under ``timeout``; a 
 Times are host clocks around calls that end in a device synchronise (medians after untimed warm-up calls).
 """
 import argparse
-import json
-import subprocess
 import sys
 import time
 from pathlib import Path
+
+from _timing import med_of, median, run_steps, timed, write_report, write_step
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
 
 STEPS = (("query", 400), ("call", 400))
 TARGETS = (1, 2, 4, 8, 16, 32, 64)
-
-
-def timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0), r
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def med_of(fn, reps=15, warm=3):
-    ts, r = [], None
-    for k in range(warm + reps):
-        ms, r = timed(fn)
-        if k >= warm:
-            ts.append(ms)
-    return median(ts), min(ts), r
 
 
 def brute_force(P, Q, chunk=512):
@@ -219,27 +197,14 @@ def main():
     if a.step:
         import torch
         assert torch.cuda.is_available(), "needs a ROCm device"
-        r = step_query() if a.step == "query" else step_call()
-        r = dict(result=r, box=f"{torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), ROCm {torch.version.hip}, torch {torch.__version__}")
-        Path(a.json).write_text(json.dumps(r, indent=1))
-        print(json.dumps(r["result"])[:3000], flush=True)
+        write_step(Path(a.json), step_query() if a.step == "query" else step_call(), show=3000)
         return 0
     out = Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)
-    res, box = {}, ""
-    for step, limit in STEPS:
-        js = out.with_suffix(f".{step}.json")
-        rc = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, str(Path(__file__).resolve()), "--step", step, "--json", str(js)]).returncode
-        if rc != 0:
-            print(f"step {step} ended with status {rc}: stopping", flush=True)
-            return rc
-        d = json.loads(js.read_text())
-        res[step], box = d["result"], d["box"]
-        js.unlink()
-    out.write_text(render(res, box))
-    out.with_suffix(".json").write_text(json.dumps(dict(box=box, **res), indent=1))
-    print(out.read_text())
-    return 0
+    rc, res, box = run_steps(Path(__file__).resolve(), out, STEPS)
+    if rc == 0:
+        write_report(out, render(res, box), dict(box=box, **res))
+    return rc
 
 
 if __name__ == "__main__":

@@ -16,11 +16,11 @@ The driver runs three steps, each a child process of its own under ``timeout``; 
 Times are host clocks around calls that end in a device synchronise (medians); the poses of (a) and (b) must be equal bit for bit.
 """
 import argparse
-import json
-import subprocess
 import sys
 import time
 from pathlib import Path
+
+from _timing import median, run_steps, timed, write_report, write_step
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
@@ -46,19 +46,6 @@ def scene(n_map, n_scan, half, seed):
     guess = T.copy()
     guess[:3, 3] += rng.normal(0, 0.3, 3)
     return m, scan, guess
-
-
-def timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0), r
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
 
 
 def step_grid():
@@ -219,27 +206,14 @@ def main():
     if a.step:
         import torch
         assert torch.cuda.is_available(), "needs a ROCm device"
-        r = step_grid() if a.step == "grid" else step_chain(a.step)
-        r = dict(result=r, box=f"{torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), ROCm {torch.version.hip}, torch {torch.__version__}")
-        Path(a.json).write_text(json.dumps(r, indent=1))
-        print(json.dumps(r["result"])[:2000], flush=True)
+        write_step(Path(a.json), step_grid() if a.step == "grid" else step_chain(a.step), show=2000)
         return 0
     out = Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)
-    res, box = {}, ""
-    for step, limit in STEPS:
-        js = out.with_suffix(f".{step}.json")
-        rc = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, str(Path(__file__).resolve()), "--step", step, "--json", str(js)]).returncode
-        if rc != 0:
-            print(f"step {step} ended with status {rc}: stopping", flush=True)
-            return rc
-        d = json.loads(js.read_text())
-        res[step], box = d["result"], d["box"]
-        js.unlink()
-    out.write_text(render(res, box))
-    out.with_suffix(".json").write_text(json.dumps(dict(box=box, **res), indent=1))
-    print(out.read_text())
-    return 0
+    rc, res, box = run_steps(Path(__file__).resolve(), out, STEPS)
+    if rc == 0:
+        write_report(out, render(res, box), dict(box=box, **res))
+    return rc
 
 
 if __name__ == "__main__":

@@ -17,10 +17,11 @@ Times are host clocks around calls that end in a device synchronise (medians aft
 import argparse
 import json
 import math
-import subprocess
 import sys
 import time
 from pathlib import Path
+
+from _timing import med_of, run_steps, write_report, write_step
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
@@ -28,28 +29,6 @@ sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
 LIMIT_S = 540
 TARGETS = (1, 2, 4, 8, 16, 32, 64)
 FORMS = ((10, 0.5), (50, 0.5), (25, math.inf))     # (k, max_d2)
-
-
-def timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0), r
-
-
-def median(v):
-    return sorted(v)[len(v) // 2]
-
-
-def med_of(fn, reps=10, warm=3):
-    ts, r = [], None
-    for i in range(warm + reps):
-        ms, r = timed(fn)
-        if i >= warm:
-            ts.append(ms)
-    return median(ts), min(ts), r
 
 
 def brute_knn(P, Q, k, chunk=2048):
@@ -190,22 +169,14 @@ def main():
     if a.step:
         import torch
         assert torch.cuda.is_available(), "needs a ROCm device"
-        r = dict(result=step(), box=f"{torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), ROCm {torch.version.hip}, torch {torch.__version__}")
-        Path(a.json).write_text(json.dumps(r, indent=1))
+        write_step(Path(a.json), step())
         return 0
     out = Path(a.out)
     out.parent.mkdir(parents=True, exist_ok=True)
-    js = out.with_suffix(".step.json")
-    rc = subprocess.run(["timeout", "-k", "10", str(LIMIT_S), sys.executable, str(Path(__file__).resolve()), "--step", "--json", str(js)]).returncode
-    if rc != 0:
-        print(f"the timing step ended with status {rc}", flush=True)
-        return rc
-    d = json.loads(js.read_text())
-    js.unlink()
-    out.write_text(render(d["result"], d["box"]))
-    out.with_suffix(".json").write_text(json.dumps(dict(box=d["box"], **d["result"]), indent=1))
-    print(out.read_text())
-    return 0
+    rc, res, box = run_steps(Path(__file__).resolve(), out, (("", LIMIT_S),))
+    if rc == 0:
+        write_report(out, render(res[""], box), dict(box=box, **res[""]))
+    return rc
 
 
 if __name__ == "__main__":

@@ -1,13 +1,13 @@
 // nn3.hip -- exact 1-nearest-neighbour search in 3-D on MI355X (gfx950): the two sklearn.neighbors.KDTree(X, metric="euclidean")
 // .query(Q, k=1) calls of registration_node.py:295-298, which recover the row of every correspondence point in the voxelised clouds.
 //   Nn3Cells (grid3.h) / nn3_gather_kernel a sorted-key CSR grid over the cloud (cell = the caller's), points copied in cell order
-//   nn3_query_kernel                     one wave per query: the 27 cells around the query, then shells of cells, until the best d2
-//                                        is below anything a cell outside the searched cube can hold; past NN3_MAX_RINGS shells a scan
-//                                        of every point (queries far from the cloud, or in its empty regions)
-//   nn3_knn_kernel                       the same walk for the k <= 64 nearest (vfm_reg/utils.py:19-44, faiss.IndexFlatL2.search): the k
-//                                        best so far are a sorted list in registers, an entry per lane
+//   nn3_walk                             one wave per query: the 27 cells around the query, then shells of cells, until the sink says
+//                                        that no cell outside the searched cube can change its answer; past NN3_MAX_RINGS shells a scan
+//                                        of every point
+//   nn3_query_kernel                     the walk into a Best per lane (Nn3Nearest)
+//   nn3_knn_kernel                       the walk into the k <= 64 best so far, a sorted list in registers, an entry per lane (Nn3List)
 // fp64, -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, dist = sqrt(d2) (correctly rounded), equal d2 to the lower index (a
-// convention of this library; sklearn leaves it unspecified).  tests/nn3_oracle.py repeats it in numpy.
+// convention of this library; sklearn leaves it unspecified).  tests/nn3_oracle.py and tests/knn3_oracle.py repeat it in numpy.
 #include "grid3.h"
 
 namespace {
@@ -41,197 +41,183 @@ __global__ __launch_bounds__(256) void nn3_gather_kernel(const double* __restric
 
 using grid3::Best;
 
-// the points sorted[lo, lo + len) against the query, a lane per point
-__device__ __forceinline__ void nn3_scan_run(Best& b, const double* __restrict__ sorted, const int* __restrict__ order, int lo, int len,
-                                             double qx, double qy, double qz, int lane) {
-    for (int t = lane; t < len; t += 64) {
-        const int64_t s = lo + t;
-        const double dx = sorted[3 * s] - qx, dy = sorted[3 * s + 1] - qy, dz = sorted[3 * s + 2] - qz;
-        grid3::take(b, (dx * dx + dy * dy) + dz * dz, order[s]);
+// f(lane) for every set bit of a wave-uniform ballot, in ascending lane order
+template <typename F>
+__device__ __forceinline__ void nn3_each_lane(unsigned long long m, F f) {
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        f(src);
     }
 }
 
-// One wave (= one workgroup) per query.  Shell r is walked by columns (ax, ay) of the (2r + 1)^2 square: the z-cells of a column are
-// consecutive keys, so a column on the square's border is ONE run of keys (cz - r .. cz + r) and a column inside it two single
-// cells (cz - r and cz + r).  64 columns at a time find their runs with two binary searches per lane; the wave then reads each
-// non-empty run together, a lane per point, from the copy of the cloud kept in cell order.
-__global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict__ sorted, const long long* __restrict__ keys,
-                                                       const int* __restrict__ order, int n, double inv_cell, double cell,
-                                                       const double* __restrict__ q, int64_t nq, int64_t* __restrict__ idx_out,
-                                                       double* __restrict__ dist_out, int* __restrict__ fallback_count) {
-    const int64_t qi = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
-    const long long cx = nn3_cell(qx, inv_cell), cy = nn3_cell(qy, inv_cell), cz = nn3_cell(qz, inv_cell);
-    Best best{INFINITY, 0x7FFFFFFF};
+// What shell r holds of column (ax, ay): the z-cells of a column are consecutive keys, so a column on the border of the (2r + 1)^2
+// square is ONE run of keys (cz - r .. cz + r, `whole`) and a column inside it two single cells (a: cz - r, b: cz + r).  A run ends at
+// grid3::upper_bound, which needs no key + 1.
+struct Nn3Runs {
+    int lo_a, len_a, lo_b, len_b;
+};
+__device__ __forceinline__ Nn3Runs nn3_column_runs(const long long* __restrict__ keys, int n, long long ax, long long ay, long long cz, int r,
+                                                   bool whole) {
+    const long long key_lo = grid3::key(ax, ay, cz - r), key_hi = grid3::key(ax, ay, cz + r);
+    Nn3Runs c{grid3::lower_bound(keys, n, key_lo), 0, 0, 0};
+    if (whole) {
+        c.len_a = grid3::upper_bound(keys, n, key_hi) - c.lo_a;
+    } else {
+        c.len_a = grid3::upper_bound(keys, n, key_lo) - c.lo_a;
+        c.lo_b = grid3::lower_bound(keys, n, key_hi);
+        c.len_b = grid3::upper_bound(keys, n, key_hi) - c.lo_b;
+    }
+    return c;
+}
+
+struct Nn3Query {   // one wave (= one workgroup) per query
+    const double* __restrict__ sorted;
+    const int* __restrict__ order;
+    double x, y, z;
+    int lane;
+};
+
+// The walk of both searches.  Shell r = the cells at Chebyshev distance r from the query's cell (r = 1: the 27 cells around it, the
+// query's own among them -- so r starts at 1), walked by columns: 64 columns at a time find their runs with two binary searches per
+// lane, and the wave then reads each non-empty run together from the copy of the cloud kept in cell order (sink.run, lo and len the
+// same in every lane).  After shell r every point of a cell at most r cells from the query's in every axis has been read -- clamping
+// is 1-Lipschitz (grid3.h), so that holds at the border too -- and every other point has a computed d2 >= reach^2, reach = r cells
+// shortened by NN3_RING_SLACK (see there).  sink.done(reach^2) says whether no such point can change the answer; since the bound is
+// >=, a sink must ask for strictly less than reach^2 before it rules out ties from outside.  Past NN3_MAX_RINGS shells (queries far
+// from the cloud, or in its empty regions) the sink reads every point from where sink.restart() leaves it -- the shells already searched
+// are read again -- and done(+inf) closes that scan.
+template <typename Sink>
+__device__ __forceinline__ void nn3_walk(Sink& sink, const Nn3Query& q, const long long* __restrict__ keys, int n, double inv_cell,
+                                         double cell, int* __restrict__ fallback_count) {
+    const long long cx = nn3_cell(q.x, inv_cell), cy = nn3_cell(q.y, inv_cell), cz = nn3_cell(q.z, inv_cell);
     bool done = false;
     for (int r = 1; r <= NN3_MAX_RINGS && !done; ++r) {
         const int side = 2 * r + 1;
         const int columns = side * side;
         for (int base = 0; base < columns; base += 64) {
-            const int t = base + lane;
-            int lo_a = 0, len_a = 0, lo_b = 0, len_b = 0;
+            const int t = base + q.lane;
+            Nn3Runs c{0, 0, 0, 0};
             if (t < columns) {
                 const int dx = t / side - r, dy = t % side - r;
-                const long long ax = cx + dx, ay = cy + dy;
-                const bool whole = r == 1 || dx == -r || dx == r || dy == -r || dy == r;
-                if (whole) {
-                    lo_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r));
-                    len_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r) + 1) - lo_a;
-                } else {
-                    lo_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r));
-                    len_a = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz - r) + 1) - lo_a;
-                    lo_b = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r));
-                    len_b = grid3::lower_bound(keys, n, grid3::key(ax, ay, cz + r) + 1) - lo_b;
-                }
+                c = nn3_column_runs(keys, n, cx + dx, cy + dy, cz, r, r == 1 || dx == -r || dx == r || dy == -r || dy == r);
             }
-            unsigned long long ma = __ballot(len_a > 0);
-            while (ma) {
-                const int src = __ffsll((long long)ma) - 1;
-                ma &= ma - 1;
-                nn3_scan_run(best, sorted, order, __shfl(lo_a, src), __shfl(len_a, src), qx, qy, qz, lane);
-            }
-            unsigned long long mb = __ballot(len_b > 0);
-            while (mb) {
-                const int src = __ffsll((long long)mb) - 1;
-                mb &= mb - 1;
-                nn3_scan_run(best, sorted, order, __shfl(lo_b, src), __shfl(len_b, src), qx, qy, qz, lane);
-            }
+            nn3_each_lane(__ballot(c.len_a > 0), [&](int src) { sink.run(q, __shfl(c.lo_a, src), __shfl(c.len_a, src)); });
+            nn3_each_lane(__ballot(c.len_b > 0), [&](int src) { sink.run(q, __shfl(c.lo_b, src), __shfl(c.len_b, src)); });
         }
-        best = grid3::wave_best(best);
         const double reach = ((double)r * cell) * NN3_RING_SLACK;
-        done = best.d2 < reach * reach;
+        done = sink.done(reach * reach);
     }
     if (!done) {
-        // more shells than the cap: every point (the shells already searched are read again -- the best of all is the best)
-        nn3_scan_run(best, sorted, order, 0, n, qx, qy, qz, lane);
-        best = grid3::wave_best(best);
-        if (fallback_count && lane == 0) atomicAdd(fallback_count, 1);
+        sink.restart();
+        sink.run(q, 0, n);
+        (void)sink.done(INFINITY);
+        if (fallback_count && q.lane == 0) atomicAdd(fallback_count, 1);
     }
-    if (lane == 0) {
-        const bool found = best.idx != 0x7FFFFFFF;   // (not found: every d2 is a NaN)
-        idx_out[qi] = found ? (int64_t)best.idx : (int64_t)-1;
-        dist_out[qi] = found ? sqrt(best.d2) : NAN;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the nearest
+// A Best per lane, reduced over the wave once per shell.  Done when the best d2 is strictly below reach^2: nothing outside the cube can
+// beat or tie it.  The scan of every point keeps the best so far: the best of all is the best, however often a point is read.
+struct Nn3Nearest {
+    Best best{INFINITY, 0x7FFFFFFF};
+    __device__ __forceinline__ void run(const Nn3Query& q, int lo, int len) {   // a lane per point
+        for (int t = q.lane; t < len; t += 64) {
+            const int64_t s = lo + t;
+            const double dx = q.sorted[3 * s] - q.x, dy = q.sorted[3 * s + 1] - q.y, dz = q.sorted[3 * s + 2] - q.z;
+            grid3::take(best, (dx * dx + dy * dy) + dz * dz, q.order[s]);
+        }
+    }
+    __device__ __forceinline__ bool done(double reach2) {
+        best = grid3::wave_best(best);
+        return best.d2 < reach2;
+    }
+    __device__ __forceinline__ void restart() {}
+};
+
+__global__ __launch_bounds__(64) void nn3_query_kernel(const double* __restrict__ sorted, const long long* __restrict__ keys,
+                                                       const int* __restrict__ order, int n, double inv_cell, double cell,
+                                                       const double* __restrict__ q, int64_t nq, int64_t* __restrict__ idx_out,
+                                                       double* __restrict__ dist_out, int* __restrict__ fallback_count) {
+    const int64_t qi = blockIdx.x;
+    const Nn3Query query{sorted, order, q[3 * qi], q[3 * qi + 1], q[3 * qi + 2], (int)threadIdx.x};
+    Nn3Nearest sink;
+    nn3_walk(sink, query, keys, n, inv_cell, cell, fallback_count);
+    if (query.lane == 0) {
+        const bool found = sink.best.idx != 0x7FFFFFFF;   // (not found: every d2 is a NaN)
+        idx_out[qi] = found ? (int64_t)sink.best.idx : (int64_t)-1;
+        dist_out[qi] = found ? sqrt(sink.best.d2) : NAN;
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- k nearest
-// The k best so far, sorted by (d2, index): lane i of the wave holds the i-th smallest, lanes >= k stay at (+inf, 0x7FFFFFFF) for
-// ever.  kth is lane k - 1's entry, the same value in every lane.
+// (vfm_reg/utils.py:19-44, faiss.IndexFlatL2.search.)  The k <= 64 best so far, sorted by (d2, index): lane i of the wave holds the
+// i-th smallest, lanes >= k stay at (+inf, 0x7FFFFFFF) for ever.  kth is lane k - 1's entry, the same value in every lane.  Done when
+// the k-th d2 is strictly below reach^2 -- the list is full then (an empty entry is +inf), and nothing outside the cube can beat or
+// tie an entry -- or when reach^2 > max_d2: every point with d2 <= max_d2 is inside the cube.  The scan of every point starts from an
+// EMPTY list: an entry kept from the shells would be in the list twice.
 struct Nn3List {
-    double d2;
-    int idx;
-    double kth_d2;
-    int kth_idx;
+    double d2 = INFINITY, kth_d2 = INFINITY;
+    int idx = 0x7FFFFFFF, kth_idx = 0x7FFFFFFF;
+    int k;
+    double max_d2;
+    __device__ __forceinline__ Nn3List(int k_, double max_d2_) : k(k_), max_d2(max_d2_) {}
+    // one candidate, the same in every lane and below the k-th entry: entries above it move up a lane, the lane at its position takes
+    // it, lane k - 1's old entry falls off
+    __device__ __forceinline__ void insert(double cd2, int cidx, int lane) {
+        const bool above = grid3::closer(cd2, cidx, d2, idx);              // false .. false true .. true over the lanes: the list is sorted
+        const double up_d2 = __shfl_up(d2, 1);
+        const int up_idx = __shfl_up(idx, 1);
+        const bool up_above = __shfl_up((int)above, 1) != 0 && lane > 0;   // (lane 0 reads itself)
+        if (above && lane < k) {
+            d2 = up_above ? up_d2 : cd2;
+            idx = up_above ? up_idx : cidx;
+        }
+        kth_d2 = __shfl(d2, k - 1);
+        kth_idx = __shfl(idx, k - 1);
+    }
+    // a lane per point, 64 at a time.  A candidate needs d2 <= max_d2 and a place below the k-th entry (a NaN d2 has neither); the
+    // marked ones are inserted one after another, each tested again against the k-th entry as it stands by then.
+    __device__ __forceinline__ void run(const Nn3Query& q, int lo, int len) {
+        for (int t0 = 0; t0 < len; t0 += 64) {
+            const int t = t0 + q.lane;
+            double pd2 = NAN;
+            int j = 0x7FFFFFFF;
+            if (t < len) {
+                const int64_t s = (int64_t)lo + t;
+                const double dx = q.sorted[3 * s] - q.x, dy = q.sorted[3 * s + 1] - q.y, dz = q.sorted[3 * s + 2] - q.z;
+                pd2 = (dx * dx + dy * dy) + dz * dz;
+                j = q.order[s];
+            }
+            nn3_each_lane(__ballot(pd2 <= max_d2 && grid3::closer(pd2, j, kth_d2, kth_idx)), [&](int src) {
+                const double cd2 = __shfl(pd2, src);
+                const int cidx = __shfl(j, src);
+                if (grid3::closer(cd2, cidx, kth_d2, kth_idx)) insert(cd2, cidx, q.lane);   // (the same branch in every lane)
+            });
+        }
+    }
+    __device__ __forceinline__ bool done(double reach2) const { return kth_d2 < reach2 || reach2 > max_d2; }
+    __device__ __forceinline__ void restart() {
+        d2 = kth_d2 = INFINITY;
+        idx = kth_idx = 0x7FFFFFFF;
+    }
 };
-__device__ __forceinline__ void nn3_list_clear(Nn3List& l) {
-    l.d2 = l.kth_d2 = INFINITY;
-    l.idx = l.kth_idx = 0x7FFFFFFF;
-}
-// one candidate, the same in every lane and below the k-th entry: entries above it move up a lane, the lane at its position takes it,
-// lane k - 1's old entry falls off
-__device__ __forceinline__ void nn3_list_insert(Nn3List& l, double cd2, int cidx, int k, int lane) {
-    const bool above = grid3::closer(cd2, cidx, l.d2, l.idx);          // false .. false true .. true over the lanes: the list is sorted
-    const double up_d2 = __shfl_up(l.d2, 1);
-    const int up_idx = __shfl_up(l.idx, 1);
-    const bool up_above = __shfl_up((int)above, 1) != 0 && lane > 0;   // (lane 0 reads itself)
-    if (above && lane < k) {
-        l.d2 = up_above ? up_d2 : cd2;
-        l.idx = up_above ? up_idx : cidx;
-    }
-    l.kth_d2 = __shfl(l.d2, k - 1);
-    l.kth_idx = __shfl(l.idx, k - 1);
-}
-// the points sorted[lo, lo + len) against the query, a lane per point, 64 at a time; lo and len are the same in every lane.  A
-// candidate needs d2 <= max_d2 and a place below the k-th entry (a NaN d2 has neither); the marked ones are inserted one after
-// another, each tested again against the k-th entry as it stands by then.
-__device__ __forceinline__ void nn3_knn_run(Nn3List& l, const double* __restrict__ sorted, const int* __restrict__ order, int lo, int len,
-                                            double qx, double qy, double qz, double max_d2, int k, int lane) {
-    for (int t0 = 0; t0 < len; t0 += 64) {
-        const int t = t0 + lane;
-        double d2 = NAN;
-        int j = 0x7FFFFFFF;
-        if (t < len) {
-            const int64_t s = (int64_t)lo + t;
-            const double dx = sorted[3 * s] - qx, dy = sorted[3 * s + 1] - qy, dz = sorted[3 * s + 2] - qz;
-            d2 = (dx * dx + dy * dy) + dz * dz;
-            j = order[s];
-        }
-        unsigned long long m = __ballot(d2 <= max_d2 && grid3::closer(d2, j, l.kth_d2, l.kth_idx));
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const double cd2 = __shfl(d2, src);
-            const int cidx = __shfl(j, src);
-            if (grid3::closer(cd2, cidx, l.kth_d2, l.kth_idx)) nn3_list_insert(l, cd2, cidx, k, lane);   // (the same branch in every lane)
-        }
-    }
-}
 
-// One wave (= one workgroup) per query: nn3_query_kernel's walk with the list where its Best is.  After shell r the search stops
-// when the k-th d2 is below reach^2 = (r cell NN3_RING_SLACK)^2 -- the list is full then (an empty entry is +inf), and every point
-// outside the searched cube has a computed d2 >= reach^2, so it can neither beat nor tie an entry -- or when reach^2 > max_d2: every
-// point with d2 <= max_d2 is inside the cube then.  The end of a column's run is grid3::upper_bound (the last key of all is 2^63 - 1).
 __global__ __launch_bounds__(64) void nn3_knn_kernel(const double* __restrict__ sorted, const long long* __restrict__ keys,
                                                      const int* __restrict__ order, int n, double inv_cell, double cell,
                                                      const double* __restrict__ q, int k, double max_d2, int64_t* __restrict__ idx_out,
                                                      double* __restrict__ d2_out, int* __restrict__ count_out,
                                                      int* __restrict__ fallback_count) {
     const int64_t qi = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double qx = q[3 * qi], qy = q[3 * qi + 1], qz = q[3 * qi + 2];
-    const long long cx = nn3_cell(qx, inv_cell), cy = nn3_cell(qy, inv_cell), cz = nn3_cell(qz, inv_cell);
-    Nn3List list;
-    nn3_list_clear(list);
-    bool done = false;
-    for (int r = 1; r <= NN3_MAX_RINGS && !done; ++r) {
-        const int side = 2 * r + 1;
-        const int columns = side * side;
-        for (int base = 0; base < columns; base += 64) {
-            const int t = base + lane;
-            int lo_a = 0, len_a = 0, lo_b = 0, len_b = 0;
-            if (t < columns) {
-                const int dx = t / side - r, dy = t % side - r;
-                const long long ax = cx + dx, ay = cy + dy;
-                const bool whole = r == 1 || dx == -r || dx == r || dy == -r || dy == r;
-                const long long key_lo = grid3::key(ax, ay, cz - r), key_hi = grid3::key(ax, ay, cz + r);
-                lo_a = grid3::lower_bound(keys, n, key_lo);
-                if (whole) {
-                    len_a = grid3::upper_bound(keys, n, key_hi) - lo_a;
-                } else {
-                    len_a = grid3::upper_bound(keys, n, key_lo) - lo_a;
-                    lo_b = grid3::lower_bound(keys, n, key_hi);
-                    len_b = grid3::upper_bound(keys, n, key_hi) - lo_b;
-                }
-            }
-            unsigned long long ma = __ballot(len_a > 0);
-            while (ma) {
-                const int src = __ffsll((long long)ma) - 1;
-                ma &= ma - 1;
-                nn3_knn_run(list, sorted, order, __shfl(lo_a, src), __shfl(len_a, src), qx, qy, qz, max_d2, k, lane);
-            }
-            unsigned long long mb = __ballot(len_b > 0);
-            while (mb) {
-                const int src = __ffsll((long long)mb) - 1;
-                mb &= mb - 1;
-                nn3_knn_run(list, sorted, order, __shfl(lo_b, src), __shfl(len_b, src), qx, qy, qz, max_d2, k, lane);
-            }
-        }
-        const double reach = ((double)r * cell) * NN3_RING_SLACK;
-        done = list.kth_d2 < reach * reach || reach * reach > max_d2;
-    }
-    if (!done) {
-        // more shells than the cap: every point, into an EMPTY list (the shells already searched are read again, and an entry kept
-        // from them would be in the list twice)
-        nn3_list_clear(list);
-        nn3_knn_run(list, sorted, order, 0, n, qx, qy, qz, max_d2, k, lane);
-        if (fallback_count && lane == 0) atomicAdd(fallback_count, 1);
-    }
-    const bool found = list.idx != 0x7FFFFFFF;   // (found implies lane < k)
+    const Nn3Query query{sorted, order, q[3 * qi], q[3 * qi + 1], q[3 * qi + 2], (int)threadIdx.x};
+    Nn3List sink(k, max_d2);
+    nn3_walk(sink, query, keys, n, inv_cell, cell, fallback_count);
+    const int lane = query.lane;
+    const bool found = sink.idx != 0x7FFFFFFF;   // (found implies lane < k)
     const unsigned long long fm = __ballot(found);
     if (lane < k) {
-        idx_out[qi * k + lane] = found ? (int64_t)list.idx : (int64_t)-1;
-        d2_out[qi * k + lane] = found ? list.d2 : INFINITY;
+        idx_out[qi * k + lane] = found ? (int64_t)sink.idx : (int64_t)-1;
+        d2_out[qi * k + lane] = found ? sink.d2 : INFINITY;
     }
     if (lane == 0) count_out[qi] = __popcll(fm);
 }
@@ -265,14 +251,23 @@ VFM_EXPORT int vfm_nn3_build(const double* pts, int64_t n, double cell, int64_t*
     return VFM_OK;
 }
 
+// What the two query entry points check alike (`who` opens every text) and do before a launch: the count of queries that read every
+// point is cleared; *launch is false for nq == 0, which is then complete.
+static int nn3_query_begin(const char* who, int64_t n, double cell, int64_t nq, int32_t* fallback_count_out, hipStream_t st, bool* launch) {
+    VFM_CHECK_ARG(n >= 1 && n <= NN3_MAX_POINTS, "%s: n must be in 1..2^26 (an empty cloud has no nearest point)", who);
+    VFM_CHECK_ARG(cell > 0.0 && cell < INFINITY, "%s: the cell size must be positive and finite", who);
+    VFM_CHECK_ARG(nq >= 0 && nq <= 0x7FFFFFFF, "%s: nq must be in 0..2^31-1", who);
+    if (fallback_count_out) VFM_CHECK_HIP(hipMemsetAsync(fallback_count_out, 0, sizeof(int32_t), st));
+    *launch = nq > 0;
+    return VFM_OK;
+}
+
 VFM_EXPORT int vfm_nn3_query(const int64_t* keys, const int32_t* order, const double* sorted, int64_t n, double cell, const double* queries,
                              int64_t nq, int64_t* idx_out, double* dist_out, int32_t* fallback_count_out, vfm_stream_t stream) {
-    VFM_CHECK_ARG(n >= 1 && n <= NN3_MAX_POINTS, "nn3_query: n must be in 1..2^26 (an empty cloud has no nearest point)");
-    VFM_CHECK_ARG(cell > 0.0 && cell < INFINITY, "nn3_query: the cell size must be positive and finite");
-    VFM_CHECK_ARG(nq >= 0 && nq <= 0x7FFFFFFF, "nn3_query: nq must be in 0..2^31-1");
     hipStream_t st = (hipStream_t)stream;
-    if (fallback_count_out) VFM_CHECK_HIP(hipMemsetAsync(fallback_count_out, 0, sizeof(int32_t), st));
-    if (nq == 0) return VFM_OK;
+    bool launch = false;
+    VFM_TRY(nn3_query_begin("nn3_query", n, cell, nq, fallback_count_out, st, &launch));
+    if (!launch) return VFM_OK;
     VFM_CHECK_ARG(keys && order && sorted && queries && idx_out && dist_out, "nn3_query: null pointer");
     hipLaunchKernelGGL(nn3_query_kernel, dim3((unsigned)nq), dim3(64), 0, st, sorted, reinterpret_cast<const long long*>(keys), order, (int)n,
                        1.0 / cell, cell, queries, nq, idx_out, dist_out, fallback_count_out);
@@ -283,14 +278,12 @@ VFM_EXPORT int vfm_nn3_query(const int64_t* keys, const int32_t* order, const do
 VFM_EXPORT int vfm_nn3_knn(const int64_t* keys, const int32_t* order, const double* sorted, int64_t n, double cell, const double* queries,
                            int64_t nq, int k, double max_d2, int64_t* idx_out, double* d2_out, int32_t* count_out,
                            int32_t* fallback_count_out, vfm_stream_t stream) {
-    VFM_CHECK_ARG(n >= 1 && n <= NN3_MAX_POINTS, "nn3_knn: n must be in 1..2^26 (an empty cloud has no nearest point)");
-    VFM_CHECK_ARG(cell > 0.0 && cell < INFINITY, "nn3_knn: the cell size must be positive and finite");
-    VFM_CHECK_ARG(nq >= 0 && nq <= 0x7FFFFFFF, "nn3_knn: nq must be in 0..2^31-1");
     VFM_CHECK_ARG(k >= 1 && k <= 64, "nn3_knn: k must be in 1..64 (an entry of the list per lane of the wave)");
     VFM_CHECK_ARG(max_d2 >= 0.0, "nn3_knn: max_d2 must be >= 0 and not a NaN (+inf: no cap)");
     hipStream_t st = (hipStream_t)stream;
-    if (fallback_count_out) VFM_CHECK_HIP(hipMemsetAsync(fallback_count_out, 0, sizeof(int32_t), st));
-    if (nq == 0) return VFM_OK;
+    bool launch = false;
+    VFM_TRY(nn3_query_begin("nn3_knn", n, cell, nq, fallback_count_out, st, &launch));
+    if (!launch) return VFM_OK;
     VFM_CHECK_ARG(keys && order && sorted && queries && idx_out && d2_out && count_out, "nn3_knn: null pointer");
     hipLaunchKernelGGL(nn3_knn_kernel, dim3((unsigned)nq), dim3(64), 0, st, sorted, reinterpret_cast<const long long*>(keys), order, (int)n,
                        1.0 / cell, cell, queries, k, max_d2, idx_out, d2_out, count_out, fallback_count_out);

@@ -56,6 +56,26 @@ def choose_cell(pts: torch.Tensor, target: float = POINTS_PER_CELL, builds: int 
     return grid
 
 
+def _rows(X, training: bool = False):
+    """``X``, a numpy array or a device tensor, as (contiguous fp64 N x 3 rows on the device, it was a device tensor); the shape is
+    refused in sklearn's words for the tree's data (``training``) or for queries before anything is uploaded."""
+    device_in = isinstance(X, torch.Tensor)
+    if not device_in:
+        X = np.asarray(X)
+    shape = tuple(X.shape)
+    if training:
+        if len(shape) != 2:
+            raise ValueError(f"Expected 2D array, got {len(shape)}D array instead")
+        if shape[0] == 0:
+            raise ValueError(f"Found array with 0 sample(s) (shape={shape}) while a minimum of 1 is required.")
+        if shape[1] != 3:
+            raise NotImplementedError("only 3-D points are implemented")
+    elif len(shape) != 2 or shape[1] != 3:
+        raise ValueError("query data dimension must match training data dimension")
+    rows = X.to(torch.float64).contiguous() if device_in else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
+    return rows, device_in
+
+
 class KDTree:
     """``sklearn.neighbors.KDTree(X, leaf_size, metric)`` for N x 3 data: the grid is built here, once (``leaf_size`` has no
     counterpart and is ignored)."""
@@ -65,22 +85,8 @@ class KDTree:
             raise NotImplementedError(f"metric {metric!r}: only 'euclidean' is implemented (registration_node.py:295-296)")
         if kwargs:
             raise NotImplementedError(f"unsupported arguments: {sorted(kwargs)}")
-        device_in = isinstance(X, torch.Tensor)
-        if not device_in:
-            X = np.asarray(X)
-        shape = tuple(X.shape)
-        if len(shape) != 2:
-            raise ValueError(f"Expected 2D array, got {len(shape)}D array instead")
-        if shape[0] == 0:
-            raise ValueError(f"Found array with 0 sample(s) (shape={shape}) while a minimum of 1 is required.")
-        if shape[1] != 3:
-            raise NotImplementedError("only 3-D points are implemented")
-        if device_in:
-            pts = X.to(torch.float64).contiguous()
-        else:
-            pts = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
-        self.data = pts
-        self.grid = choose_cell(pts)
+        self.data, _ = _rows(X, training=True)
+        self.grid = choose_cell(self.data)
 
     def query_device(self, Q: torch.Tensor, want_fallbacks: bool = False):
         """(idx int64[K], dist fp64[K]) on the device, no read-back; ``want_fallbacks``: see ``ops.nn3_query``."""
@@ -92,12 +98,7 @@ class KDTree:
             raise NotImplementedError("query answers k = 1 (registration_node.py:297-298); the k nearest are query_knn(X, k)")
         if kwargs:
             raise NotImplementedError(f"unsupported arguments: {sorted(kwargs)}")
-        device_in = isinstance(X, torch.Tensor)
-        if not device_in:
-            X = np.asarray(X)
-        if len(X.shape) != 2 or X.shape[1] != 3:
-            raise ValueError("query data dimension must match training data dimension")
-        Q = X.to(torch.float64).contiguous() if device_in else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
+        Q, device_in = _rows(X)
         idx, dist = ops.nn3_query(self.grid, Q)
         idx, dist = idx.reshape(-1, 1), dist.reshape(-1, 1)
         if not device_in:
@@ -115,12 +116,7 @@ class KDTree:
             raise ValueError("k must be less than or equal to the number of training points")
         if k > ops.NN3_KNN_MAX_K:
             raise NotImplementedError(f"k = {k}: at most {ops.NN3_KNN_MAX_K} neighbours are implemented")
-        device_in = isinstance(X, torch.Tensor)
-        if not device_in:
-            X = np.asarray(X)
-        if len(X.shape) != 2 or X.shape[1] != 3:
-            raise ValueError("query data dimension must match training data dimension")
-        Q = X.to(torch.float64).contiguous() if device_in else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).cuda()
+        Q, device_in = _rows(X)
         idx, d2, _ = ops.nn3_knn(self.grid, Q, k)
         dist = torch.sqrt(d2)
         if not device_in:

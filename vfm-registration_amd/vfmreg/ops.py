@@ -616,20 +616,23 @@ def nn3_build(pts: torch.Tensor, cell: float, ws: Optional[torch.Tensor] = None)
     return Nn3Grid(keys, order, sorted_pts, cell, n)
 
 
+def _nn3_head(grid: Nn3Grid, q: torch.Tensor) -> tuple:
+    """the arguments vfm_nn3_query and vfm_nn3_knn open with: the structure, then the checked nq x 3 fp64 rows of ``q``"""
+    _chk(q, torch.float64, "q")
+    if q.dim() != 2 or q.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    return grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), q.shape[0]
+
+
 def nn3_query(grid: Nn3Grid, q: torch.Tensor, want_fallbacks: bool = False):
     """vfm_nn3_query: (idx int64[nq], dist fp64[nq]) of the nearest point of the cloud for every row of ``q`` (nq x 3 fp64) --
     ``KDTree.query(k=1)`` of registration_node.py:297-298; with ``want_fallbacks`` also int32[1], the number of queries that read every
     point instead of cells.  No read-back."""
-    _chk(q, torch.float64, "q")
-    if q.dim() != 2 or q.shape[1] != 3:
-        raise ValueError("Invalid shape")
-    lib = _lib.load()
-    nq = q.shape[0]
-    idx = torch.empty(nq, dtype=torch.int64, device=q.device)
-    dist = torch.empty(nq, dtype=torch.float64, device=q.device)
+    head = _nn3_head(grid, q)
+    idx = torch.empty(q.shape[0], dtype=torch.int64, device=q.device)
+    dist = torch.empty(q.shape[0], dtype=torch.float64, device=q.device)
     fb = torch.empty(1, dtype=torch.int32, device=q.device) if want_fallbacks else None
-    _lib.check(lib.vfm_nn3_query(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), nq,
-                                 idx.data_ptr(), dist.data_ptr(), _ptr(fb), _stream()), "nn3_query")
+    _lib.check(_lib.load().vfm_nn3_query(*head, idx.data_ptr(), dist.data_ptr(), _ptr(fb), _stream()), "nn3_query")
     return (idx, dist, fb) if want_fallbacks else (idx, dist)
 
 
@@ -641,16 +644,12 @@ def nn3_knn(grid: Nn3Grid, q: torch.Tensor, k: int, max_d2: float = math.inf, wa
     row of ``q`` (nq x 3 fp64), rows ascending in (d2, index), SQUARED distances, only points with ``d2 <= max_d2``; entries past
     ``count`` are (-1, +inf).  ``faiss.IndexFlatL2.search`` of vfm_reg/utils.py:31,40.  With ``want_fallbacks`` also int32[1], the
     number of queries that read every point.  No read-back."""
-    _chk(q, torch.float64, "q")
-    if q.dim() != 2 or q.shape[1] != 3:
-        raise ValueError("Invalid shape")
-    k = int(k)
-    lib = _lib.load()
-    nq = q.shape[0]
+    head = _nn3_head(grid, q)
+    nq, k = q.shape[0], int(k)
     idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
     d2 = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device)
     count = torch.empty(nq, dtype=torch.int32, device=q.device)
     fb = torch.empty(1, dtype=torch.int32, device=q.device) if want_fallbacks else None
-    _lib.check(lib.vfm_nn3_knn(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), grid.n, grid.cell, q.data_ptr(), nq, k,
-                               float(max_d2), idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _ptr(fb), _stream()), "nn3_knn")
+    _lib.check(_lib.load().vfm_nn3_knn(*head, k, float(max_d2), idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _ptr(fb), _stream()),
+               "nn3_knn")
     return (idx, d2, count, fb) if want_fallbacks else (idx, d2, count)
