@@ -618,6 +618,33 @@ int vfm_nn3_knn(const int64_t *keys, const int32_t *order, const double *sorted,
                 int64_t nq, int k, double max_d2, int64_t *idx_out, double *d2_out, int32_t *count_out,
                 int32_t *fallback_count_out, vfm_stream_t stream);
 
+/* ------------------------------------------------------------------ exact HDBSCAN* in 3-D (the map filter's clustering) */
+
+/* hdbscan.HDBSCAN(min_cluster_size=100, min_samples=25).fit_predict(X) of src/vfm-reg/src/registration_node.py:735-736, as the exact
+ * algorithm with every tie decided (that library builds an approximate spanning tree by default): points are rows of 3 fp64 with
+ * finite coordinates, d2 as above, every order is decided on SQUARES.  core2[i] = the d2 of the min_samples-th nearest point of the
+ * set, i itself included (vfm_nn3_knn with the points as queries, k = min_samples, no cap: column k - 1);
+ * w2(i, j) = max(core2[i], core2[j], d2(i, j)); THE spanning tree is the unique one under the total order
+ * (w2, min(i, j), max(i, j)) on edges.
+ * vfm_mreach_mst_workspace_bytes: the workspace of vfm_mreach_mst for n points. */
+size_t vfm_mreach_mst_workspace_bytes(int64_t n);
+/* That spanning tree, by Boruvka rounds on a structure of vfm_nn3_build over the same n points (2 <= n <= 2^26) and cell.  core2
+ * (fp64[n], by point index): finite, >= 0.  edge_lo_out / edge_hi_out (int32[n - 1]) / w2_out (fp64[n - 1]): the n - 1 edges,
+ * lo < hi, in NO particular order (the caller sorts them by (w2, lo, hi)).  ceil(log2 n) rounds are enqueued; the kernels of a round
+ * that finds one component left return at once.  rounds_out (nullable, device int32[1]): the rounds that did work.
+ * fallback_count_out (nullable, device int32[1]): the searches, over all rounds, that read every point instead of cells.  Nothing
+ * here synchronises `stream` or keeps state between calls. */
+int vfm_mreach_mst(const int64_t *keys, const int32_t *order, const double *sorted, int64_t n, double cell, const double *core2,
+                   int32_t *edge_lo_out, int32_t *edge_hi_out, double *w2_out, int32_t *rounds_out, int32_t *fallback_count_out,
+                   void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* From that tree to labels, on the HOST (no HIP call, host pointers): lo / hi / w2 are the n - 1 edges ascending strictly in
+ * (w2, lo, hi) (anything else, or edges that are no spanning tree: VFM_EINVAL).  Single linkage by Kruskal in that order,
+ * lambda = 1 / sqrt(w2) (+inf for w2 == 0); condensed tree, stabilities and excess-of-mass selection as
+ * sklearn.cluster._hdbscan._tree computes them with allow_single_cluster=False and cluster_selection_epsilon=0.  labels_out
+ * (int32[n]): clusters 0.. in ascending condensed-tree node, noise -1.  min_cluster_size >= 2. */
+int vfm_hdbscan_labels_host(const int32_t *lo, const int32_t *hi, const double *w2, int64_t n, int min_cluster_size,
+                            int32_t *labels_out);
+
 /* ------------------------------------------------------------------ DINOv2 ViT-S/14 (row A1) */
 
 /* self.model.model(img) of IF:101 incl. the transform of IF:67-77: bilinear resize (antialias

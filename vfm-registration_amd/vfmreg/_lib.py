@@ -110,6 +110,9 @@ SIGNATURES = {
     "vfm_nn3_build": (C.c_int, [c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_nn3_query": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_double, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "vfm_nn3_knn": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_double, c_vp, c_i64, C.c_int, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vfm_mreach_mst_workspace_bytes": (C.c_size_t, [c_i64]),
+    "vfm_mreach_mst": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_hdbscan_labels_host": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp]),
     "vfm_vit_weights_bytes": (C.c_size_t, [C.POINTER(VitConfig)]),
     "vfm_vit_weights_layout": (C.c_int, [C.POINTER(VitConfig), C.POINTER(c_i64), C.POINTER(c_i64), C.c_int]),
     "vfm_vit_workspace_bytes": (C.c_size_t, [C.POINTER(VitConfig), C.c_int]),

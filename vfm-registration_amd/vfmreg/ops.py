@@ -653,3 +653,44 @@ def nn3_knn(grid: Nn3Grid, q: torch.Tensor, k: int, max_d2: float = math.inf, wa
     _lib.check(_lib.load().vfm_nn3_knn(*head, k, float(max_d2), idx.data_ptr(), d2.data_ptr(), count.data_ptr(), _ptr(fb), _stream()),
                "nn3_knn")
     return (idx, d2, count, fb) if want_fallbacks else (idx, d2, count)
+
+
+# ------------------------------------------------------------------------------------- exact HDBSCAN* in 3-D (csrc/hdbscan.hip)
+def mreach_mst(grid: Nn3Grid, core2: torch.Tensor, want_counts: bool = False, ws: Optional[torch.Tensor] = None):
+    """vfm_mreach_mst: (lo int32[n-1], hi int32[n-1], w2 fp64[n-1]) -- the edges of THE minimum spanning tree of the grid's points under
+    ``w2(i, j) = max(core2[i], core2[j], d2(i, j))`` and the total order ``(w2, lo, hi)``, in no particular order; ``core2`` fp64[n] by
+    point index, finite and >= 0.  With ``want_counts`` also (rounds int32[1], fallbacks int32[1]): the Boruvka rounds that did work
+    and the searches that read every point.  No read-back."""
+    _chk(core2, torch.float64, "core2")
+    n = grid.n
+    if core2.dim() != 1 or core2.shape[0] != n:
+        raise ValueError(f"core2: expected {n} values, one per point of the grid")
+    lib = _lib.load()
+    dev = core2.device
+    lo = torch.empty(max(n - 1, 0), dtype=torch.int32, device=dev)
+    hi = torch.empty(max(n - 1, 0), dtype=torch.int32, device=dev)
+    w2 = torch.empty(max(n - 1, 0), dtype=torch.float64, device=dev)
+    rounds = torch.empty(1, dtype=torch.int32, device=dev) if want_counts else None
+    fb = torch.empty(1, dtype=torch.int32, device=dev) if want_counts else None
+    need = lib.vfm_mreach_mst_workspace_bytes(n)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    _lib.check(lib.vfm_mreach_mst(grid.keys.data_ptr(), grid.order.data_ptr(), grid.sorted.data_ptr(), n, grid.cell, core2.data_ptr(),
+                                  lo.data_ptr(), hi.data_ptr(), w2.data_ptr(), _ptr(rounds), _ptr(fb), ws.data_ptr(), ws.numel(), _stream()),
+               "mreach_mst")
+    return (lo, hi, w2, rounds, fb) if want_counts else (lo, hi, w2)
+
+
+def hdbscan_labels_host(lo, hi, w2, min_cluster_size: int):
+    """vfm_hdbscan_labels_host: labels int32[n] (numpy, on the host) from the n - 1 edges of the spanning tree ascending in
+    ``(w2, lo, hi)`` (numpy int32, int32, fp64).  No device is touched."""
+    import numpy as np
+    lo = np.ascontiguousarray(lo, dtype=np.int32)
+    hi = np.ascontiguousarray(hi, dtype=np.int32)
+    w2 = np.ascontiguousarray(w2, dtype=np.float64)
+    if not (lo.ndim == hi.ndim == w2.ndim == 1 and len(lo) == len(hi) == len(w2)):
+        raise ValueError("lo, hi and w2 must be three vectors of one length")
+    labels = np.empty(len(lo) + 1, dtype=np.int32)
+    _lib.check(_lib.load().vfm_hdbscan_labels_host(lo.ctypes.data, hi.ctypes.data, w2.ctypes.data, len(lo) + 1, int(min_cluster_size),
+                                                   labels.ctypes.data), "hdbscan_labels_host")
+    return labels

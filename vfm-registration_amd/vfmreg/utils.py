@@ -1,5 +1,6 @@
 """Mirror of the hot-path helpers of vfm_reg.utils: ``transform_pcl`` (vfm_reg/utils.py:47-54) and ``FaissKNeighbors``
-(vfm_reg/utils.py:19-44) with the map filter that uses it (registration_node.py:704-717, ``grow_deletion_set``)."""
+(vfm_reg/utils.py:19-44) with the map filter that uses it (registration_node.py:704-778: ``grow_deletion_set``, ``remove_clusters``
+and both around the clustering in ``filter_map_clusters``)."""
 from __future__ import annotations
 
 import math
@@ -107,3 +108,53 @@ def grow_deletion_set(local_map_xyz: np.ndarray, del_idx: np.ndarray):
     rest.fit(xyz[others], others)
     grown = np.concatenate([cand, rest.query(xyz[cand], 50, .5)])
     return grown, _rows_without(n, grown)
+
+
+def _norm_ppf(p: float) -> float:
+    try:
+        from scipy.stats import norm
+        return float(norm.ppf(p))
+    except ImportError:
+        from statistics import NormalDist
+        if not 0 < p < 1:
+            return -math.inf if p == 0 else math.inf if p == 1 else math.nan
+        return NormalDist().inv_cdf(p)
+
+
+def remove_clusters(del_idx: np.ndarray, labels: np.ndarray, remove_chance: float, rng):
+    """The seeded coin per cluster of registration_node.py:740-778.  ``labels`` are the cluster labels of the rows ``del_idx``.  Noise
+    rows (label -1) leave the deletion set (RN:740-741).  Then, for ``label in range(labels.max() + 1)`` IN THAT ORDER, one
+    ``rng.standard_normal()`` per label is compared with ``norm.ppf(remove_chance)``: a draw above the threshold takes the cluster out
+    of the deletion set, i.e. keeps it in the map (RN:769-776).  ``rng`` is anything with ``standard_normal()``
+    (``np.random.RandomState``, ``np.random.Generator``).  The threshold is ``scipy.stats.norm.ppf`` where scipy imports and
+    ``statistics.NormalDist().inv_cdf`` otherwise (with -inf / +inf for a chance of 0 / 1, as scipy gives them).  Returns
+    ``(del_idx, keep_idx)``: the rows that remain in the deletion set and, in their input order, the given rows that stay in the map
+    (noise and kept clusters); the ``keep_idx`` of RN:777-778 over the whole map needs its size: ``filter_map_clusters`` returns it.
+
+    Deviation: with no cluster at all the reference fails on ``max()`` of an empty array; here nothing is drawn and nothing remains."""
+    del_idx, labels = np.asarray(del_idx), np.asarray(labels)
+    if del_idx.shape != labels.shape:
+        raise ValueError(f"{len(del_idx)} rows but {len(labels)} labels")
+    given = del_idx
+    del_idx, labels = del_idx[labels != -1], labels[labels != -1]
+    if len(labels) == 0:
+        return del_idx, given
+    threshold = _norm_ppf(float(remove_chance))
+    for label in range(int(labels.max()) + 1):
+        if rng.standard_normal() > threshold:
+            del_idx, labels = del_idx[labels != label], labels[labels != label]
+    return del_idx, given[~np.isin(given, del_idx)]
+
+
+def filter_map_clusters(local_map_xyz: np.ndarray, del_idx: np.ndarray, remove_chance: float, rng, min_cluster_size: int = 100,
+                        min_samples: int = 25):
+    """registration_node.py:704-778 in one call: ``grow_deletion_set``, then ``HDBSCAN(100, 25)`` on the grown set's float32
+    coordinates (vfmreg.clustering: exact, on the GPU), then ``remove_clusters``.  Starts from ``del_idx`` as ``grow_deletion_set``
+    does: the colour gate in front (RN:694-702) is a choice of colours on a projection with a sign-ambiguous SVD and stays with the
+    caller.  Returns ``(del_idx, keep_idx)`` as RN:777-778 leave them."""
+    from .clustering import HDBSCAN
+    xyz = np.asarray(local_map_xyz)[:, :3]
+    grown, _ = grow_deletion_set(xyz, del_idx)
+    labels = HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples).fit_predict(xyz[grown].astype(np.float32))
+    removed, _ = remove_clusters(grown, labels, remove_chance, rng)
+    return removed, _rows_without(xyz.shape[0], removed)
