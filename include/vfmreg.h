@@ -61,6 +61,8 @@ const char *vfm_build_info(void);
  *                        round 6: one read, a tile's fp16 copy in registers); 44 = prep_once_kernel as a persistent grid (two workgroups
  *                        per compute unit, the next group's loads under a group's second pass: the same bytes as 43); 50 / 51 = chunk-major rescan as long-lived (default) / short
  *                        workgroups; 60 / 61 = the rescan gathers its queries from the int8 fragment tiles / the row-major int8 scan (default)
+ *   "mx6_tune"           (A/B) bits of the fp6 coarse kernel: 1 = s_setprio 1 for waves 4 - 7; 2 = a ring of five steps (headline shape); 4 = 32-query
+ *                        sets past the end of the scan are multiplied as copies of tile 0, as before (default: such sets do no matrix work)
  *   "match_stats"        1: the searches collect the counters vfm_debug_match_stats reads (they cost same-address atomics)
  *   "i8_min_queries"     the gated family takes the int8 pass for more than this many query rows (default 0: always)
  *   "prep_grid"          workgroups of prep_chunk_kernel: -1 (default) one per 128-row group, 0 one per compute unit, n > 0; of the

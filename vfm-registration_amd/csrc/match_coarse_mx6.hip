@@ -187,7 +187,19 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
             if (k < my_pieces) issue_piece(k, slot_byte);
     };
 
-    // ---- the wave's queries (two 32-query tiles of the same image layout) and the per-query terms of the bounds
+    // Query tiles past the end of the scan (the last query block's: nqb x 8 NS slots for nq_tiles tiles) are ABSENT.  A wave's present
+    // sets are a prefix of its NS, their number is wave-uniform and constant over the launch: the rest of the wave's work exists once
+    // per count (run_sets) and a wave takes the copy that loads, multiplies, folds and emits its present sets only -- the copy for NS
+    // is the kernel as it always was.  A wave with none still stages its pieces, fills the table and meets every barrier.  (A/B,
+    // "mx6_tune" bit 2: an absent set is a second copy of tile 0, multiplied and thrown away, as before.)
+    // (Not the d = 256 half-width best-score form: it sits at exactly 128 registers, two workgroups per compute unit, and the copies cost it two.)
+    constexpr bool SKIP_ABSENT = !(KS6 == 2 && KIND == MX6_BEST);
+    int np = a.nq_tiles - qt0;
+    np = (!SKIP_ABSENT || (a.tune & 4)) ? NS : (np < 0 ? 0 : (np > NS ? NS : np));
+    auto run_sets = [&](auto NPc) __attribute__((always_inline)) {   // (its body keeps the kernel's indentation)
+    constexpr int NP = decltype(NPc)::value;               // this wave's present query sets: 0 .. NS
+
+    // ---- the wave's queries (NP 32-query tiles of the same image layout) and the per-query terms of the bounds
     Mx6Frag qf[NS][KS6];
     uint2 qs[NS];
     float fx_A[NS], fx_mult[NS], fx_low[NS], fx_rq[NS];
@@ -196,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
     unsigned livemask[NS] = {};   // FUSE: the set's queries that exist and are not zero rows, one bit per query of the tile
     const unsigned char* qimg = reinterpret_cast<const unsigned char*>(a.Qh);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) {
+    for (int j = 0; j < NP; ++j) {
         const int qt = qt0 + j < a.nq_tiles ? qt0 + j : 0;
         const unsigned char* qtile = qimg + (size_t)qt * IMG_TB;
 #pragma unroll
@@ -245,9 +257,9 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
     auto next_thr = [&]() __attribute__((always_inline)) {
         if constexpr (FUSE) {
 #pragma unroll
-            for (int j = 0; j < NS; ++j) thr[j] = ((a.gate - 1.0e-6f) - (fx_A[j] + fx_mult[j] * tab.x)) - (fx_rq[j] * tab.y + 1.0e-6f);
+            for (int j = 0; j < NP; ++j) thr[j] = ((a.gate - 1.0e-6f) - (fx_A[j] + fx_mult[j] * tab.x)) - (fx_rq[j] * tab.y + 1.0e-6f);
 #pragma unroll
-            for (int j = 0; j < NS; ++j) asm volatile("" ::"v"(thr[j]));
+            for (int j = 0; j < NP; ++j) asm volatile("" ::"v"(thr[j]));
         }
     };
     auto emit_chunk = [&](int ci) __attribute__((always_inline)) {  // ci = chunk of the unit, < 0: nothing folded yet
@@ -265,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
             unsigned m[NS];
             unsigned many = 0u;
 #pragma unroll
-            for (int j = 0; j < NS; ++j) {
+            for (int j = 0; j < NP; ++j) {
                 const unsigned long long hit = __ballot(!(s1[j] < thr[j]));
                 m[j] = ((unsigned)hit | (unsigned)(hit >> 32)) & livemask[j];
                 many |= m[j];
@@ -278,7 +290,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
                 // (a list that has overflowed -- descriptors that are all alike -- takes no more entries: the search's guard goes up at
                 // the end of the workgroup and match_gatepass_kernel decides every query; `seen` is a chunk old, the cap is exact)
 #pragma unroll
-                for (int j = 0; j < NS; ++j)
+                for (int j = 0; j < NP; ++j)
                     if (lane < 32 && ((m[j] >> lane) & 1u) && seen < (unsigned)LCAP) {
                         const unsigned pos = atomicAdd(&llist[0], 1u);
                         if (pos < (unsigned)LCAP) llist[1 + pos] = ((unsigned)ci << (NS == 2 ? 9 : 10)) | (unsigned)((wave * NS + j) * 32 + lane);
@@ -286,7 +298,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
             }
         }
 #pragma unroll
-        for (int j = 0; j < NS; ++j) {
+        for (int j = 0; j < NP; ++j) {
             if constexpr (FUSE) continue;
             unsigned best;
             if constexpr (TOP2) {
@@ -334,7 +346,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
 
     floatx16 accA[NS], accB[NS];
 #pragma unroll
-    for (int j = 0; j < NS; ++j)
+    for (int j = 0; j < NP; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) accA[j][r] = accB[j][r] = TOP2 ? 0.0f : -__builtin_inff();   // (folded by the first tile: no effect)
 
@@ -344,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
     // everything the loop reads from registers is here before it starts: the compiler puts its own s_waitcnt vmcnt(0) in front of the
     // first use of a loaded value, and inside the loop that would wait for every piece in flight, step after step
 #pragma unroll
-    for (int j = 0; j < NS; ++j) {
+    for (int j = 0; j < NP; ++j) {
         asm volatile("" ::"v"(fx_A[j]), "v"(fx_mult[j]), "v"(fx_rq[j]), "v"(qs[j].x), "v"(qs[j].y), "v"((int)live[j]));
 #pragma unroll
         for (int s = 0; s < KS6; ++s) asm volatile("" ::"v"(qf[j][s].c[0]), "v"(qf[j][s].c[1]), "v"(qf[j][s].c[2]), "v"(qf[j][s].c[3]), "v"(qf[j][s].c[4]), "v"(qf[j][s].c[5]));
@@ -407,15 +419,15 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
 #pragma unroll
                     for (int r = 0; r < 16; ++r) zero[r] = ACC0;
 #pragma unroll
-                    for (int j = 0; j < NS; ++j) acc[j] = mfma_mx6<s>(fr[s % PF], sc_cur, qf[j][s], qs[j], zero);
+                    for (int j = 0; j < NP; ++j) acc[j] = mfma_mx6<s>(fr[s % PF], sc_cur, qf[j][s], qs[j], zero);
                 } else {
 #pragma unroll
-                    for (int j = 0; j < NS; ++j) acc[j] = mfma_mx6<s>(fr[s % PF], sc_cur, qf[j][s], qs[j], acc[j]);
+                    for (int j = 0; j < NP; ++j) acc[j] = mfma_mx6<s>(fr[s % PF], sc_cur, qf[j][s], qs[j], acc[j]);
                 }
                 // (an empty use of the results: without it the MFMAs -- pure functions to the compiler -- are sunk across the
                 // blocks of the step to their first reader, the fold one tile later)
 #pragma unroll
-                for (int j = 0; j < NS; ++j) asm volatile("" ::"v"(acc[j]));
+                for (int j = 0; j < NP; ++j) asm volatile("" ::"v"(acc[j]));
 #ifndef VFM_ABL_NOLDS
                 fr[s % PF] = (s + PF < KS6) ? mx6_frag(la0 + tb, lb0 + tb, s + PF) : mx6_frag(la0 + tn, lb0 + tn, s + PF - KS6);
 #else
@@ -441,14 +453,14 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
                 if constexpr (s == 0 && (J & 3) == 3) next_thr();
 #ifndef VFM_ABL_NOFOLD
 #pragma unroll
-                for (int e = s * (16 * NS) / KS6; e < (s + 1) * (16 * NS) / KS6; ++e) {   // `done` is tile (J + 3) & 3 of its chunk
+                for (int e = s * (16 * NP) / KS6; e < (s + 1) * (16 * NP) / KS6; ++e) {   // `done` is tile (J + 3) & 3 of its chunk
                     if constexpr (TOP2) coarse_fold(t1[e >> 4], t2[e >> 4], done[e >> 4][e & 15], ((J + 3) & 3) * 16 + (e & 15));
                     else s1[e >> 4] = fmaxf(s1[e >> 4], done[e >> 4][e & 15]);
                 }
 #else
                 if (s == 0) {
 #pragma unroll
-                    for (int j = 0; j < NS; ++j) s1[j] = fmaxf(s1[j], done[j][0]);
+                    for (int j = 0; j < NP; ++j) s1[j] = fmaxf(s1[j], done[j][0]);
                 }
 #endif
                 // (the same for the fold: the running maxima are read at the end of the chunk only, and the compiler had moved the
@@ -457,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
                 if constexpr (TOP2) asm volatile("" ::"v"(t1[0]), "v"(t1[1]), "v"(t2[0]), "v"(t2[1]));
                 else {
 #pragma unroll
-                    for (int j = 0; j < NS; ++j) asm volatile("" ::"v"(s1[j]));
+                    for (int j = 0; j < NP; ++j) asm volatile("" ::"v"(s1[j]));
                 }
                 // one 1 KiB piece per k-step slot of the window: the last tile of the step carries slots 0 .. KS6 - 1, tile J of the
                 // next step slots KS6 (J + 1) ..
@@ -508,7 +520,7 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
         ring = ring1;
     }
 #pragma unroll
-    for (int e = 0; e < 16 * NS; ++e) {
+    for (int e = 0; e < 16 * NP; ++e) {
         if constexpr (TOP2) coarse_fold(t1[e >> 4], t2[e >> 4], accB[e >> 4][e & 15], 3 * 16 + (e & 15));
         else s1[e >> 4] = fmaxf(s1[e >> 4], accB[e >> 4][e & 15]);
     }
@@ -516,13 +528,18 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
     emit_chunk(nch - 1);
     if constexpr (LOW) {
 #pragma unroll
-        for (int j = 0; j < NS; ++j)
+        for (int j = 0; j < NP; ++j)
             if (lane < 32 && qt0 + j < a.nq_tiles) {
                 atomicMax(a.qmax + (size_t)(qt0 + j) * 32 + lane, float_key(fx_low[j]));
                 if (a.qbest && fx_low[j] > -__builtin_inff())
                     atomicMax(a.qbest + (size_t)(qt0 + j) * 32 + lane, ((unsigned long long)float_key(fx_low[j]) << 32) | (unsigned)fx_arg[j]);
             }
     }
+    };
+    if (!SKIP_ABSENT || np == NS) run_sets(std::integral_constant<int, NS>{});
+    else if (NS == 3 && np == 2) run_sets(std::integral_constant<int, SKIP_ABSENT && NS == 3 ? 2 : NS>{});
+    else if (np == 1) run_sets(std::integral_constant<int, SKIP_ABSENT ? 1 : NS>{});
+    else run_sets(std::integral_constant<int, SKIP_ABSENT ? 0 : NS>{});
     if constexpr (FUSE) {
         // the workgroup's list -> its slot of the survivor buffer: [count, query block, first chunk, -][entries]; plain stores
         __syncthreads();
