@@ -56,8 +56,8 @@ const char *vfm_build_info(void);
  *                        records; 5 = the fp16 pass in the gated family too; 7 = 5 without seed units; 12 / 10 = int8 kernel with 32 resident
  *                        queries per wave (10: two tiles per step); 20 = general selection kernel on best-score records; 21 = no chunk-major
  *                        rescan; 30 / 31 = fused fp6 half-width kernel with one (default) / two chunks per barrier; 32 / 33 = ... with two /
- *                        three (default) 32-query tiles per wave at d = 384; 40 / 41 / 42 / 43 = fp6 operand preparation by prep_chunk_kernel
- *                        (a 128-row group in registers) / prep_stream_kernel (rows read twice) / by width / prep_once_kernel (default since
+ *                        three (default) 32-query tiles per wave at d = 384; 40 / 41 / 43 = fp6 operand preparation by prep_chunk_kernel
+ *                        (a 128-row group in registers) / prep_stream_kernel (rows read twice) / prep_once_kernel (default since
  *                        round 6: one read, a tile's fp16 copy in registers); 44 = prep_once_kernel as a persistent grid (two workgroups
  *                        per compute unit, the next group's loads under a group's second pass: the same bytes as 43); 50 / 51 = chunk-major rescan as long-lived (default) / short
  *                        workgroups; 60 / 61 = the rescan gathers its queries from the int8 fragment tiles / the row-major int8 scan (default)
@@ -89,7 +89,7 @@ const char *vfm_build_info(void);
  *                        vfm_vit_forward's policy -- from two rounds of workgroups on (~150 images per call) when the last round is at least four
  *                        fifths full: a single round runs in lockstep and ends level with the two kernels --, n > 0
  *                        from n images per call on, -1 never
- *   and the single fields behind the codes: "coarse_qsets", "seed_units", "select_variant", "mx6_t4", "mx6_ns3", "prep_form" (0 .. 3),
+ *   and the single fields behind the codes: "coarse_qsets", "seed_units", "select_variant", "mx6_t4", "mx6_ns3", "prep_form" (0, 1, 3, 4),
  *   "finish_short", "rescan_rows", "vit_*", "voxel_replay2", "voxel_one_launch", "voxel_trace", "voxel_grid_ppt" (vfm_config_get reads these;
  *   cfg == NULL there: what the calling thread's entry points would read now). */
 typedef struct vfm_config vfm_config_t;

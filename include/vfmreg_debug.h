@@ -11,6 +11,8 @@
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows  read-backs for tests; they synchronise the device.
+ *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
+ *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
  */
 #ifndef VFMREG_DEBUG_H
 #define VFMREG_DEBUG_H
@@ -28,6 +30,16 @@ int vfm_prof_events_create(void **start, void **stop);
 int vfm_prof_arm(void *start, void *stop);
 int vfm_prof_elapsed_ms(void *start, void *stop, float *ms_host);
 int vfm_prof_events_destroy(void *start, void *stop);
+
+/* tests: which coarse kernel ran.  Every launcher instantiation of csrc/match_coarse_*.hip has a name spelled from its template arguments
+ * ("i8q2<12,top2=0,low=0,fused=0>", "mx6q2<3,FUSE,low=0,img=6,ring=5,T=4,NS=3>", "pipe<24,sparse>+seed": the sparse fp16 kernel launched with
+ * seed units) and notes it, per thread, when it launches.  vfm_debug_last_coarse_kernel: the name noted last by the calling thread -- the
+ * Euclidean entry points launch one kernel per direction, the reverse direction last -- or "" if it has launched none.
+ * vfm_debug_coarse_kernel_names: every name the library's launchers can note, sorted, separated by '\n'; the list is put together by the
+ * instantiations themselves while the library is loaded.  Both write a NUL-terminated string to buf_host[cap] (VFM_EINVAL if it does not
+ * fit) and do not touch the device. */
+int vfm_debug_last_coarse_kernel(char *buf_host, int cap);
+int vfm_debug_coarse_kernel_names(char *buf_host, int cap);
 
 /* counters of the last FAST search that used workspace `ws` (candidate histogram, refined / fallback queries;
  * see csrc/match_finish.hip).  out64_host: HOST int32[64].  Synchronises the device. */

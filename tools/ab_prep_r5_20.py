@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The driver's form (20 timed steps behind 3 warm-up steps) and 200 steps, headline mode: fp6 operand preparation as the stream
-form (41) / the one-pass form (40) / by width (42), alternating on one box."""
+form (41) / the one-pass form (40), alternating on one box."""
 import sys
 from pathlib import Path
 

@@ -46,7 +46,7 @@ const Field k_fields[] = {
 void set_coarse_variant(VfmConfig& c, int v) {
     if (v == 60 || v == 61) { c.rescan_rows = v == 61 ? 1 : 0; return; }
     if (v == 50 || v == 51) { c.finish_short = v == 51 ? 1 : 0; return; }
-    if (v >= 40 && v <= 44) { c.prep_stream = v == 44 ? 4 : v == 43 ? 3 : v == 42 ? 2 : v == 41 ? 1 : 0; return; }
+    if (v >= 40 && v <= 44) { c.prep_stream = v == 44 ? 4 : v == 43 ? 3 : v == 41 ? 1 : 0; return; }
     if (v == 32 || v == 33) { c.mx6_ns3 = v == 33 ? 1 : 0; return; }
     if (v == 30 || v == 31) { c.mx6_t4 = v == 30 ? 1 : 0; return; }
     c.seed_units = v == 7 ? 0 : 1;
@@ -104,6 +104,9 @@ VFM_EXPORT int vfm_config_use(const vfm_config_t* cfg) {
 }
 VFM_EXPORT int vfm_config_set(vfm_config_t* cfg, const char* key, int64_t value) {
     VFM_CHECK_ARG(cfg && key, "config_set: null pointer");
+    // (the by-width choice between the two older preparation forms is gone: DESIGN.md R5.10)
+    if ((!strcmp(key, "coarse_variant") && value == 42) || (!strcmp(key, "prep_form") && value == 2))
+        return vfm_fail(VFM_EINVAL, "config_set: %s %lld (fp6 operand preparation by width) has been removed", key, (long long)value);
     if (!strcmp(key, "coarse_variant")) { set_coarse_variant(cfg->c, (int)value); return VFM_OK; }
     if (!strcmp(key, "voxel_small")) { set_voxel_small(cfg->c, (int)value); return VFM_OK; }
     if (!strcmp(key, "vit_gemm")) { set_vit_gemm(cfg->c, (int)(value >> 32), (int)(int32_t)(uint32_t)(value & 0xffffffffll)); return VFM_OK; }

@@ -3,6 +3,12 @@
 // profiling hook.  Kernels: match_prep.hip, match_coarse_f16.hip, match_coarse_i8.hip, match_finish.hip, match_l2.hip.
 #include "match_internal.h"
 
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
 namespace vfmm {
 
 
@@ -40,6 +46,20 @@ int choose_slices(int nqb, int nchunks) {
 
 // profiling hook (vfm_prof_arm): events recorded around the next coarse launch on this thread
 thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
+
+// the launcher instantiations' names (match_internal.h, CoarseKernelName): a list the objects link themselves into while the library is
+// loaded (the head is constant-initialised, so it is there before any of them is constructed), and the calling thread's last launch
+static const CoarseKernelName* g_coarse_kernel_names = nullptr;
+thread_local const CoarseKernelName* g_last_coarse_kernel = nullptr;
+
+CoarseKernelName::CoarseKernelName(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof(name), fmt, ap);
+    va_end(ap);
+    next = g_coarse_kernel_names;
+    g_coarse_kernel_names = this;
+}
 
 // 0 = default (pipelined kernel for d <= 384); 1 = match_coarse_kernel<.,1>; 2 = match_coarse_kernel<.,2>;
 // set through vfm_debug_set_coarse_variant for A/B runs
@@ -502,6 +522,26 @@ VFM_EXPORT int vfm_debug_mx6_half_err(const void* prepared, int64_t rows, int d,
 
 
 
+
+// The coarse kernel most recently launched from the calling thread, as its launcher instantiation spells itself ("" if none), and the
+// sorted, newline-separated list of every such name in the library.  Host memory only.
+static int copy_out(const std::string& s, char* buf_host, int cap, const char* what) {
+    VFM_CHECK_ARG(buf_host && cap > 0, "%s: null buffer", what);
+    if ((size_t)cap <= s.size()) return vfm_fail(VFM_EINVAL, "%s: the buffer holds %d bytes, the answer needs %zu", what, cap, s.size() + 1);
+    memcpy(buf_host, s.c_str(), s.size() + 1);
+    return VFM_OK;
+}
+VFM_EXPORT int vfm_debug_last_coarse_kernel(char* buf_host, int cap) {
+    return copy_out(g_last_coarse_kernel ? g_last_coarse_kernel->name : "", buf_host, cap, "last_coarse_kernel");
+}
+VFM_EXPORT int vfm_debug_coarse_kernel_names(char* buf_host, int cap) {
+    std::vector<std::string> names;
+    for (const CoarseKernelName* e = g_coarse_kernel_names; e; e = e->next) names.push_back(e->name);
+    std::sort(names.begin(), names.end());
+    std::string all;
+    for (const std::string& s : names) all += (all.empty() ? "" : "\n") + s;
+    return copy_out(all, buf_host, cap, "coarse_kernel_names");
+}
 
 VFM_EXPORT int vfm_prof_events_create(void** start, void** stop) {
     VFM_CHECK_ARG(start && stop, "prof: null pointer");

@@ -586,8 +586,23 @@ __global__ __launch_bounds__(256, 1) void match_coarse_r_kernel(CoarseArgs a) {
 
 }  // namespace
 
+// the launchers' names (match_internal.h, CoarseKernelName).  The sparse pipelined kernel has two: with and without seed units at the head
+// of its grid (a launch argument, not a template one -- but a different grid and a different first round)
+template <int KSTEPS, bool SPARSE>
+CoarseKernelName k_pipe_name{"pipe<%d,%s>", KSTEPS, SPARSE ? "sparse" : "dense"};
+template <int KSTEPS>
+CoarseKernelName k_pipe_seeded_name{"pipe<%d,sparse>+seed", KSTEPS};
+template <int KSTEPS, int QSETS>
+CoarseKernelName k_v_name{"v<%d,qsets=%d>", KSTEPS, QSETS};
+template <int KSTEPS, int QSETS, int NBUF, bool BIAS>
+CoarseKernelName k_r_name{"r<%d,qsets=%d,nbuf=%d,bias=%d>", KSTEPS, QSETS, NBUF, (int)BIAS};
+
 template <int KSTEPS, bool SPARSE>
 int launch_coarse_pipe(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_pipe_name<KSTEPS, SPARSE>;
+    if constexpr (SPARSE) {
+        if (a.nseed_pad) g_last_coarse_kernel = &k_pipe_seeded_name<KSTEPS>;
+    }
     const int lds = 6 * KSTEPS * 1024 + (SPARSE ? SPARSE_LREC_CAP * 8 + 16 : 0);
     static unsigned long long attr_set = 0ull;  // one bit per device
     if (!attr_done(attr_set)) {
@@ -601,6 +616,7 @@ int launch_coarse_pipe(const CoarseArgs& a, hipStream_t st) {
 
 template <int KSTEPS, int QSETS>
 int launch_coarse_v(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_v_name<KSTEPS, QSETS>;
     const int lds = ring_depth(KSTEPS) * KSTEPS * 1024;
     static unsigned long long attr_set = 0ull;  // one bit per device
     if (!attr_done(attr_set)) {
@@ -614,6 +630,7 @@ int launch_coarse_v(const CoarseArgs& a, hipStream_t st) {
 
 template <int KSTEPS, int QSETS, int NBUF, bool BIAS>
 int launch_coarse_r(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_r_name<KSTEPS, QSETS, NBUF, BIAS>;
     const int lds = NBUF * KSTEPS * 1024;
     static unsigned long long attr_set = 0ull;  // one bit per device
     if (!attr_done(attr_set)) {

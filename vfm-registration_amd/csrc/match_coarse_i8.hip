@@ -359,8 +359,15 @@ __global__ __launch_bounds__(512, 2) void match_coarse_i8q2_kernel(CoarseArgs a)
 
 }  // namespace
 
+// the launchers' names (match_internal.h, CoarseKernelName)
+template <int KSTEPS, int T, bool TOP2, bool LOW>
+CoarseKernelName k_i8_name{"i8<%d,T=%d,top2=%d,low=%d>", KSTEPS, T, (int)TOP2, (int)LOW};
+template <int KSTEPS, bool TOP2, bool LOW, bool FUSE>
+CoarseKernelName k_i8q2_name{"i8q2<%d,top2=%d,low=%d,fused=%d>", KSTEPS, (int)TOP2, (int)LOW, (int)FUSE};
+
 template <int KSTEPS, int T, bool TOP2 = false, bool LOW = true>
 int launch_coarse_i8(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_i8_name<KSTEPS, T, TOP2, LOW>;
     const int lds = 3 * T * KSTEPS * 1024;
     static unsigned long long attr_set = 0ull;  // one bit per device
     if (!attr_done(attr_set)) {
@@ -374,6 +381,7 @@ int launch_coarse_i8(const CoarseArgs& a, hipStream_t st) {
 
 template <int KSTEPS, bool TOP2, bool LOW = true, bool FUSE = false>
 int launch_coarse_i8q2(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_i8q2_name<KSTEPS, TOP2, LOW, FUSE>;
     const int lds = 12 * KSTEPS * 1024;
     static unsigned long long attr_set = 0ull;  // one bit per device
     if (!attr_done(attr_set)) {

@@ -559,8 +559,14 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
 #endif   // __HIP_DEVICE_COMPILE__
 }
 
+// the launcher's names (match_internal.h, CoarseKernelName)
+template <int KS6, int KIND, bool LOW, int IMG_KS6, int RING, int T, int NS>
+CoarseKernelName k_mx6q2_name{"mx6q2<%d,%s,low=%d,img=%d,ring=%d,T=%d,NS=%d>", KS6, KIND == MX6_FUSE ? "FUSE" : KIND == MX6_TOP2 ? "TOP2" : "BEST",
+                              (int)LOW, IMG_KS6, RING, T, NS};
+
 template <int KS6, int KIND, bool LOW, int IMG_KS6, int RING, int T = 4, int NS = 2>
 int launch_mx6q2(const CoarseArgs& a, hipStream_t st) {
+    g_last_coarse_kernel = &k_mx6q2_name<KS6, KIND, LOW, IMG_KS6, RING, T, NS>;
     constexpr int LT = MX6_SCALE_PLANE + KS6 * MX6_KSTEP_BYTES;
     constexpr int LCAP = RING * T * LT + MX6_LTAB * 8 + (MX6_LCAP + 1) * 4 <= 160 * 1024 ? MX6_LCAP : 1023;
     const int lds = RING * T * LT + MX6_LTAB * 8 + (KIND == MX6_FUSE ? (LCAP + 1) * 4 : 0);

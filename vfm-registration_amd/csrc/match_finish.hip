@@ -1990,7 +1990,11 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
         const bool top2 = i8 && (records == VFM_RECORDS_TOP2 || records == VFM_RECORDS_MX6_TOP2);
         if (mx6) records = top2 ? VFM_RECORDS_TOP2 : VFM_RECORDS_BEST;
         const bool best = i8 && records == VFM_RECORDS_BEST && vfm_cfg().select_variant != 1;
-        use_bins = (best || half) && vfm_cfg().select_variant != 2 && n >= 4 * (int64_t)a.nchunks;
+        // (the fused kinds have no choice: their coarse kernel -- or match_bin_survivors_kernel below -- has filed the survivors in the
+        // bins already, and a search that does not rescan the bins reports every one of those queries as below the gate.  That was
+        // the case under "coarse_variant" 21, and at factory settings where effective_records -- which counts the chunks that hold
+        // rows -- keeps the fused kind and the padded chunk count below, one larger when that count is odd, says n < 4 nchunks.)
+        use_bins = fused || ((best || half) && vfm_cfg().select_variant != 2 && n >= 4 * (int64_t)a.nchunks);
         if (pilot && use_bins) {
             // the pilot rescan: one chunk per query, scored exactly on the int8 image, raises qmax (match_rescan_chunk_kernel, pilot
             // branch); the bins it used are emptied again for the selection

@@ -582,6 +582,18 @@ struct Rows {
 // experiment knobs and profiling hook (match_api.hip)
 extern thread_local hipEvent_t g_prof_start, g_prof_stop;  // vfm_prof_arm: events around the next coarse launch of this thread
 
+// Which coarse kernel a search ran (include/vfmreg_debug.h: vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names).  Every launcher
+// template of match_coarse_*.hip owns one CoarseKernelName per instantiation -- a variable template beside it, spelled from its template
+// arguments -- and stores its address on every launch: using the variable is what instantiates it, and its constructor (run when the
+// library is loaded) links it into the list the second function prints.  So the list is the set of launcher instantiations in the
+// binary, by construction.  Host side only: one thread-local pointer store per launch, nothing in CoarseArgs, nothing on the device.
+struct CoarseKernelName {
+    char name[56];
+    const CoarseKernelName* next;
+    explicit CoarseKernelName(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+};
+extern thread_local const CoarseKernelName* g_last_coarse_kernel;
+
 // which coarse pass / record kind a search takes (match_api.hip)
 bool use_sparse(int d, int64_t n, int64_t m);
 bool use_i8(int d, int64_t n, int64_t m, bool gated);

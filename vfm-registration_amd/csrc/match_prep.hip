@@ -1521,15 +1521,15 @@ int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows
         int pg = prep_grid(groups, grid_mode);
         const dim3 grid((unsigned)pg), block(1024);
         if (want_mx6) {   // int8 + fp6 images from one read of the rows; the fp16 image, if wanted, by its own kernel
-            // Which form (vfm_cfg().prep_stream, "coarse_variant" 40 .. 44).  Default since round 6: prep_once_kernel (3) -- one read of the
+            // Which form (vfm_cfg().prep_stream, "coarse_variant" 40, 41, 43, 44).  Default since round 6: prep_once_kernel (3) -- one read of the
             // rows, the fp16 copy of a wave's tile in registers, two short workgroups per compute unit; 4 is the same kernel as a persistent
             // grid with the next group's loads under a group's second pass.  Both take d = 256 / 384 in fp32 rows; everything else -- and
-            // the older forms when asked for -- goes on as before: prep_stream_kernel (1; 2 = at d = 256 only) was built to run BESIDE a
+            // the older forms when asked for -- goes on as before: prep_stream_kernel (1) was built to run BESIDE a
             // coarse workgroup of round 4 (332 of a SIMD's 512 registers, 90 KiB) and reads every row twice; prep_chunk_kernel (0) holds
             // a group in the registers of 8 fat waves, one workgroup per compute unit.  Since round 5 nothing runs beside a d = 384 coarse
             // workgroup (444 registers per SIMD), so a preparation form is judged by its own work: tools/ab_prep_r5.py, ab_prep_r6.py,
             // DESIGN.md R6.2 and the section on the persistent form.
-            const bool stream_form = vfm_cfg().prep_stream == 1 || (vfm_cfg().prep_stream == 2 && d == 256);
+            const bool stream_form = vfm_cfg().prep_stream == 1;
             if ((vfm_cfg().prep_stream == 3 || vfm_cfg().prep_stream == 4) && (d == 384 || d == 256) && !any_f16) {
                 const bool persist = vfm_cfg().prep_stream == 4;
                 const dim3 sg((unsigned)(persist ? prep_persist_grid(groups, st) : groups)), sb(256);

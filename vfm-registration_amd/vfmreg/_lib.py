@@ -127,6 +127,8 @@ DEBUG_SIGNATURES = {
     "vfm_prof_arm": (C.c_int, [c_vp, c_vp]),
     "vfm_prof_elapsed_ms": (C.c_int, [c_vp, c_vp, C.POINTER(C.c_float)]),
     "vfm_prof_events_destroy": (C.c_int, [c_vp, c_vp]),
+    "vfm_debug_last_coarse_kernel": (C.c_int, [C.c_char_p, C.c_int]),
+    "vfm_debug_coarse_kernel_names": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_match_stats": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "vfm_debug_i8_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_mx6_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp]),
@@ -259,6 +261,20 @@ def _install_tool_names(lib) -> None:
         thread_config().set_vit_gemm(narrow, wide)
         return 0
     lib.vfm_debug_set_vit_gemm = vit_gemm
+
+
+def last_coarse_kernel() -> str:
+    """The coarse kernel the calling thread's last search launched (include/vfmreg_debug.h), "" if none."""
+    buf = C.create_string_buffer(256)
+    check(load().vfm_debug_last_coarse_kernel(buf, len(buf)), "last_coarse_kernel")
+    return buf.value.decode()
+
+
+def coarse_kernel_names() -> list:
+    """Every name ``last_coarse_kernel`` can return: one per launcher instantiation in the library, sorted."""
+    buf = C.create_string_buffer(1 << 14)
+    check(load().vfm_debug_coarse_kernel_names(buf, len(buf)), "coarse_kernel_names")
+    return buf.value.decode().split("\n") if buf.value else []
 
 
 def check(rc: int, what: str = "") -> None:
