@@ -10,7 +10,7 @@
  *   - (until round 5 this header also held vfm_debug_set_*: PROCESS-GLOBAL A/B switches.  They are gone: kernel policy is a caller-owned
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
- *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows  read-backs for tests; they synchronise the device.
+ *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
  */
@@ -61,6 +61,26 @@ int vfm_debug_mx6_half_err(const void *prepared, int64_t rows, int d, float *err
 /* tests / bench: what the last vfm_ransac_corr in `ws` (same c_max, n_iter) did: out_host[0] = hypotheses scored in fp64 from the candidate
  * list, [1] = the list overflowed (every hypothesis scored in fp64), [2] = the point-wise fp32 pass was needed.  Synchronises. */
 int vfm_debug_ransac_counts(const void *ws, int64_t c_max, int32_t n_iter, int32_t *out_host);
+/* tests: everything the last vfm_ransac_corr in `ws` (same c_max, n_iter) left there, copied to HOST buffers; any of them may be NULL.
+ * Reads only; synchronises the device.
+ *   n_lo / n_hi / r_lo / r_hi [n_iter]   the bounds of every hypothesis (n_hi < 0: degenerate sample, or fewer than 3 correspondences),
+ *                                        from the point-wise fp32 pass if sel[3] is set, else from the closed-form moment pass
+ *   sel [4]                              F (max n_lo), count, overflow, unsure; *rstar = R* (min r_hi over n_lo = n_hi = F; +inf if none).
+ *                                        count: the hypotheses the bounds could not rule out, NOT clamped to the list's capacity
+ *   list [VFM_DEBUG_RANSAC_CAND_MAX]     the first min(count, CAND_MAX) survivors in the order they were appended (no particular order)
+ *   fit / rmse / hyp [CAND_MAX + nblocks], nblocks = (n_iter + 63) / 64: the exact fp64 scores, hyp = -1 for an empty slot (fit = rmse = 0:
+ *                                        nothing scored there, a degenerate sample, or a hypothesis without a single inlier)
+ * Which slots a call fills depends on the chain ("ransac_fused"):
+ *   2 (default), 0   list: yes.  Slot k < CAND_MAX: the score of list[k] for k < count, empty for k >= count -- and ALL CAND_MAX slots are
+ *                    empty when the list overflowed.  Slot CAND_MAX + b: empty unless the list overflowed; then the best of hypotheses
+ *                    [64 b, 64 b + 64) under (fitness desc, rmse asc, id asc), every one of them scored.
+ *   1                no list (`list` and the slots k < CAND_MAX are not written: they hold what an earlier call left), no capacity and so
+ *                    never an overflow.  Slot CAND_MAX + b: the best of the SURVIVORS among hypotheses [64 b, 64 b + 64), empty if none.
+ *   "ransac_exact_only": slots [0, nblocks) hold the per-block best of all hypotheses; bounds, sel and list are not written. */
+#define VFM_DEBUG_RANSAC_CAND_MAX 2048
+int vfm_debug_ransac_state(const void *ws, int64_t c_max, int32_t n_iter, int32_t *n_lo_host, int32_t *n_hi_host, double *r_lo_host,
+                           double *r_hi_host, int32_t *sel_host, double *rstar_host, int32_t *list_host, double *fit_host,
+                           double *rmse_host, int32_t *hyp_host);
 
 /* tests: where vfm_vit_forward(cfg, ..., B, ...) keeps its buffers inside the caller's workspace, in the order x (fp32 [M][dim] residual
  * stream), a (fp16 fragment tiles: im2col, then the attention output), xh (fp16 fragment copy of x), stats (fp32 [M][dim / 32][2]), h (fp16

@@ -43,7 +43,7 @@ def _stale(target: Path, deps) -> bool:
 def build(force: bool = False, verbose: bool = True) -> Path:
     OUT_DIR.mkdir(parents=True, exist_ok=True)
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
-    headers = list(CSRC.glob("*.h")) + [HERE.parent / "include" / "vfmreg.h"]
+    headers = list(CSRC.glob("*.h")) + [HERE.parent / "include" / h for h in ("vfmreg.h", "vfmreg_debug.h")]
     srcs = [CSRC / s for s in SOURCES if (CSRC / s).exists()]
     objs = [OBJ_DIR / (s.name + ".o") for s in srcs]
     jobs = [(s, o, FILE_FLAGS.get(s.name, [])) for s, o in zip(srcs, objs)]

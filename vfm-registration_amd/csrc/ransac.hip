@@ -17,8 +17,12 @@
 // -> ransac_final_kernel: total order (fitness desc, rmse asc, id asc), pose of the winner; ransac_mask_kernel.
 // Exact arithmetic is fp64, compiled with -ffp-contract=off, written as the exact operation sequence of
 // oracle/vfm_oracle.c so that poses, masks and the winning hypothesis are bit-identical to the oracle's.
-#include <atomic>
+#include <string.h>
 
+#include <atomic>
+#include <vector>
+
+#include "../../include/vfmreg_debug.h"
 #include "common.h"
 
 namespace {
@@ -1268,6 +1272,49 @@ VFM_EXPORT int vfm_debug_ransac_counts(const void* ws, int64_t c_max, int32_t n_
     out_host[0] = h.count < CAND_MAX ? h.count : CAND_MAX;
     out_host[1] = h.overflow;
     out_host[2] = h.unsure;
+    return VFM_OK;
+}
+
+// tests: everything the last vfm_ransac_corr in `ws` left behind (include/vfmreg_debug.h describes which chain fills which slot).
+// Reads only; any destination may be NULL.  Synchronises the device.
+VFM_EXPORT int vfm_debug_ransac_state(const void* ws, int64_t c_max, int32_t n_iter, int32_t* n_lo_host, int32_t* n_hi_host,
+                                      double* r_lo_host, double* r_hi_host, int32_t* sel_host, double* rstar_host, int32_t* list_host,
+                                      double* fit_host, double* rmse_host, int32_t* hyp_host) {
+    static_assert(CAND_MAX == VFM_DEBUG_RANSAC_CAND_MAX, "include/vfmreg_debug.h states the capacity of the candidate list");
+    VFM_CHECK_ARG(ws && c_max >= 0 && n_iter > 0, "ransac_state: bad arguments");
+    RansacWs w = carve_ransac(const_cast<void*>(ws), c_max, n_iter);
+    SelectState s;
+    VFM_CHECK_HIP(hipMemcpy(&s, w.sel, sizeof(s), hipMemcpyDeviceToHost));
+    if (sel_host) {
+        sel_host[0] = s.F;
+        sel_host[1] = s.count;
+        sel_host[2] = s.overflow;
+        sel_host[3] = s.unsure;
+    }
+    if (rstar_host) memcpy(rstar_host, &s.Rbits, sizeof(double));
+    if (n_lo_host || n_hi_host || r_lo_host || r_hi_host) {
+        std::vector<CoarseHyp> hy((size_t)n_iter);
+        VFM_CHECK_HIP(hipMemcpy(hy.data(), w.hyps, sizeof(CoarseHyp) * hy.size(), hipMemcpyDeviceToHost));
+        for (int32_t h = 0; h < n_iter; ++h) {
+            if (n_lo_host) n_lo_host[h] = hy[h].n_lo;
+            if (n_hi_host) n_hi_host[h] = hy[h].n_hi;
+            if (r_lo_host) r_lo_host[h] = hy[h].r_lo;
+            if (r_hi_host) r_hi_host[h] = hy[h].r_hi;
+        }
+    }
+    if (list_host) {
+        const int n = s.count < 0 ? 0 : (s.count < CAND_MAX ? s.count : CAND_MAX);
+        if (n > 0) VFM_CHECK_HIP(hipMemcpy(list_host, w.list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    if (fit_host || rmse_host || hyp_host) {
+        std::vector<HypScore> bb((size_t)CAND_MAX + (size_t)((n_iter + 63) / 64));
+        VFM_CHECK_HIP(hipMemcpy(bb.data(), w.block_best, sizeof(HypScore) * bb.size(), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < bb.size(); ++k) {
+            if (fit_host) fit_host[k] = bb[k].fit;
+            if (rmse_host) rmse_host[k] = bb[k].rmse;
+            if (hyp_host) hyp_host[k] = bb[k].hyp;
+        }
+    }
     return VFM_OK;
 }
 

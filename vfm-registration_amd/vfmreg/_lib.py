@@ -135,6 +135,7 @@ DEBUG_SIGNATURES = {
     "vfm_debug_mx6_half_err": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp]),
     "vfm_debug_voxel_trace": (C.c_int, [c_vp, c_i64, c_vp]),
     "vfm_debug_ransac_counts": (C.c_int, [c_vp, c_i64, C.c_int, c_vp]),
+    "vfm_debug_ransac_state": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_vit_workspace_layout": (C.c_int, [C.POINTER(VitConfig), C.c_int, C.POINTER(c_i64), C.POINTER(c_i64)]),
 }
 
