@@ -187,6 +187,12 @@ int vfm_match_prepare2_gated(const float *x1, int64_t rows1, void *prepared1, co
  *                            correct, slow), and VFM_RECORDS_HALF / _HALF_FUSED / the half-width probe must not be run on it.
  *                            The half-width kinds bound with the image's residual over the columns they multiply either way. */
 #define VFM_PREPARE_MX6_HALF 16
+/*   VFM_PREPARE_NO_I8        flag, valid only together with VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF, d = 256 / 384 and fp32 rows
+ *                            (_prepare2_gated_p and _z; _prepare2_gated_t refuses it): the int8 image is NOT written -- no tiles, no
+ *                            row-major copy of the scan, no err / step data; those regions of the operand keep whatever they held.
+ *                            inv, the fp6 half image with its scales and bounds, rest / grest are the bytes the call writes without
+ *                            the flag.  Such operands serve exactly one search: VFM_RECORDS_MX6_HALF_FUSED | VFM_RECORDS_NO_I8. */
+#define VFM_PREPARE_NO_I8 32
 int vfm_match_prepare2_gated_p(const float *x1, int64_t rows1, void *prepared1, const float *x2, int64_t rows2,
                                void *prepared2, int d, int schedule, vfm_stream_t stream);
 /* _prepare2_gated_p which also clears, on `stream`, the part of the search workspace `ws` (of an n x m search: ws_bytes >=
@@ -289,6 +295,19 @@ int vfm_match_search_finish_gated(const float *q, const void *q_prepared, int64_
  *                     region was cleared by vfm_match_prepare2_gated_z and nothing has touched the workspace since; the call issues no
  *                     fill.  (The matching _finish call takes the kind without the flag.) */
 #define VFM_RECORDS_WS_CLEAN 0x100
+/*   VFM_RECORDS_NO_I8     not a kind: an option of VFM_RECORDS_MX6_HALF_FUSED, or-ed into `records` of BOTH
+ *                     vfm_match_search_coarse_gated_g and vfm_match_search_finish_gated_r -- the operands were prepared with
+ *                     VFM_PREPARE_NO_I8 and carry no int8 image.  The surviving (query, chunk) pairs are rescanned on the fp6 half
+ *                     image itself, row by row with the row's own bound terms, and the rows that pass go straight to the fp64
+ *                     decision: same answers.  Where the kind would not run as VFM_RECORDS_MX6_HALF_FUSED (d other than 256 / 384,
+ *                     2048 queries or fewer, fewer than four queries per map chunk) both calls fail with VFM_EINVAL: every other
+ *                     kind needs the image that was not written.  When the device-side guard goes up (descriptors that are all
+ *                     alike: too many survivors) there is no int8 gate pass to fall back on: every query of THAT search is
+ *                     decided by the all-pairs fp64 kernel -- the oracle's answers, tens of milliseconds at 20 000 x 200 000.
+ *                     The load figure of such a search (vfm_match_search_rescans_async) says so, as without the option; a caller
+ *                     that follows it (vfmreg/pipeline.py) leaves the half-width pass after that search and prepares its next
+ *                     operands with the int8 image again. */
+#define VFM_RECORDS_NO_I8 0x200
 int vfm_match_search_coarse_gated_r(const void *q_prepared, int64_t n, const void *b_prepared, int64_t m,
                                     int d, void *ws, size_t ws_bytes, int records, vfm_stream_t stream);
 /* _coarse_gated_r with the gate of the search (needed by VFM_RECORDS_HALF_FUSED; ignored by the other kinds) */

@@ -30,6 +30,7 @@ const Field k_fields[] = {
     {"mx6_tune", &VfmConfig::mx6_tune},
     {"mx6_ns3", &VfmConfig::mx6_ns3},                {"prep_form", &VfmConfig::prep_stream},
     {"finish_short", &VfmConfig::finish_short},      {"rescan_rows", &VfmConfig::rescan_rows},
+    {"half_noi8", &VfmConfig::half_noi8},
     {"vit_preprocess_patch", &VfmConfig::vit_preprocess_patch}, {"vit_xcd", &VfmConfig::vit_xcd},
     {"vit_cfg_narrow", &VfmConfig::vit_cfg_narrow},  {"vit_cfg_wide", &VfmConfig::vit_cfg_wide},
     {"vit_wpw", &VfmConfig::vit_wpw},                {"vit_hot_a", &VfmConfig::vit_hot_a},

@@ -16,6 +16,8 @@ struct VfmConfig {
     int prep_stream = 3;       // "coarse_variant" 40, 41, 43, 44: fp6 operand preparation by prep_chunk_kernel (0) / prep_stream_kernel (1) / prep_once_kernel (3, default) /
                                // prep_once_kernel as a persistent grid, the next group's loads under a group's second pass (4)
     int finish_short = 0;      // "coarse_variant" 50 / 51: chunk-major rescan as long-lived (default) / short workgroups
+    int half_noi8 = 1;         // 1 (default): callers that follow the policy (vfmreg/pipeline.py) run VFM_RECORDS_MX6_HALF_FUSED without the int8 image
+                               // (VFM_PREPARE_NO_I8 + VFM_RECORDS_NO_I8); 0: with it, as before (A/B).  The library itself only stores the key.
     int rescan_rows = 1;       // "coarse_variant" 60 / 61: rescan gathers its queries from the fragment tiles / the row-major int8 scan (default)
     int mx6_tune = 0;          // (A/B) bit 0: s_setprio 1 for waves 4 - 7 of the fp6 coarse kernel; bit 1: its ring five steps deep (headline shape);
                                // bit 2: query sets past the end of the scan are multiplied as copies of tile 0 again (default: they do no matrix work)

@@ -121,6 +121,14 @@ CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, 
 // vfm_match_prepare2_gated_z, nothing has used the workspace since) -- no fill is issued
 int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, hipStream_t st,
                      bool bias_from_map_inv, bool inner_product, bool gated, int records, float gate, bool ws_clean) {
+    // VFM_RECORDS_NO_I8: an option beside the kind; the kind must run as VFM_RECORDS_MX6_HALF_FUSED -- any other reads the int8 image
+    const bool no_i8 = (records & VFM_RECORDS_NO_I8) != 0;
+    records &= ~VFM_RECORDS_NO_I8;
+    if (no_i8 && !(inner_product && records == VFM_RECORDS_MX6_HALF_FUSED && use_i8(d, n, m, gated) && gated &&
+                   effective_records(records, d, n, m) == VFM_RECORDS_MX6_HALF_FUSED && mx6_width(d)))
+        return vfm_fail(VFM_EINVAL, "search_coarse: VFM_RECORDS_NO_I8 needs a search that runs as VFM_RECORDS_MX6_HALF_FUSED at d = 256 / 384 (records %d, n %lld, m %lld, d %d)",
+                        records, (long long)n, (long long)m, d);
+    if (no_i8 && !(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_coarse: VFM_RECORDS_MX6_HALF_FUSED needs a finite gate");
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
@@ -219,13 +227,23 @@ VFM_EXPORT int vfm_match_prepare2_gated(const float* x1, int64_t rows1, void* pr
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16);
 }
 
+// VFM_PREPARE_NO_I8 (host-side part; do_prepare2 checks what depends on the policy): only beside the half-width fp6 image, d = 256 / 384
+static int check_no_i8(int schedule, int d) {
+    if (!(schedule & VFM_PREPARE_NO_I8)) return VFM_OK;
+    VFM_CHECK_ARG((schedule & VFM_PREPARE_MX6) && (schedule & VFM_PREPARE_MX6_HALF),
+                  "prepare2: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF (schedule %d)", schedule);
+    VFM_CHECK_ARG(d == 256 || d == 384, "prepare2: VFM_PREPARE_NO_I8 exists for d = 256 / 384, got %d", d);
+    return VFM_OK;
+}
+
 VFM_EXPORT int vfm_match_prepare2_gated_p(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2,
                                           void* prepared2, int d, int schedule, vfm_stream_t stream) {
     VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) <= VFM_PREPARE_INTERLEAVED,
+    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
+                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
                   "prepare2: unknown schedule %d", schedule);
+    if (int rc = check_no_i8(schedule, d)) return rc;
     const bool want_f16 = !use_i8(d, rows2, rows1, true);
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule);
 }
@@ -239,9 +257,10 @@ VFM_EXPORT int vfm_match_prepare2_gated_z(const float* x1, int64_t rows1, void* 
                                           vfm_stream_t stream) {
     VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2 && ws, "prepare2: null pointer");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) <= VFM_PREPARE_INTERLEAVED,
+    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
+                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
                   "prepare2: unknown schedule %d", schedule);
+    if (int rc = check_no_i8(schedule, d)) return rc;
     VFM_CHECK_ARG(n > 0 && m > 0 && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "prepare2: bad search size (n=%lld m=%lld)", (long long)n, (long long)m);
     if (ws_bytes < carve_search(nullptr, n, m).bytes) return vfm_fail(VFM_EWORKSPACE, "prepare2: search workspace too small");
     const bool want_f16 = !use_i8(d, rows2, rows1, true);
@@ -255,9 +274,10 @@ VFM_EXPORT int vfm_match_prepare2_gated_t(const void* x1, int dtype1, int64_t ro
     VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
     VFM_CHECK_ARG((dtype1 == VFM_ROWS_F32 || dtype1 == VFM_ROWS_F16) && (dtype2 == VFM_ROWS_F32 || dtype2 == VFM_ROWS_F16), "prepare2: unknown row type");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF)) <= VFM_PREPARE_INTERLEAVED,
+    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
+                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
                   "prepare2: unknown schedule %d", schedule);
+    VFM_CHECK_ARG(!(schedule & VFM_PREPARE_NO_I8), "prepare2: VFM_PREPARE_NO_I8 is for fp32 rows (vfm_match_prepare2_gated_p / _z)");
     const bool want_f16 = !use_i8(d, rows2, rows1, true);
     return do_prepare2(Rows(x1, dtype1 == VFM_ROWS_F16), rows1, prepared1, Rows(x2, dtype2 == VFM_ROWS_F16), rows2, prepared2, d,
                        (hipStream_t)stream, want_f16, schedule);
@@ -320,7 +340,8 @@ VFM_EXPORT int vfm_match_search_coarse_gated_g(const void* q_prepared, int64_t n
     VFM_CHECK_ARG(q_prepared && b_prepared && ws, "search_coarse: null pointer");
     const bool ws_clean = (records & VFM_RECORDS_WS_CLEAN) != 0;   // (a flag beside the kind, not a kind)
     records &= ~VFM_RECORDS_WS_CLEAN;
-    VFM_CHECK_ARG(records >= VFM_RECORDS_BEST && records <= VFM_RECORDS_MX6_FUSED, "search_coarse: unknown record kind %d", records);
+    VFM_CHECK_ARG((records & ~VFM_RECORDS_NO_I8) >= VFM_RECORDS_BEST && (records & ~VFM_RECORDS_NO_I8) <= VFM_RECORDS_MX6_FUSED,
+                  "search_coarse: unknown record kind %d", records);
     VFM_CHECK_ARG(gate == gate, "search_coarse: gate is NaN");
     return do_search_coarse(q_prepared, n, b_prepared, m, d, ws, (hipStream_t)stream, false, true, true, records, gate, ws_clean);
 }
@@ -338,7 +359,8 @@ VFM_EXPORT int vfm_match_search_finish_gated_r(const float* q, const void* q_pre
     if (int rc = check_search_args(n, m, d, ws_bytes)) return rc;
     VFM_CHECK_ARG(q && b && q_prepared && b_prepared && ws && idx_out && sim_out, "search_finish: null pointer");
     VFM_CHECK_ARG(gate == gate, "search_finish: gate is NaN");
-    VFM_CHECK_ARG(records >= VFM_RECORDS_BEST && records <= VFM_RECORDS_MX6_FUSED, "search_finish: unknown record kind %d", records);
+    VFM_CHECK_ARG((records & ~VFM_RECORDS_NO_I8) >= VFM_RECORDS_BEST && (records & ~VFM_RECORDS_NO_I8) <= VFM_RECORDS_MX6_FUSED,
+                  "search_finish: unknown record kind %d", records);
     return do_search_finish(q, q_prepared, n, b, b_prepared, m, d, idx_out, sim_out, ws, (hipStream_t)stream, true, gate, records);
 }
 

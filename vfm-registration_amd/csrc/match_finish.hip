@@ -935,6 +935,252 @@ int launch_rescan_chunk(const SearchWs& w, int nchunks, int64_t n, int64_t m, in
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// VFM_RECORDS_MX6_HALF_FUSED | VFM_RECORDS_NO_I8: the chunk-major rescan on the fp6 HALF image -- the image the coarse kernel has just
+// multiplied (5 KiB per 32-row tile at d = 384; operands prepared with VFM_PREPARE_NO_I8 carry no int8 byte).  The frame is
+// match_rescan_chunk_kernel's: one workgroup per (chunk, bin slice); wave w holds tile w of the chunk as the MFMA's first operand (the
+// scales and the first KS6 k-steps of the stored tile: 6 KS6 + 1 registers); the bin's queries are taken 32 at a time, their fragments
+// gathered from the scan's fp6 tiles into ONE operand image in the LDS by LDS-DMA issued D - 1 blocks ahead, and KS6 scaled MFMAs per
+// wave (match_coarse_mx6.hip's, same operand order, same accumulation: the scores are the coarse kernel's) give x = the fp6 score of
+// 32 rows x 32 queries over the first d / 2 columns.
+//
+// Hit test per (query q, row r) -- emit_chunk's expression (the bound of match_select_half_kernel with mx6_bounds_half) with the ROW's
+// residual norm and rest norm in place of the chunk's maxima:
+//     exact score of (q, r)  <=  x + A_q + (1 + 2^-13 + E_q) E_r + rest_q rest_r  (+ 2e-6 for the fp32 evaluation),
+// E = err6h, the image's residual over the columns the pass multiplies (MX6_SLACK, which pays for the MFMA's fp32 accumulation, is in
+// every E), rest = |second half of the normalised row|, rounded up (Cauchy-Schwarz on the columns the pass does not multiply).  A row is
+// a hit when that upper bound reaches the gate, tested as a threshold on x exactly as emit_chunk does.
+// Nothing is lost: the bound holds row by row -- the chunk's form is this one with E_r, rest_r replaced by their maxima over the chunk --
+// so every row whose exact cosine reaches the gate is a hit here; and its chunk was binned for the query, because every fp32 operation
+// of the threshold is monotone in E_r and rest_r: threshold(chunk) <= threshold(row) <= x(row) <= the chunk's best x.
+// Hits are single-row entries (chunk << 8 | row) with their upper bound in cand_up, staged in the LDS and counted through hit_cnt as
+// the int8 kernel's are: match_rescan_close_kernel is reused as it stands.  Rows at or beyond m never hit; guard up: nothing to do.
+// ---------------------------------------------------------------------------------------------
+typedef int finish_intx8 __attribute__((ext_vector_type(8)));
+// one lane's operand of a k-step of v_mfma_scale_f32_32x32x64_f8f6f4 in e2m3: 32 codes in six registers (match_coarse_mx6.hip)
+struct Mx6Frag {
+    int c[6];
+};
+template <int S>
+__device__ __forceinline__ floatx16 mfma_mx6(const Mx6Frag& x, unsigned xs, const Mx6Frag& y, unsigned ys, floatx16 c) {
+    static_assert(S >= 0 && S < 4, "the scales of k-steps 0 .. 3 are the four bytes of one register");
+    finish_intx8 a, b;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        a[i] = x.c[i];
+        b[i] = y.c[i];
+    }
+    a[6] = a[7] = b[6] = b[7] = 0;   // not read: cbsz = blgp = 2 (e2m3) takes six registers per operand
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, S, (int)xs, S, (int)ys);
+}
+constexpr int rescan6_depth() { return 3; }   // ring slots (blocks of 32 queries)
+// A ring slot: [KS6][64] x 16 B = code plane A of every k-step as the MFMA lanes read it, [KS6][2][64] x 4 B = code plane B as its two
+// dwords (LDS-DMA moves 4 or 16 bytes per lane: the 8-byte units of the stored plane arrive as two dword gathers), [64] x 4 B = the
+// scales of k-steps 0 .. 3, then two rows of 64 per-query terms: [0] cand_cnt | err6h (lanes 0 - 31 | 32 - 63), [1] rest
+template <int KS6>
+constexpr unsigned rescan6_slot_bytes() { return (unsigned)KS6 * 1536u + 256u + 512u; }
+template <int KS6>  // k-steps of 64 columns the half-width pass multiplies (d / 128)
+__global__ __launch_bounds__(256) void match_rescan_chunk_mx6h_kernel(int64_t n, int64_t m, const unsigned char* __restrict__ q6,
+                                                                      const unsigned char* __restrict__ b6, const float* __restrict__ qerr,
+                                                                      const float* __restrict__ qrest, const float* __restrict__ berr,
+                                                                      const float* __restrict__ brest, int* __restrict__ cand_cnt,
+                                                                      unsigned* __restrict__ cand, int cap, const unsigned* __restrict__ bin_cnt,
+                                                                      const int* __restrict__ bins, float gate, const int* __restrict__ guard,
+                                                                      int bin_cap, unsigned* __restrict__ hit_cnt, float* __restrict__ cand_up,
+                                                                      int slice) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(KS6 >= 2 && KS6 <= 4, "the half-width image of d = 256 / 384 / 512: one scale register per lane");
+    constexpr int D = rescan6_depth();
+    constexpr unsigned SLOT = rescan6_slot_bytes<KS6>();
+    constexpr int IMG_TB = mx6_tile_bytes(2 * KS6);   // bytes of a stored tile (the full-width layout; the pass reads its prefix)
+    constexpr int NI = 3 * KS6 + 3;                   // DMA instructions per block: KS6 plane A, 2 KS6 plane B, scales, two rows of terms
+    constexpr int NG = (NI + 3) / 4;                  // ... per wave (a wave past the end repeats the last one: the same bytes again)
+    __shared__ __attribute__((aligned(16))) unsigned char ring[D * SLOT];
+    __shared__ int lbin[RESCAN_SLICE];
+    __shared__ int lhq[RESCAN_LHITS];
+    __shared__ unsigned char lhr[RESCAN_LHITS];
+    __shared__ float lhu[RESCAN_LHITS];   // the row's upper bound (cand_up)
+    __shared__ int lhit_n;
+    const int c = blockIdx.x;
+    if (guard && *guard) return;   // too many survivors: match_guard_fallback_kernel has sent every query to the all-pairs kernel
+    const unsigned filled = bin_cnt[(size_t)c * BIN_CNT_STRIDE];
+    const int nall = filled < (unsigned)bin_cap ? (int)filled : bin_cap;
+    const int jbeg = blockIdx.y * slice;   // a long bin is shared by the workgroups (c, 0), (c, 1), ... (slice <= RESCAN_SLICE entries each)
+    if (jbeg >= nall) return;
+    const int nq = nall - jbeg < slice ? nall - jbeg : slice;
+    const int nblocks = (nq + 31) >> 5;
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x == 0) lhit_n = 0;
+    {
+        const int* bin = bins + (size_t)c * bin_cap + jbeg;
+        for (int t = threadIdx.x; t < nblocks * 32; t += 256) lbin[t] = t < nq ? bin[t] : 0;
+    }
+    // tile `wave` of the chunk: the first operand
+    Mx6Frag af[KS6];
+    unsigned as;
+    {
+        const unsigned char* tile = b6 + ((size_t)c * 4 + wave) * (size_t)IMG_TB;
+#pragma unroll
+        for (int s = 0; s < KS6; ++s) {
+            const uint4 lo = *reinterpret_cast<const uint4*>(tile + mx6_code_a(s, lane));
+            const uint2 hi = *reinterpret_cast<const uint2*>(tile + mx6_code_b(s, lane));
+            af[s] = Mx6Frag{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}};
+        }
+        as = *reinterpret_cast<const unsigned*>(tile + mx6_scale_at(2 * KS6, 0, lane));
+    }
+    const long long base = (long long)c * CHUNK_ROWS;
+    const int rr0 = wave * 32 + 4 * (lane >> 5);   // + (e & 3) + 8 (e >> 2): the chunk row of accumulator element e
+    float be16[16], br16[16];                      // err6h / rest of the lane's sixteen rows (rows of the padded operand always exist)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        be16[e] = berr[base + rr0 + (e & 3) + 8 * (e >> 2)];
+        br16[e] = brest[base + rr0 + (e & 3) + 8 * (e >> 2)];
+    }
+    // everything loaded above is in its registers before the first DMA goes out: from here on the vector-memory queue holds DMA only
+#pragma unroll
+    for (int s = 0; s < KS6; ++s) asm volatile("" ::"v"(af[s].c[0]), "v"(af[s].c[1]), "v"(af[s].c[2]), "v"(af[s].c[3]), "v"(af[s].c[4]), "v"(af[s].c[5]));
+    asm volatile("" ::"v"(as));
+#pragma unroll
+    for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(be16[e]), "v"(br16[e]));
+    wait_vmcnt<0>();
+    __syncthreads();
+    const unsigned lds_base = (unsigned)(uintptr_t)(LDS_AS unsigned char*)ring;
+    auto issue = [&](int blk) {
+        const int qi = lbin[blk * 32 + (lane & 31)];
+        const unsigned slot = lds_base + (unsigned)(blk % D) * SLOT;
+        // MFMA lane (h, p) of the block's operand = lane 32 h + (qi & 31) of the query's stored tile
+        const unsigned char* qtile = q6 + (size_t)(qi >> 5) * (size_t)IMG_TB;
+        const int ql = (lane & 32) + (qi & 31);
+#pragma unroll
+        for (int t = 0; t < NG; ++t) {
+            int i = wave + 4 * t;   // wave-uniform
+            i = i < NI ? i : NI - 1;
+            if (i < KS6) {
+                glds16(qtile + mx6_code_a(i, ql), __builtin_amdgcn_readfirstlane(slot + (unsigned)i * 1024u));
+            } else if (i < 3 * KS6) {
+                const int j = i - KS6;   // (k-step j >> 1, dword j & 1 of the lane's eight bytes of plane B)
+                glds4(qtile + mx6_code_b(j >> 1, ql) + 4 * (j & 1), __builtin_amdgcn_readfirstlane(slot + (unsigned)KS6 * 1024u + (unsigned)j * 256u));
+            } else if (i == 3 * KS6) {
+                glds4(qtile + mx6_scale_at(2 * KS6, 0, ql), __builtin_amdgcn_readfirstlane(slot + (unsigned)KS6 * 1536u));
+            } else if (i == 3 * KS6 + 1) {
+                glds4(lane < 32 ? (const void*)(cand_cnt + qi) : (const void*)(qerr + qi), __builtin_amdgcn_readfirstlane(slot + (unsigned)KS6 * 1536u + 256u));
+            } else {
+                glds4((const void*)(qrest + qi), __builtin_amdgcn_readfirstlane(slot + (unsigned)KS6 * 1536u + 512u));
+            }
+        }
+    };
+#pragma unroll
+    for (int blk = 0; blk < D - 1; ++blk)
+        if (blk < nblocks) issue(blk);
+    for (int blk = 0; blk < nblocks; ++blk) {          // the bin, one MFMA column block at a time
+        // this wave's pieces of block blk have landed: at most the D - 2 blocks issued behind it may still be in flight
+        if (blk + D - 2 < nblocks) wait_vmcnt<(D - 2) * NG>();
+        else wait_vmcnt<0>();
+        __syncthreads();                               // ... and every wave's; block blk - 1 has been read by every wave
+        if (blk + D - 1 < nblocks) issue(blk + D - 1);
+        const unsigned char* slot = ring + (size_t)(blk % D) * SLOT;
+        const int* lt = reinterpret_cast<const int*>(slot + (size_t)KS6 * 1536 + 256);
+        const int j = blk * 32 + (lane & 31);
+        const int qi = lbin[j];
+        const bool live = j < nq && lt[lane & 31] >= 0;   // (-1: already with the all-pairs kernel)
+        const float eq = __int_as_float(lt[32 + (lane & 31)]);
+        const float rq = __int_as_float(lt[64 + (lane & 31)]);
+        const unsigned qs = *reinterpret_cast<const unsigned*>(slot + (size_t)KS6 * 1536 + 4 * lane);
+        floatx16 acc;
+        auto kstep = [&](auto Sc) __attribute__((always_inline)) {
+            constexpr int s = decltype(Sc)::value;
+            const uint4 lo = *reinterpret_cast<const uint4*>(slot + (size_t)s * 1024 + 16 * lane);
+            const unsigned h0 = *reinterpret_cast<const unsigned*>(slot + (size_t)KS6 * 1024 + (size_t)(2 * s) * 256 + 4 * lane);
+            const unsigned h1 = *reinterpret_cast<const unsigned*>(slot + (size_t)KS6 * 1024 + (size_t)(2 * s + 1) * 256 + 4 * lane);
+            const Mx6Frag qf{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)h0, (int)h1}};
+            if constexpr (s == 0) {   // (the coarse kernel's first MFMA starts from the constant 0 as well)
+                floatx16 zero;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) zero[r] = 0.0f;
+                acc = mfma_mx6<s>(af[s], as, qf, qs, zero);
+            } else {
+                acc = mfma_mx6<s>(af[s], as, qf, qs, acc);
+            }
+        };
+        kstep(std::integral_constant<int, 0>{});
+        kstep(std::integral_constant<int, 1>{});
+        if constexpr (KS6 > 2) kstep(std::integral_constant<int, 2>{});
+        if constexpr (KS6 > 3) kstep(std::integral_constant<int, 3>{});
+        // emit_chunk's threshold (next_thr in match_coarse_mx6.hip) with the row's terms for the chunk's maxima
+        const float fx_A = eq * 1.0001220703125f + 1.0e-6f, fx_mult = 1.0001220703125f + eq;
+        unsigned hits = 0u;
+        if (live) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const float thr = ((gate - 1.0e-6f) - (fx_A + fx_mult * be16[e])) - (rq * br16[e] + 1.0e-6f);
+                if (base + rr < m && !(acc[e] < thr)) hits |= 1u << e;
+            }
+        }
+        if (hits) {
+            int at = atomicAdd(&lhit_n, __popc(hits));
+            while (hits) {
+                const int e = __ffs(hits) - 1;
+                hits &= hits - 1u;
+                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const float upe = (acc[e] + (fx_A + fx_mult * be16[e])) + (rq * br16[e] + 2.0e-6f);
+                if (at < RESCAN_LHITS) {
+                    lhq[at] = qi;
+                    lhr[at] = (unsigned char)rr;
+                    lhu[at] = upe;
+                } else {   // more hits than the staging buffer holds (duplicate-rich chunk): on the spot
+                    const int pos = cand_cnt[qi] + (int)atomicAdd(&hit_cnt[(size_t)qi * BIN_CNT_STRIDE], 1u);
+                    if (pos < cap) {
+                        cand[(size_t)qi * cap + pos] = ((unsigned)c << 8) | (unsigned)rr;
+                        cand_up[(size_t)qi * cap + pos] = upe;
+                    }
+                }
+                ++at;
+            }
+        }
+        // (a full staging buffer is emptied before the next block adds to it; lhit_n is read by every thread between two barriers
+        // that no atomic of another block can cross, so the branch is uniform)
+        __syncthreads();
+        if (lhit_n > RESCAN_LHITS / 2 || blk + 1 == nblocks) {
+            wait_vmcnt<0>();   // (the atomics below are compiler-tracked: nothing of the ring may be pending behind them)
+            const int nh = lhit_n < RESCAN_LHITS ? lhit_n : RESCAN_LHITS;
+            for (int i = threadIdx.x; i < nh; i += 256) {
+                // (the list's length stays as match_bin_survivors_kernel left it during this kernel; the appended rows are counted in
+                // hit_cnt, a line of their own per query, and added by match_rescan_close_kernel)
+                const int hq = lhq[i];
+                const int pos = cand_cnt[hq] + (int)atomicAdd(&hit_cnt[(size_t)hq * BIN_CNT_STRIDE], 1u);
+                if (pos < cap) {
+                    cand[(size_t)hq * cap + pos] = ((unsigned)c << 8) | (unsigned)lhr[i];
+                    cand_up[(size_t)hq * cap + pos] = lhu[i];
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) lhit_n = 0;
+        }
+    }
+#endif   // __HIP_DEVICE_COMPILE__
+}
+
+// VFM_RECORDS_NO_I8, behind half_guard_kernel: with the guard up there is no int8 image for a gate pass -- every live query goes to the
+// all-pairs kernel (cand_cnt = -1, listed in fb_list; half_guard_kernel has reset the list's length).  One atomic per wavefront.
+__global__ __launch_bounds__(256) void match_guard_fallback_kernel(int64_t n, const float* __restrict__ invq, const int* __restrict__ guard,
+                                                                   int* __restrict__ cand_cnt, int* __restrict__ fb_count,
+                                                                   int* __restrict__ fb_list) {
+    if (*guard == 0) return;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = lane_id();
+    const bool live = q < n && invq[q] != 0.0f;
+    const unsigned long long bal = __ballot(live);
+    if (bal == 0ull) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(fb_count, __popcll(bal));
+    base = __shfl(base, 0);
+    if (live) {
+        cand_cnt[q] = -1;
+        fb_list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (int)q;
+    }
+}
+
 // VFM_RECORDS_MX6_PILOT: every query (zero rows aside) into the bin of the chunk its best fp6 score came from
 __global__ __launch_bounds__(256) void match_pilot_bin_kernel(int64_t n, const unsigned long long* __restrict__ qbest,
                                                               const float* __restrict__ invq, unsigned* __restrict__ bin_cnt,
@@ -1954,6 +2200,64 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__
 
 }  // namespace
 
+template <int KS6>
+int launch_rescan_chunk_mx6h(const SearchWs& w, int nchunks, int64_t n, int64_t m, const Prepared& Q, const Prepared& B, float gate,
+                             const int* guard, hipStream_t st) {
+    const int slice = vfm_cfg().finish_short ? 128 : RESCAN_SLICE;
+    hipLaunchKernelGGL(match_rescan_chunk_mx6h_kernel<KS6>, dim3((unsigned)nchunks, (unsigned)((w.bin_cap + slice - 1) / slice)), dim3(256), 0, st,
+                       n, m, reinterpret_cast<const unsigned char*>(Q.tiles6), reinterpret_cast<const unsigned char*>(B.tiles6),
+                       (const float*)Q.err6h, (const float*)Q.rest, (const float*)B.err6h, (const float*)B.rest, w.cand_cnt, w.cand, w.cap,
+                       (const unsigned*)w.bin_cnt, (const int*)w.bins, gate, guard, w.bin_cap, w.hit_cnt, w.cand_up, slice);
+    VFM_CHECK_LAUNCH("match_rescan_chunk_mx6h_kernel");
+    return VFM_OK;
+}
+
+// VFM_RECORDS_MX6_HALF_FUSED | VFM_RECORDS_NO_I8: the finish stage of operands without an int8 image.  No kernel launched here reads
+// tiles8 / tiles8h / rows8 / err / gstep / gerr of either operand: the survivors are binned (match_bin_survivors_kernel: the slots
+// only), the guard counts the bins, the rescan reads the fp6 half image with err6h / rest, the closing pass the counters, and the fp64
+// decision the rows themselves.
+//   whole-chunk entries (a full bin leaves chunk << 8 | 128 in the query's list): match_rescan_close_kernel changes lengths, never
+//     entries, and match_rescore_kernel scores such a chunk's 128 rows in fp64 -- they stay as they are;
+//   crowded queries: match_rescore_kernel takes any list up to `cap` (epochs of RS_PAIRS pairs) and decides it in fp64 with the
+//     oracle's tie rule; the fp32 refinement only ever shortened such a list.  The closing pass still notes them (rec_cnt,
+//     fb_count[6]); nothing reads that here;
+//   guard up: match_guard_fallback_kernel hands every live query to match_exact_kernel (include/vfmreg.h, VFM_RECORDS_NO_I8).
+static int finish_half_noi8(Rows q, const Prepared& Q, int64_t n, Rows b, const Prepared& B, int64_t m, int d, int64_t* idx_out,
+                            float* sim_out, const SearchWs& w, const CoarseArgs& a, float gate, hipStream_t st) {
+    const int* guard = w.fb_count + HALF_GUARD_FLAG;
+    hipLaunchKernelGGL(match_bin_survivors_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w.partials),
+                       mx6_survivor_slot_words(), (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
+    VFM_CHECK_LAUNCH("match_bin_survivors_kernel");
+    hipLaunchKernelGGL(half_guard_kernel, dim3(1), dim3(256), 0, st, w.fb_count, (const unsigned*)w.bin_cnt, a.nchunks, 1,
+                       (long long)HALF_GUARD_PER_QUERY * (long long)n);
+    VFM_CHECK_LAUNCH("half_guard_kernel");
+    hipLaunchKernelGGL(match_guard_fallback_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const float*)Q.inv, guard,
+                       w.cand_cnt, w.fb_count, w.fb_list);
+    VFM_CHECK_LAUNCH("match_guard_fallback_kernel");
+    const int rc = d == 384 ? launch_rescan_chunk_mx6h<3>(w, a.nchunks, n, m, Q, B, gate, guard, st)
+                            : launch_rescan_chunk_mx6h<2>(w, a.nchunks, n, m, Q, B, gate, guard, st);
+    if (rc != VFM_OK) return rc;
+    hipLaunchKernelGGL(match_rescan_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, w.cand_cnt, w.cap, w.fb_count,
+                       w.fb_list, reinterpret_cast<int*>(w.rec_cnt), (const float*)Q.inv, (const unsigned*)w.hit_cnt);
+    VFM_CHECK_LAUNCH("match_rescan_close_kernel");
+    {
+        const size_t lds = (size_t)(64 * RS_STRIDE + RS_PAIRS) * sizeof(double) + (size_t)d * sizeof(float);
+        static unsigned long long attr_set = 0ull;  // one bit per device
+        if (!attr_done(attr_set)) {
+            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            attr_mark(attr_set);
+        }
+        hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m, d,
+                           w.cand_cnt, w.cand, w.cap, idx_out, sim_out, gate);
+    }
+    VFM_CHECK_LAUNCH("match_rescore_kernel");
+    hipLaunchKernelGGL(match_exact_kernel, dim3(256), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q, Q.inv, b, B.inv, n, m,
+                       d, w.fb_list, w.fb_count, idx_out, sim_out);
+    VFM_CHECK_LAUNCH("match_exact_kernel(fallback)");
+    return VFM_OK;
+}
+
 // stage 2 of a search: candidate selection + exact fp64 decision (reads ws of stage 1)
 // gated: the search was started by the gated family (do_search_coarse(..., gated)); gate: queries whose best similarity is
 // provably below it are reported as (-1, -2.0) instead of being resolved (int8 pass only; -Inf = resolve every query)
@@ -1964,9 +2268,19 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
     SearchWs w = carve_search(ws, n, m);
     const CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
     const float w2 = 2.0f * (float)(d / 16 + 4 + 2) * 5.9604645e-8f;
+    const bool no_i8 = (records & VFM_RECORDS_NO_I8) != 0;   // an option beside the kind (VFM_RECORDS_MX6_HALF_FUSED only)
+    records &= ~VFM_RECORDS_NO_I8;
     const bool i8 = records != VFM_RECORDS_F16 && use_i8(d, n, m, gated);
     if (i8 && !gated) records = VFM_RECORDS_TOP2;  // as do_search_coarse chose
     records = effective_records(records, d, n, m);
+    if (no_i8) {
+        // any other kind -- asked for, or what this shape makes of the one asked for -- reads the int8 image that was not written
+        if (!(i8 && gated && records == VFM_RECORDS_MX6_HALF_FUSED && mx6_width(d)))
+            return vfm_fail(VFM_EINVAL, "search_finish: VFM_RECORDS_NO_I8 needs a search that runs as VFM_RECORDS_MX6_HALF_FUSED at d = 256 / 384 (n %lld, m %lld, d %d)",
+                            (long long)n, (long long)m, d);
+        if (!(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_finish: VFM_RECORDS_HALF needs a finite gate");
+        return finish_half_noi8(q, Q, n, b, B, m, d, idx_out, sim_out, w, a, gate, st);
+    }
     // the fp6 coarse kernel has left the survivors in its workgroups' slots (half width, or -- VFM_RECORDS_MX6_FUSED -- full width: behind
     // the kernel the two are the same search: survivors of a gate test, binned, rescanned on the int8 image with the gate as hit test)
     const bool fused6 = i8 && (records == VFM_RECORDS_MX6_HALF_FUSED || records == VFM_RECORDS_MX6_FUSED);

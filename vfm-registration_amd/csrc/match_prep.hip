@@ -847,7 +847,14 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
 // z: ranges of a search workspace this launch clears for the coarse pass that follows (vfm_match_prepare2_gated_z), 16 bytes per lane,
 // spread over the grid; none (z.na == z.nb == 0) for every other caller.
 // ---------------------------------------------------------------------------------------------
-template <int D, bool HALF, bool PERSIST>
+//
+// NOI8 (VFM_PREPARE_NO_I8, with HALF only): the operands of a VFM_RECORDS_MX6_HALF_FUSED | VFM_RECORDS_NO_I8 search, which reads no int8
+// byte.  Everything that exists only for the int8 image is left out -- the group's largest magnitude and its round through the LDS (two
+// barriers), rint / packing / the tile stores, the scan's row-major copy, err / gstep / gerr -- and pass 1 keeps only what the fp6 half
+// image is converted from: the first chunks (the second chunks of d = 384 lie past column d / 2: 32 registers less).  inv, the fp6 half
+// image with its scales, err6h / gerr6h (err6 / gerr6: infinite, as with HALF), gstep6, rest / grest and the PrepZero ranges are the
+// bytes of the form without the flag: the same arithmetic on the same values.  The int8 regions of the operand stay unwritten.
+template <int D, bool HALF, bool PERSIST, bool NOI8 = false>
 __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restrict__ x1, int64_t rows1, PrepOut o1, int groups1,
                                                            const float* __restrict__ x2, int64_t rows2, PrepOut o2, int groups, PrepZero z) {
     constexpr bool PAIR = D > 256;               // d = 384: a row is one chunk per lane + half a chunk -- the second chunks of TWO rows share a register
@@ -857,7 +864,8 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     constexpr int nconv = HALF ? NBLK >> 1 : NBLK;   // blocks the fp6 image covers (HALF: VFM_PREPARE_MX6_HALF, o.mx6_half)
     constexpr int nitems = 8 * nconv;            // (row, block) items of a batch
     static_assert(D == 256 || D == 384, "a lane owns one chunk (d = 256) or one and a half (d = 384) of a row");
-    __shared__ __attribute__((aligned(16))) unsigned char l_i8[4][8 * RS8];
+    static_assert(!NOI8 || (HALF && 8 * nconv <= 64), "without the int8 image: the half-width fp6 image, converted from the first chunks alone");
+    __shared__ __attribute__((aligned(16))) unsigned char l_i8[4][NOI8 ? 16 : 8 * RS8];
     __shared__ __attribute__((aligned(16))) unsigned char l_h16[4][4 * nitems * 16];
     __shared__ float l_e6[NBLK][I8_GROUP];
     __shared__ unsigned char l_sc[I8_GROUP][16];
@@ -993,7 +1001,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     }
     // the wave's 32 normalised rows as packed halves: hs0[row] = the lane's first chunk; hs1[pair] (d = 384) = the pair's second chunks
     uint2 hs0[32];
-    uint2 hs1[PAIR ? 16 : 1];
+    uint2 hs1[PAIR && !NOI8 ? 16 : 1];
     // ---- pass 1: 1 / |row| (oracle order), the group's largest normalised magnitude, |second half|, the fp16 copy (its first batch is
     // in v0 / vp: requested above, or under the previous group's pass 2)
     __syncthreads();   // the maxima are initialised (pass 1 already adds to rmax_bits)
@@ -1024,14 +1032,15 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
             ivs[j] = iv;
             // normalised values exactly as faiss leaves them in fp32
             const float nv[4] = {v0[j].x * iv, v0[j].y * iv, v0[j].z * iv, v0[j].w * iv};
-            lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(nv[0]), fabsf(nv[1])), fmaxf(fabsf(nv[2]), fabsf(nv[3]))));
+            if constexpr (!NOI8) lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(nv[0]), fabsf(nv[1])), fmaxf(fabsf(nv[2]), fabsf(nv[3]))));
             const float ss = nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] + nv[3] * nv[3];
             float r2 = 0.0f;
             r2 = r2 + ((8 * lane >= D) ? ss : 0.0f);   // columns >= d / 2 (the other forms' sum: x + 0 = x)
             hs0[8 * b + j] = pack4(nv);
             // (the row's sums are wanted HERE: left to the compiler they were formed at the end of the batch and the normalised values of
             // its rows were spilled to wait for it)
-            asm volatile("" : "+v"(r2), "+v"(lmax));
+            if constexpr (NOI8) asm volatile("" : "+v"(r2));
+            else asm volatile("" : "+v"(r2), "+v"(lmax));
             rpart[j] = r2;
             if (b < 3) load_row(b + 1, j);
         }
@@ -1040,10 +1049,14 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
             for (int jp = 0; jp < 4; ++jp) {
                 const float iv = lo ? ivs[2 * jp] : ivs[2 * jp + 1];
                 const float nv[4] = {vp[jp].x * iv, vp[jp].y * iv, vp[jp].z * iv, vp[jp].w * iv};
-                lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(nv[0]), fabsf(nv[1])), fmaxf(fabsf(nv[2]), fabsf(nv[3]))));
+                if constexpr (!NOI8) lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(nv[0]), fabsf(nv[1])), fmaxf(fabsf(nv[2]), fabsf(nv[3]))));
                 float ss = nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] + nv[3] * nv[3];   // all of these columns are >= d / 2
-                hs1[4 * b + jp] = pack4(nv);
-                asm volatile("" : "+v"(ss), "+v"(lmax));
+                if constexpr (NOI8) {   // (past column d / 2: nothing is converted from them)
+                    asm volatile("" : "+v"(ss));
+                } else {
+                    hs1[4 * b + jp] = pack4(nv);
+                    asm volatile("" : "+v"(ss), "+v"(lmax));
+                }
                 const float ssb = hi_to_lo(ss);                       // the odd row's, back in the lanes the oracle's tree expects
                 rpart[2 * jp] = rpart[2 * jp] + (lo ? ss : 0.0f);
                 rpart[2 * jp + 1] = rpart[2 * jp + 1] + (lo ? ssb : 0.0f);
@@ -1061,15 +1074,18 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
             }
         }
     }
+    float qstep = 1.0f, inv_qstep = 0.0f;
+    if constexpr (!NOI8) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off));
-    __syncthreads();
-    if (lane == 0 && lmax > 0.0f) atomicMax(&amax_bits, __float_as_uint(lmax));
-    __syncthreads();
-    const float amax = __uint_as_float(amax_bits);
-    const bool usable = amax > 0.0f && amax < 3.0e38f;
-    const float qstep = usable ? amax / 127.0f : 1.0f;
-    const float inv_qstep = usable ? 127.0f / amax : 0.0f;
+        for (int off = 32; off >= 1; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off));
+        __syncthreads();
+        if (lane == 0 && lmax > 0.0f) atomicMax(&amax_bits, __float_as_uint(lmax));
+        __syncthreads();
+        const float amax = __uint_as_float(amax_bits);
+        const bool usable = amax > 0.0f && amax < 3.0e38f;
+        qstep = usable ? amax / 127.0f : 1.0f;
+        inv_qstep = usable ? 127.0f / amax : 0.0f;
+    }
     const int next = gidx + (int)gridDim.x;
     if constexpr (PERSIST) {
         // v0 / vp are free from here to the top of the loop: the next group's first batch travels under this group's pass 2
@@ -1084,6 +1100,13 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     uint4* tile8h = o.tiles8h + ((size_t)grp * 4 + wave) * (size_t)((NU >> 1) * 32);
     // one chunk of a row: quantise (codes to the batch's int8 slice), residual against the fp16 value, the halves to the fp6 staging
     auto quant_chunk = [&](uint2 hh, int jr, int c) __attribute__((always_inline)) {
+        if constexpr (NOI8) {   // the halves to the fp6 staging, nothing else
+            if (c < 8 * nconv) {
+                const int blk = c >> 3, k = (c & 7) >> 1, sub = c & 1;
+                *reinterpret_cast<uint2*>(my16 + ((size_t)(k * nitems + jr * nconv + blk) * 16 + sub * 8)) = hh;
+            }
+            return 0.0f;
+        }
         float nv[4];
         unpack4(hh, nv);
         int qi[4];
@@ -1113,7 +1136,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         float part[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) part[j] = quant_chunk(hs0[8 * b + j], j, lane);
-        if constexpr (PAIR) {
+        if constexpr (PAIR && !NOI8) {
 #pragma unroll
             for (int jp = 0; jp < 4; ++jp) {
                 const float e2 = quant_chunk(hs1[4 * b + jp], 2 * jp + (lane >> 5), 64 + (lane & 31));
@@ -1122,7 +1145,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
                 part[2 * jp + 1] = part[2 * jp + 1] + (lo ? 0.0f : e2);
             }
         }
-        {
+        if constexpr (!NOI8) {
             // E = |h - s q|_2 (measured, rounded up) + |v - h|_2 (bounded: PREP_F16_ROUNDING)
             float en = (sqrtf(scatter8(part)) * 1.000244140625f + PREP_F16_ROUNDING) * 1.0000002384185791f + 1.0e-30f;
             if (!(en == en)) en = __builtin_inff();
@@ -1139,7 +1162,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         // int8: unit column u of the batch's 8 rows = 128 consecutive bytes of the tile
 #ifndef VFM_POABL_NOST8
 #pragma unroll
-        for (int rd = 0; rd < (NU * 8 + 63) / 64; ++rd) {
+        for (int rd = 0; rd < (NOI8 ? 0 : (NU * 8 + 63) / 64); ++rd) {
             const int e = rd * 64 + lane, u = e >> 3, j = e & 7;
             if (e < NU * 8) {
                 const uint4 tq = *reinterpret_cast<const uint4*>(my8 + j * RS8 + 16 * u);
@@ -1158,7 +1181,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
             }
         }
 #endif
-        if (o.rows8) {   // row-major copy (scan-sized operands): the batch's rows as they lie in the slice
+        if (!NOI8 && o.rows8) {   // row-major copy (scan-sized operands): the batch's rows as they lie in the slice
 #pragma unroll
             for (int rd = 0; rd < (NU * 8 + 63) / 64; ++rd) {
                 const int e = rd * 64 + lane, j = e / NU, u = e - j * NU;
@@ -1246,8 +1269,10 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     }
     __syncthreads();
     if (tid == 0) {
-        o.gstep[grp] = qstep;
-        o.gerr[grp] = __uint_as_float(emax_bits);
+        if constexpr (!NOI8) {
+            o.gstep[grp] = qstep;
+            o.gerr[grp] = __uint_as_float(emax_bits);
+        }
         o.grest[grp] = __uint_as_float(rmax_bits);
         o.gerr6[grp] = __uint_as_float(e6max_bits);
         o.gerr6h[grp] = __uint_as_float(e6hmax_bits);
@@ -1257,7 +1282,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         break;
     } else {
         // (the scales and E of this group were read from l_sc / l_e6 before the barrier above, and the next group writes them only
-        // behind three more: no barrier of its own is needed here)
+        // behind three more -- one, at the top of its pass 1, without the int8 image: no barrier of its own is needed here)
         if (next >= groups) break;
         gidx = next;
     }
@@ -1497,6 +1522,12 @@ int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows
     const float* x2 = static_cast<const float*>(x2r.p);
     const int h6 = (grid_mode & VFM_PREPARE_MX6_HALF) != 0 ? 1 : 0;   // the fp6 image of the first d / 2 columns only (implies VFM_PREPARE_MX6)
     if (h6) grid_mode |= VFM_PREPARE_MX6;
+    // VFM_PREPARE_NO_I8: prep_once_kernel<., true, ., true> or nothing -- no other form leaves the int8 image out
+    const bool no_i8 = (grid_mode & VFM_PREPARE_NO_I8) != 0;
+    grid_mode &= ~VFM_PREPARE_NO_I8;
+    if (no_i8 && !(h6 && mx6_width(d) && !any_f16 && x2 && (vfm_cfg().prep_stream == 3 || vfm_cfg().prep_stream == 4)))
+        return vfm_fail(VFM_EINVAL, "prepare: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6_HALF, d = 256 / 384, fp32 rows of both operands and the "
+                                    "one-read preparation (prep_form 3 / 4)");
     const bool want_mx6 = (grid_mode & VFM_PREPARE_MX6) != 0 && mx6_width(d);              // int8 + fp6 image from one kernel
     const bool want_mx6_wide = (grid_mode & VFM_PREPARE_MX6) != 0 && !want_mx6 && mx6_half_width(d);   // d = 512, 768: kernels of their own
     grid_mode &= ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF);
@@ -1535,7 +1566,12 @@ int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows
                 const dim3 sg((unsigned)(persist ? prep_persist_grid(groups, st) : groups)), sb(256);
                 const PrepOut po1 = prep_out(p1, nullptr, h6), po2 = prep_out(p2, nullptr, h6);
 #define VFM_PREP_ONCE(D_, H_, P_) hipLaunchKernelGGL((prep_once_kernel<D_, H_, P_>), sg, sb, 0, st, x1, rows1, po1, g1, x2, rows2, po2, groups, zero)
-                if (d == 384) {
+                if (no_i8) {
+#define VFM_PREP_ONCE_NOI8(D_, P_) hipLaunchKernelGGL((prep_once_kernel<D_, true, P_, true>), sg, sb, 0, st, x1, rows1, po1, g1, x2, rows2, po2, groups, zero)
+                    if (d == 384) { if (persist) VFM_PREP_ONCE_NOI8(384, true); else VFM_PREP_ONCE_NOI8(384, false); }
+                    else          { if (persist) VFM_PREP_ONCE_NOI8(256, true); else VFM_PREP_ONCE_NOI8(256, false); }
+#undef VFM_PREP_ONCE_NOI8
+                } else if (d == 384) {
                     if (h6) { if (persist) VFM_PREP_ONCE(384, true, true); else VFM_PREP_ONCE(384, true, false); }
                     else    { if (persist) VFM_PREP_ONCE(384, false, true); else VFM_PREP_ONCE(384, false, false); }
                 } else {

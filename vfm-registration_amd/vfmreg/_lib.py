@@ -233,6 +233,13 @@ class using:
         return False
 
 
+def policy(key: str) -> int:
+    """What the library's entry points would read for ``key`` if called from this thread now (its bound Config, or the factory setting)."""
+    v = c_i64()
+    check(load().vfm_config_get(None, key.encode(), C.byref(v)), f"config_get({key})")
+    return int(v.value)
+
+
 def thread_config() -> Config:
     """The calling thread's Config, created and bound on first use: what the tools' ``lib.vfm_debug_set_*`` names write to."""
     cfg = current()

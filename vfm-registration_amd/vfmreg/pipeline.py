@@ -240,6 +240,15 @@ class RegistrationPipeline:
         # the coarse call is told so (VFM_RECORDS_WS_CLEAN): no fill between "preparation finished" and "coarse kernel starts", the one
         # place of the cycle where nothing else can run.  False: the coarse call fills for itself, as before (A/B runs)
         self._ws_clean = True
+        # VFM_RECORDS_MX6_HALF_FUSED without the int8 image (VFM_PREPARE_NO_I8 + VFM_RECORDS_NO_I8, include/vfmreg.h): where the search runs as
+        # that kind inside the library (d = 256 / 384, more than 2048 queries, four queries per map chunk) and the one-read preparation is
+        # the form in use; per registration under the conditions of `_ws_clean`, and only while the policy key "half_noi8" is 1.
+        # `auto` only: when such a search's guard goes up (descriptors that are all alike) its queries are decided by the all-pairs kernel
+        # -- tens of milliseconds --, and it is `auto`'s feedback that leaves kind 8 after that search; a pinned "mx6-half" has no way out
+        # and keeps the int8 image, whose gate pass bounds such a registration at a few milliseconds
+        self._noi8_shape = coarse == "auto" and d in (256, 384) and n > 2048 and n >= 4 * ((m + 127) // 128)
+        self.last_prep_schedule: Optional[int] = None   # `schedule` of the last registration's vfm_match_prepare2_gated_* call (None: another call)
+        self.last_records: Optional[int] = None         # record kind of the last registration's search, option bits included (None: fp16 pass)
 
     def prepare_map(self, b_desc: torch.Tensor) -> None:
         """IndexFlatIP.add: normalise + convert the map once (it is immutable per scene); every buffer
@@ -440,6 +449,9 @@ class RegistrationPipeline:
         # the half-width probe runs its own coarse pass in r.sws between this pair's preparation and its coarse call
         probe = bool(i8 and self._probe_due and not self.half and len(self._pending) < 8)
         ws_clean = 0   # VFM_RECORDS_WS_CLEAN once this pair's preparation has cleared r.sws for its coarse call
+        no_i8 = 0      # VFM_RECORDS_NO_I8 once this pair has been prepared without the int8 image
+        self.last_prep_schedule = None
+        self.last_records = None
         if not (reuse_map and r.map_key == b_desc.data_ptr()):
             # (a map that will be reused keeps both images: the coarse pass may change between registrations)
             if i8 and not reuse_map:
@@ -456,6 +468,13 @@ class RegistrationPipeline:
                     # VFM_PREPARE_MX6_HALF: the half-width pass reads the first d / 2 columns of the fp6 image -- only those are
                     # converted, and no int8 half-width image is written (the probe that needs it runs outside this mode)
                     schedule |= 8 | 16
+                if (records == 8 and self._noi8_shape and self._ws_clean and not probe and not (f16q or f16b)
+                        and _lib.policy("half_noi8") == 1 and _lib.policy("prep_form") in (3, 4)):
+                    # nothing behind a kind-8 coarse pass needs the int8 image (the rescan runs on the fp6 half image): it is not written.
+                    # When the search's guard goes up, `auto` leaves kind 8 on that search's feedback and the next pair gets the image again.
+                    schedule |= 32   # VFM_PREPARE_NO_I8
+                    no_i8 = 0x200
+                self.last_prep_schedule = schedule
                 if f16q or f16b:
                     _lib.check(lib.vfm_match_prepare2_gated_t(b_desc.data_ptr(), int(f16b), self.m, r.bprep.data_ptr(), q_desc.data_ptr(), int(f16q),
                                                               self.n, r.qprep.data_ptr(), self.d, schedule, pst), "prepare(map + scan)")
@@ -486,8 +505,9 @@ class RegistrationPipeline:
             ev.record(main)
             self._pending.append((ev, slot, "probe"))
         if i8:
+            self.last_records = records | no_i8
             _lib.check(lib.vfm_match_search_coarse_gated_g(r.qprep.data_ptr(), self.n, r.bprep.data_ptr(), self.m, self.d,
-                                                           r.sws.data_ptr(), r.sws.numel(), records | ws_clean, gate, st), "search(coarse)")
+                                                           r.sws.data_ptr(), r.sws.numel(), records | ws_clean | no_i8, gate, st), "search(coarse)")
         else:
             # (VFM_RECORDS_F16 = 2: the fp16 pass explicitly -- the ungated calls route large searches to the int8 pass)
             _lib.check(lib.vfm_match_search_coarse_gated_r(r.qprep.data_ptr(), self.n, r.bprep.data_ptr(), self.m, self.d,
@@ -506,7 +526,7 @@ class RegistrationPipeline:
         if i8 and not (f16q or f16b):
             _lib.check(lib.vfm_match_search_finish_gated_r(q_desc.data_ptr(), r.qprep.data_ptr(), self.n, b_desc.data_ptr(),
                                                            r.bprep.data_ptr(), self.m, self.d, r.idx.data_ptr(), r.sim.data_ptr(),
-                                                           r.sws.data_ptr(), r.sws.numel(), gate, records, rst), "search(finish)")
+                                                           r.sws.data_ptr(), r.sws.numel(), gate, records | no_i8, rst), "search(finish)")
         if i8:
             if self.coarse == "auto" and len(self._pending) < 8:  # feedback: candidate chunks this search rescans
                 slot = self._slots.pop() if self._slots else torch.zeros(1, dtype=torch.int32).pin_memory()
