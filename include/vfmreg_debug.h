@@ -11,6 +11,7 @@
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
+ *   - vfm_debug_search_plan  reads the calling thread's vfm_config and nothing else; host memory only.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
  */
@@ -40,6 +41,15 @@ int vfm_prof_events_destroy(void *start, void *stop);
  * fit) and do not touch the device. */
 int vfm_debug_last_coarse_kernel(char *buf_host, int cap);
 int vfm_debug_coarse_kernel_names(char *buf_host, int cap);
+
+/* tests / callers' policy: what a search of these arguments would do under the calling thread's vfm_config, resolved by the same function
+ * the search entry points use -- `records` as passed to them (a kind, VFM_RECORDS_NO_I8 beside it or not), gated: the gated family or not.
+ * One line of text to buf_host[cap]:
+ *     pass=<f16-dense|f16-sparse|int8|fp6> kind=<the VFM_RECORDS_* value the search runs as, after every fallback; 2 for an fp16 pass>
+ *     half=<0|1> fused=<0|1> top2=<0|1> pilot=<0|1> bins=<0|1: the chunk-major rescan runs> no_i8=<0|1>
+ *     finish=<the kernels of the finish stage in launch order, separated by ','>
+ * A combination the search refuses fails here with the same error.  Host memory only: no device is touched. */
+int vfm_debug_search_plan(int records, int d, int64_t n, int64_t m, int gated, char *buf_host, int cap);
 
 /* counters of the last FAST search that used workspace `ws` (candidate histogram, refined / fallback queries;
  * see csrc/match_finish.hip).  out64_host: HOST int32[64].  Synchronises the device. */

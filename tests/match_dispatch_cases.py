@@ -1,7 +1,7 @@
 """The dispatch tree of the matcher's coarse pass as a table of cases, and one adversarial data set for all of them.
 
-Which coarse kernel a search launches is decided at call time (csrc/match_api.hip: do_search_coarse, use_i8, use_sparse,
-effective_records; the launchers at the end of csrc/match_coarse_f16.hip, _i8.hip and _mx6.hip) from the width, the record kind, gated or
+Which coarse kernel a search launches is decided at call time (csrc/match_internal.h: resolve_search; csrc/match_api.hip:
+do_search_coarse, use_i8, use_sparse; the launchers at the end of csrc/match_coarse_f16.hip, _i8.hip and _mx6.hip) from the width, the record kind, gated or
 not, size thresholds and the thread's vfm_config.  Every case below names the kernel the launchers' rules give for it, with the rule
 beside it; tests/test_gpu_coarse_dispatch.py runs each case, reads back which kernel ran (vfm_debug_last_coarse_kernel) and compares
 the answers with the fp64 oracle; tests/test_coarse_dispatch_table.py checks that the table names every launcher instantiation in the
@@ -244,7 +244,7 @@ _add("gated", 384, N_HI, M, HALF, _variant(12), _i8(6, 4, 0, 0))
 for d, n_small in ((256, N_LO), (384, N_EDGE), (512, N_LO), (640, N_EDGE), (768, N_LO)):
     _add("gated", d, N_HI, M, HALF, (), _i8q2(d // 64, 0, 0, 0))
     _add("gated", d, n_small, M, HALF, (), _i8(d // 64, 4, 0, 0))
-# ... with the selection fused into the kernel (effective_records: d = 256 / 384, n > 2048, n >= 4 chunks)
+# ... with the selection fused into the kernel (resolve_search: d = 256 / 384, n > 2048, n >= 4 chunks)
 _add("gated", 256, N_HI, M, HALF_FUSED, (), _i8q2(4, 0, 0, 1))
 _add("gated", 384, N_HI, M, HALF_FUSED, (), _i8q2(6, 0, 0, 1))
 
@@ -252,7 +252,7 @@ _add("gated", 384, N_HI, M, HALF_FUSED, (), _i8q2(6, 0, 0, 1))
 for d in (256, 384):
     _add("gated", d, N_HI, M, MX6, (), _mx6(d // 64, "BEST", 1, d // 64))
     _add("gated", d, N_HI, M, MX6_TOP2, (), _mx6(d // 64, "TOP2", 1, d // 64))
-    # n = 2113 >= 4 x 33 chunks with rows: the fused full-width form stays (effective_records)
+    # n = 2113 >= 4 x 33 chunks with rows: the fused full-width form stays (resolve_search)
     _add("gated", d, N_HI, M, MX6_FUSED, (), _mx6(d // 64, "FUSE", 0, d // 64))
 for d in (256, 384, 512, 768):
     _add("gated", d, N_HI, M, MX6_HALF, (), _mx6(d // 128, "BEST", 0, d // 64))
@@ -273,8 +273,8 @@ _add("gated", 256, N_HI, M, MX6_HALF_FUSED, _variant(30), _mx6(2, "FUSE", 0, 4))
 
 assert len({c.id for c in CASES}) == len(CASES)
 
-# The fused kinds where the two chunk counts disagree: effective_records keeps a fused kind from n >= 4 x (chunks that hold rows) on, the
-# finish stage chose the chunk-major rescan from n >= 4 x (chunks of the map padded to 256 rows) on.  65 600 rows are 513 chunks with
+# The fused kinds where the two chunk counts disagree: a fused kind is kept from n >= 4 x chunks_with_rows(m) on, the finish stage
+# used to choose the chunk-major rescan from n >= 4 x chunks_padded(m) (the map padded to 256 rows) on.  65 600 rows are 513 chunks with
 # rows and 514 padded ones; 2053 queries lie between 4 x 513 and 4 x 514.  (Until this table existed the finish stage then left the
 # survivors the coarse kernel had binned unread, and every match came back as "below the gate".)
 M_ODD, N_BETWEEN = 65600, 2053

@@ -279,6 +279,47 @@ def test_a_full_bin_leaves_whole_chunk_entries_that_the_fp64_decision_scores():
     assert _fb_count(ws, n, m)[7] == 0
 
 
+def test_a_duplicate_rich_chunk_overflows_the_hit_staging_of_the_fp6_rescan():
+    """d = 256, n = 2304, m = 4096 (32 chunks, n >= 4 x 32: kind 8 is kept).  All 128 rows of chunk 3 are near-copies of one row with 48
+    queries aimed at it: 32 queries x 128 rows = 4096 hits in one block of match_rescan_chunk_mx6h_kernel against 1024 staged -- hits
+    are appended on the spot and the staging buffer is flushed inside the loop.  k rows of chunk 7 are near-copies of another row with
+    40 queries aimed at it (1600 hits; k + the rest of such a query's list stays under the list's capacity, so these are decided from
+    their lists).  Answers: the fp64 all-pairs oracle's wherever its similarity reaches 0.8, the gate contract elsewhere, and bit-equal
+    to the same search with the int8 image."""
+    d, n, m = 256, 2304, 4096
+    lay, cap, _ = workspace_layout(n, m)
+    k = min(40, cap - 16)
+    assert n >= 4 * (m // 128) and k == 40
+    rng = np.random.default_rng(8)
+    b = rng.standard_normal((m, d)).astype(np.float32)
+    q = rng.standard_normal((n, d)).astype(np.float32)           # the odd queries stay unrelated
+    pick = rng.integers(8 * 128, m, n // 2)                      # the planted half, on rows outside the two crowded chunks
+    q[::2] = b[pick] + 0.25 * rng.standard_normal((n // 2, d)).astype(np.float32)
+    r0, r1 = rng.standard_normal((2, d)).astype(np.float32)
+    b[3 * 128:4 * 128] = r0 + 1e-3 * rng.standard_normal((128, d)).astype(np.float32)
+    b[7 * 128:7 * 128 + k] = r1 + 1e-3 * rng.standard_normal((k, d)).astype(np.float32)
+    group3, group7 = np.arange(1, 97, 2), np.arange(101, 181, 2)
+    q[group3] = r0 + 0.05 * rng.standard_normal((48, d)).astype(np.float32)
+    q[group7] = r1 + 0.05 * rng.standard_normal((40, d)).astype(np.float32)
+    qn, _ = orc.l2norm_rows(q)
+    bn, _ = orc.l2norm_rows(b)
+    ridx, rsim = orc.match_ip_top1_bruteforce(qn, bn)            # fp64 over all pairs, ties to the lowest index
+    assert (ridx[group3] // 128 == 3).all() and (ridx[group7] // 128 == 7).all() and (rsim[group7] > 0.99).all()
+    qd, bd = torch.from_numpy(q).cuda(), torch.from_numpy(b).cuda()
+    idx, sim, _, _, ws = _search(qd, bd, True)
+    solved = _gate_contract(idx, sim, ridx, rsim, GATE)
+    assert solved[rsim >= 0.8].all() and solved[group3].all() and solved[group7].all()
+    ref_idx, ref_sim, _, _, _ = _search(qd, bd, False)
+    assert torch.equal(idx, ref_idx) and torch.equal(sim.view(torch.int32), ref_sim.view(torch.int32))
+    fb = _fb_count(ws, n, m)
+    assert fb[7] == 0, "the guard is up"
+    fb_list = _view(ws, lay, "fb_list", torch.int32).cpu().numpy()[:fb[0]]
+    assert not np.isin(group7, fb_list).any()
+    # every row of chunk 3 is a hit for each of its 48 queries: 6144 hits in the bin's two blocks, at least 3072 in one of them
+    hit_cnt = _view(ws, lay, "hit_cnt", torch.int32).cpu().numpy()[::32]
+    assert (hit_cnt[group3] >= 128).all() and (hit_cnt[group7] >= k).all()
+
+
 def test_descriptors_that_are_all_alike_raise_the_guard_and_the_exact_kernel_decides_every_query():
     d, n, m = 384, N, 1024
     rng = np.random.default_rng(6)

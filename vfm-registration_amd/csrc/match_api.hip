@@ -11,7 +11,6 @@
 
 namespace vfmm {
 
-
 int choose_slices(int nqb, int nchunks) {
     if (vfm_cfg().force_slices > 0) return vfm_cfg().force_slices < nchunks ? vfm_cfg().force_slices : nchunks;
     // Fill 256 CUs with whole "rounds" of workgroups (tail efficiency).  Every (query block, slice) unit re-reads its 256
@@ -86,6 +85,12 @@ bool use_i8(int d, int64_t n, int64_t m, bool gated) {
            (vfm_cfg().coarse_qsets == 0 || vfm_cfg().coarse_qsets == 10 || vfm_cfg().coarse_qsets == 12);
 }
 
+// does a search of this kind and shape run on the int8 or the fp6 image (the plan's pass, for callers that want nothing else of it)
+static bool runs_quantised(int records, int d, int64_t n, int64_t m, bool gated) {
+    SearchPlan plan;
+    return resolve_search(plan, records & ~VFM_RECORDS_NO_I8, d, n, m, gated, true) == VFM_OK && plan.quantised();
+}
+
 // queries per workgroup of the coarse kernel that do_search_coarse will launch
 int coarse_qblock(int d) { return d > 512 ? 128 : QBLOCK; }
 
@@ -121,14 +126,9 @@ CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, 
 // vfm_match_prepare2_gated_z, nothing has used the workspace since) -- no fill is issued
 int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, hipStream_t st,
                      bool bias_from_map_inv, bool inner_product, bool gated, int records, float gate, bool ws_clean) {
-    // VFM_RECORDS_NO_I8: an option beside the kind; the kind must run as VFM_RECORDS_MX6_HALF_FUSED -- any other reads the int8 image
-    const bool no_i8 = (records & VFM_RECORDS_NO_I8) != 0;
-    records &= ~VFM_RECORDS_NO_I8;
-    if (no_i8 && !(inner_product && records == VFM_RECORDS_MX6_HALF_FUSED && use_i8(d, n, m, gated) && gated &&
-                   effective_records(records, d, n, m) == VFM_RECORDS_MX6_HALF_FUSED && mx6_width(d)))
-        return vfm_fail(VFM_EINVAL, "search_coarse: VFM_RECORDS_NO_I8 needs a search that runs as VFM_RECORDS_MX6_HALF_FUSED at d = 256 / 384 (records %d, n %lld, m %lld, d %d)",
-                        records, (long long)n, (long long)m, d);
-    if (no_i8 && !(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_coarse: VFM_RECORDS_MX6_HALF_FUSED needs a finite gate");
+    SearchPlan plan;
+    VFM_TRY(resolve_search(plan, records, d, n, m, gated, inner_product));
+    VFM_TRY(check_plan_gate(plan.fused, gate, "search_coarse"));
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
@@ -137,8 +137,7 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
         if (d != 640 && d != 768) return vfm_fail(VFM_EINVAL, "row bias needs the 4-wave coarse kernel (K = 640 / 768), got %d", d);
         a.row_bias = B.inv;
     }
-    const bool i8 = inner_product && records != VFM_RECORDS_F16 && use_i8(d, n, m, gated);
-    if (inner_product && !i8 && use_sparse(d, n, m)) {
+    if (plan.pass == PASS_F16_SPARSE) {
         a.rec_cnt = w.rec_cnt;
         a.rec = w.rec;
         a.rcap = w.rcap;
@@ -150,54 +149,33 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
         }
     }
     if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.fb_count, 0, search_zero_bytes(n, m), st));  // fb_count | qmax | rec_cnt | bin_cnt
-    if (i8) {
-        if (!gated) records = VFM_RECORDS_TOP2;  // no feedback loop behind an ungated call: the robust record kind
-        records = effective_records(records, d, n, m);
-        if (records == VFM_RECORDS_HALF_FUSED || records == VFM_RECORDS_MX6_HALF_FUSED || records == VFM_RECORDS_MX6_FUSED) {
-            if (!(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_coarse: VFM_RECORDS_HALF_FUSED needs a finite gate");
-            a.gate = gate;
-            a.n_valid = n;
-            a.qrest = Q.rest;
-            a.grest = B.grest;
-            a.bin_cnt = w.bin_cnt;
-            a.bins = w.bins;
-            a.bin_cap = w.bin_cap;
-            a.cand_cnt = w.cand_cnt;
-            a.cand = w.cand;
-            a.cap = w.cap;
-            a.survivors = w.fb_count + 5;
-            a.surv = reinterpret_cast<unsigned*>(w.partials);   // the fp6 form: one slot per workgroup in the record buffer it does not write
-            if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.cand_cnt, 0, (size_t)a.npad * sizeof(int), st));  // lengths of the queries' own lists
-        }
-        const bool half = records == VFM_RECORDS_HALF || records == VFM_RECORDS_HALF_FUSED;   // the image of the first d / 2 columns
-        a.Qh = half ? Q.tiles8h : Q.tiles8;
-        a.Bh = half ? B.tiles8h : B.tiles8;
-        a.ib = I8Bounds{Q.err, Q.gstep, B.gstep, B.gerr, records == VFM_RECORDS_TOP2 ? 1 : 0};
-        if (records == VFM_RECORDS_MX6_PILOT) {   // the full-width fp6 pass, which also notes every query's best chunk
-            a.qbest = w.qbest;
-            records = VFM_RECORDS_MX6;
-        }
-        if (records == VFM_RECORDS_MX6 || records == VFM_RECORDS_MX6_TOP2 || records == VFM_RECORDS_MX6_HALF || records == VFM_RECORDS_MX6_HALF_FUSED ||
-            records == VFM_RECORDS_MX6_FUSED) {
-            // the fp6 image and its bounds (operands prepared with VFM_PREPARE_MX6)
-            a.Qh = Q.tiles6;
-            a.Bh = B.tiles6;
-            const bool fuse6 = records == VFM_RECORDS_MX6_HALF_FUSED, fusefull = records == VFM_RECORDS_MX6_FUSED;
-            a.ib = (fuse6 || records == VFM_RECORDS_MX6_HALF) ? mx6_bounds_half(Q, B) : mx6_bounds(Q, B, records == VFM_RECORDS_MX6_TOP2 ? 1 : 0);
-            return launch_coarse_mx6(a, d, records == VFM_RECORDS_MX6_TOP2, records == VFM_RECORDS_MX6_HALF || fuse6, fuse6 || fusefull, st);
-        }
-        return launch_coarse_int8(a, d, n, records, st);
+    if (!plan.quantised()) return launch_coarse_f16(a, d, st);
+    if (plan.fused) {
+        a.gate = gate;
+        a.n_valid = n;
+        a.qrest = Q.rest;
+        a.grest = B.grest;
+        a.bin_cnt = w.bin_cnt;
+        a.bins = w.bins;
+        a.bin_cap = w.bin_cap;
+        a.cand_cnt = w.cand_cnt;
+        a.cand = w.cand;
+        a.cap = w.cap;
+        a.survivors = w.fb_count + 5;
+        a.surv = reinterpret_cast<unsigned*>(w.partials);   // the fp6 form: one slot per workgroup in the record buffer it does not write
+        if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.cand_cnt, 0, (size_t)a.npad * sizeof(int), st));  // lengths of the queries' own lists
     }
-    return launch_coarse_f16(a, d, st);
+    a.ib = plan_bounds(plan, Q, B);
+    if (plan.pass == PASS_MX6) {   // the fp6 image and its bounds (operands prepared with VFM_PREPARE_MX6)
+        a.Qh = Q.tiles6;
+        a.Bh = B.tiles6;
+        if (plan.pilot) a.qbest = w.qbest;   // the full-width pass also notes every query's best chunk
+        return launch_coarse_mx6(a, d, plan.top2, plan.half, plan.fused, st);
+    }
+    a.Qh = plan.half ? Q.tiles8h : Q.tiles8;   // (half: the image of the first d / 2 columns)
+    a.Bh = plan.half ? B.tiles8h : B.tiles8;
+    return launch_coarse_int8(a, d, n, plan.kind, st);
 }
-
-int do_search(const float* q, const void* qprep, int64_t n, const float* b, const void* bprep, int64_t m, int d,
-              int64_t* idx_out, float* sim_out, void* ws, hipStream_t st) {
-    const int rc = do_search_coarse(qprep, n, bprep, m, d, ws, st, false, true);
-    if (rc) return rc;
-    return do_search_finish(q, qprep, n, b, bprep, m, d, idx_out, sim_out, ws, st);
-}
-
 
 }  // namespace vfmm
 
@@ -223,7 +201,7 @@ VFM_EXPORT int vfm_match_prepare2_gated(const float* x1, int64_t rows1, void* pr
     VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
     // (map, scan): where the gated search of x2 in x1 runs the int8 pass, the fp16 image is never read
-    const bool want_f16 = !use_i8(d, rows2, rows1, true);
+    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16);
 }
 
@@ -244,7 +222,7 @@ VFM_EXPORT int vfm_match_prepare2_gated_p(const float* x1, int64_t rows1, void* 
                       (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
                   "prepare2: unknown schedule %d", schedule);
     if (int rc = check_no_i8(schedule, d)) return rc;
-    const bool want_f16 = !use_i8(d, rows2, rows1, true);
+    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule);
 }
 
@@ -263,7 +241,7 @@ VFM_EXPORT int vfm_match_prepare2_gated_z(const float* x1, int64_t rows1, void* 
     if (int rc = check_no_i8(schedule, d)) return rc;
     VFM_CHECK_ARG(n > 0 && m > 0 && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "prepare2: bad search size (n=%lld m=%lld)", (long long)n, (long long)m);
     if (ws_bytes < carve_search(nullptr, n, m).bytes) return vfm_fail(VFM_EWORKSPACE, "prepare2: search workspace too small");
-    const bool want_f16 = !use_i8(d, rows2, rows1, true);
+    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
     return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule, prep_zero(ws, n, m));
 }
 
@@ -278,7 +256,7 @@ VFM_EXPORT int vfm_match_prepare2_gated_t(const void* x1, int dtype1, int64_t ro
                       (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
                   "prepare2: unknown schedule %d", schedule);
     VFM_CHECK_ARG(!(schedule & VFM_PREPARE_NO_I8), "prepare2: VFM_PREPARE_NO_I8 is for fp32 rows (vfm_match_prepare2_gated_p / _z)");
-    const bool want_f16 = !use_i8(d, rows2, rows1, true);
+    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
     return do_prepare2(Rows(x1, dtype1 == VFM_ROWS_F16), rows1, prepared1, Rows(x2, dtype2 == VFM_ROWS_F16), rows2, prepared2, d,
                        (hipStream_t)stream, want_f16, schedule);
 }
@@ -288,22 +266,20 @@ VFM_EXPORT size_t vfm_match_search_workspace_bytes(int64_t n, int64_t m, int d) 
     return carve_search(nullptr, n, m).bytes;
 }
 
-VFM_EXPORT int vfm_match_search_prepared(const float* q, const void* q_prepared, int64_t n, const float* b,
-                                         const void* b_prepared, int64_t m, int d, int64_t* idx_out, float* sim_out,
-                                         void* ws, size_t ws_bytes, vfm_stream_t stream) {
-    VFM_CHECK_ARG(n > 0 && m > 0, "search: empty operand (n=%lld m=%lld)", (long long)n, (long long)m);
-    VFM_CHECK_ARG(d % 128 == 0 && d >= 128 && d <= 768, "search: d must be in {128,256,384,512,640,768}");
-    VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "search: more than 2^31 rows");
-    if (ws_bytes < vfm_match_search_workspace_bytes(n, m, d)) return vfm_fail(VFM_EWORKSPACE, "search: workspace too small");
-    return do_search(q, q_prepared, n, b, b_prepared, m, d, idx_out, sim_out, ws, (hipStream_t)stream);
-}
-
 static int check_search_args(int64_t n, int64_t m, int d, size_t ws_bytes) {
     VFM_CHECK_ARG(n > 0 && m > 0, "search: empty operand (n=%lld m=%lld)", (long long)n, (long long)m);
     VFM_CHECK_ARG(d % 128 == 0 && d >= 128 && d <= 768, "search: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "search: more than 2^31 rows");
     if (ws_bytes < vfm_match_search_workspace_bytes(n, m, d)) return vfm_fail(VFM_EWORKSPACE, "search: workspace too small");
     return VFM_OK;
+}
+
+VFM_EXPORT int vfm_match_search_prepared(const float* q, const void* q_prepared, int64_t n, const float* b,
+                                         const void* b_prepared, int64_t m, int d, int64_t* idx_out, float* sim_out,
+                                         void* ws, size_t ws_bytes, vfm_stream_t stream) {
+    VFM_TRY(check_search_args(n, m, d, ws_bytes));
+    VFM_TRY(do_search_coarse(q_prepared, n, b_prepared, m, d, ws, (hipStream_t)stream, false, true));
+    return do_search_finish(q, q_prepared, n, b, b_prepared, m, d, idx_out, sim_out, ws, (hipStream_t)stream);
 }
 
 VFM_EXPORT int vfm_match_search_coarse(const void* q_prepared, int64_t n, const void* b_prepared, int64_t m, int d,
@@ -372,7 +348,7 @@ VFM_EXPORT int vfm_match_search_finish_gated_t(const void* q, int dtype_q, const
     VFM_CHECK_ARG(gate == gate, "search_finish: gate is NaN");
     VFM_CHECK_ARG(records >= VFM_RECORDS_BEST && records <= VFM_RECORDS_MX6_FUSED, "search_finish: unknown record kind %d", records);
     VFM_CHECK_ARG((dtype_q == VFM_ROWS_F32 || dtype_q == VFM_ROWS_F16) && (dtype_b == VFM_ROWS_F32 || dtype_b == VFM_ROWS_F16), "search_finish: unknown row type");
-    VFM_CHECK_ARG((dtype_q == VFM_ROWS_F32 && dtype_b == VFM_ROWS_F32) || (records != VFM_RECORDS_F16 && use_i8(d, n, m, true)),
+    VFM_CHECK_ARG((dtype_q == VFM_ROWS_F32 && dtype_b == VFM_ROWS_F32) || runs_quantised(records, d, n, m, true),
                   "search_finish: fp16 rows are taken by the int8 / fp6 searches only");
     return do_search_finish(Rows(q, dtype_q == VFM_ROWS_F16), q_prepared, n, Rows(b, dtype_b == VFM_ROWS_F16), b_prepared, m, d, idx_out, sim_out,
                             ws, (hipStream_t)stream, true, gate, records);
@@ -390,13 +366,15 @@ VFM_EXPORT int vfm_match_search_probe_half(const void* q_prepared, int64_t n, co
     if (int rc = check_search_args(n, m, d, ws_bytes)) return rc;
     VFM_CHECK_ARG(q_prepared && b_prepared && ws && out_host, "probe_half: null pointer");
     VFM_CHECK_ARG(gate > -__builtin_inff(), "probe_half: needs a finite gate");
-    if (!(use_i8(d, n, m, true) && half_capable(d, n))) {  // no half-width kernel for this shape: "everything survives"
+    SearchPlan plan;
+    VFM_TRY(resolve_search(plan, VFM_RECORDS_HALF, d, n, m, true, true));
+    if (plan.kind != VFM_RECORDS_HALF) {  // no half-width kernel for this shape: "everything survives"
         *out_host = INT32_MAX;
         return VFM_OK;
     }
     hipStream_t st = (hipStream_t)stream;
     if (int rc = do_search_coarse(q_prepared, n, b_prepared, m, d, ws, st, false, true, true, VFM_RECORDS_HALF)) return rc;
-    if (int rc = probe_half_select(q_prepared, n, b_prepared, m, d, ws, gate, st)) return rc;
+    if (int rc = probe_half_select(plan, q_prepared, n, b_prepared, m, d, ws, gate, st)) return rc;
     SearchWs w = carve_search(ws, n, m);
     VFM_CHECK_HIP(hipMemcpyAsync(out_host, w.fb_count + 5, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     return VFM_OK;
@@ -424,7 +402,7 @@ static int ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, 
     void* bprep = p + vfm_match_prepared_bytes(n, d);
     void* sws = p + vfm_match_prepared_bytes(n, d) + vfm_match_prepared_bytes(m, d);
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "match: more than 2^31 rows");
-    int rc = do_prepare2(b, m, bprep, q, n, qprep, d, st, !use_i8(d, n, m, gated));
+    int rc = do_prepare2(b, m, bprep, q, n, qprep, d, st, !runs_quantised(VFM_RECORDS_TOP2, d, n, m, gated));
     if (rc) return rc;
     // one-shot calls have no feedback loop: packed top-2 records, the robust kind (real lifted descriptors are duplicate-rich)
     rc = do_search_coarse(qprep, n, bprep, m, d, sws, st, false, true, gated, VFM_RECORDS_TOP2);
@@ -541,10 +519,6 @@ VFM_EXPORT int vfm_debug_mx6_half_err(const void* prepared, int64_t rows, int d,
     return VFM_OK;
 }
 
-
-
-
-
 // The coarse kernel most recently launched from the calling thread, as its launcher instantiation spells itself ("" if none), and the
 // sorted, newline-separated list of every such name in the library.  Host memory only.
 static int copy_out(const std::string& s, char* buf_host, int cap, const char* what) {
@@ -563,6 +537,19 @@ VFM_EXPORT int vfm_debug_coarse_kernel_names(char* buf_host, int cap) {
     std::string all;
     for (const std::string& s : names) all += (all.empty() ? "" : "\n") + s;
     return copy_out(all, buf_host, cap, "coarse_kernel_names");
+}
+
+// The plan of a search (match_internal.h, resolve_search) as one line of text; a refused combination fails as the search would.
+VFM_EXPORT int vfm_debug_search_plan(int records, int d, int64_t n, int64_t m, int gated, char* buf_host, int cap) {
+    VFM_CHECK_ARG(n > 0 && m > 0 && d % 128 == 0 && d >= 128 && d <= 768, "search_plan: bad shape (n=%lld m=%lld d=%d)", (long long)n, (long long)m, d);
+    SearchPlan plan;
+    VFM_TRY(resolve_search(plan, records, d, n, m, gated != 0, true));
+    static const char* const pass[] = {"f16-dense", "f16-sparse", "int8", "fp6"};
+    std::string line = std::string("pass=") + pass[plan.pass] + " kind=" + std::to_string(plan.kind) + " half=" + std::to_string(plan.half) +
+                       " fused=" + std::to_string(plan.fused) + " top2=" + std::to_string(plan.top2) + " pilot=" + std::to_string(plan.pilot) +
+                       " bins=" + std::to_string(plan.use_bins) + " no_i8=" + std::to_string(plan.no_i8) + " finish=";
+    for (int i = 0; i < plan.nsteps; ++i) line += (i ? "," : "") + std::string(finish_step_name(plan.steps[i]));
+    return copy_out(line, buf_host, cap, "search_plan");
 }
 
 VFM_EXPORT int vfm_prof_events_create(void** start, void** stop) {

@@ -401,7 +401,7 @@ int launch_coarse_int8(CoarseArgs& a, int d, int64_t n, int records, hipStream_t
     if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
     const bool top2 = records == VFM_RECORDS_TOP2;
     int rc8;
-    if (records == VFM_RECORDS_HALF_FUSED) {   // d = 256 / 384, more than 2048 queries (effective_records)
+    if (records == VFM_RECORDS_HALF_FUSED) {   // d = 256 / 384, more than 2048 queries (resolve_search)
         a.nqb = (a.nq_tiles + 15) / 16;
         a.nslices = choose_slices(a.nqb, a.nchunks);
         rc8 = d == 384 ? launch_coarse_i8q2<6, false, false, true>(a, st) : launch_coarse_i8q2<4, false, false, true>(a, st);

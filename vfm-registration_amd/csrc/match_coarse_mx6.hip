@@ -41,35 +41,12 @@
 namespace vfmm {
 namespace {
 
-typedef int intx8 __attribute__((ext_vector_type(8)));
-
-// one lane's operand of a k-step: 32 e2m3 codes in six registers (the instruction reads v[n:n+5] for fp6)
-struct Mx6Frag {
-    int c[6];
-};
 // k-step s of the tile whose code planes start at pa (this lane's 16-byte slot of plane A) / pb (its 8-byte slot of plane B)
 __device__ __forceinline__ Mx6Frag mx6_frag(const unsigned char* pa, const unsigned char* pb, int s) {
     const uint4 lo = *reinterpret_cast<const uint4*>(pa + s * MX6_KSTEP_BYTES);
     const uint2 hi = *reinterpret_cast<const uint2*>(pb + s * MX6_KSTEP_BYTES);
     return Mx6Frag{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}};
 }
-template <int S>
-__device__ __forceinline__ floatx16 mfma_mx6(const Mx6Frag& x, const uint2& xs, const Mx6Frag& y, const uint2& ys, floatx16 c) {
-    intx8 a, b;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        a[i] = x.c[i];
-        b[i] = y.c[i];
-    }
-    a[6] = a[7] = b[6] = b[7] = 0;   // not read: cbsz = blgp = 2 (e2m3) takes six registers per operand
-#ifdef VFM_ABL_NOSCALE   // (timing experiment, tools/ablate6.py: the unscaled instruction -- results are garbage)
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, 0, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, S & 3, (int)(S < 4 ? xs.x : xs.y), S & 3,
-                                                           (int)(S < 4 ? ys.x : ys.y));
-#endif
-}
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt_n() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -586,7 +563,7 @@ static_assert(MX6_LCAP + 1 + 3 == MX6_SURV_SLOT_WORDS, "carve_search sizes the s
 int mx6_survivor_slot_words() { return MX6_SURV_SLOT_WORDS; }
 
 // the fp6 coarse kernel for the arguments do_search_coarse prepared (a.Qh / a.Bh = the fp6 tiles, a.ib = mx6_bounds);
-// d = 256 / 384 (full width) or 256 / 384 / 512 / 768 (half width) and more than 2048 queries (effective_records)
+// d = 256 / 384 (full width) or 256 / 384 / 512 / 768 (half width) and more than 2048 queries (resolve_search)
 int launch_coarse_mx6(CoarseArgs& a, int d, bool top2, bool half, bool fuse, hipStream_t st) {
     const bool ns3 = half && fuse && d == 384 && vfm_cfg().mx6_ns3 && vfm_cfg().mx6_t4;
     a.nqb = ns3 ? (a.nq_tiles + 23) / 24 : (a.nq_tiles + 15) / 16;

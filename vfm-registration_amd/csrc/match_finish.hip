@@ -723,6 +723,82 @@ __global__ __launch_bounds__(64 * SELECT_BEST_WAVES) void match_select_best_kern
 // block for all of its hits).  Same integers, same hit test, hence the same rows as the v_dot4 loop it replaces (24 LDS reads +
 // 96 dot4 per query and wave: 26 us at C2's 9891 candidates but 0.7 ms at the 220 000 of an ungated Euclidean search).
 constexpr int RESCAN_LHITS = 1024;   // rows a workgroup of match_rescan_chunk_kernel stages in the LDS before it touches the lists (1024: 13 KB of static LDS beside the 39 KB ring at d = 384 -- three workgroups per compute unit instead of two)
+// ---- the frame of the two chunk-major rescans (this kernel and match_rescan_chunk_mx6h_kernel): the workgroup's slice of its chunk's
+// bin, and its hits, staged: the global side (a returning atomic on the query's list length, then the entry) is done for all of
+// them at once.  The scoring and the hit test between the two are each kernel's own.
+struct RescanStage {
+    int lbin[RESCAN_SLICE];
+    int lhq[RESCAN_LHITS];
+    unsigned char lhr[RESCAN_LHITS];
+    float lhu[RESCAN_LHITS];   // the row's upper bound (cand_up)
+    int lhit_n;
+};
+struct RescanLists {   // the queries' lists (SearchWs); handed on by value, restrict kept: the kernels' register counts stay what they were
+    int* __restrict__ cand_cnt;
+    unsigned* __restrict__ cand;
+    float* __restrict__ cand_up;
+    unsigned* __restrict__ hit_cnt;
+    int cap;
+};
+// the chunk row of accumulator element e of a lane whose element 0 is row rr0 = 32 wave + 4 (lane >> 5)
+__device__ __forceinline__ int chunk_row(int rr0, int e) { return rr0 + (e & 3) + 8 * (e >> 2); }
+// Prologue: workgroup (c, y) takes entries [y slice, y slice + nq) of chunk c's bin into S.lbin, padded to nblocks blocks of 32.
+// false: nothing to do (guard up: another kernel has decided every query; or the bin ends before this slice).
+__device__ __forceinline__ bool rescan_take_slice(RescanStage& S, const int* guard, const unsigned* bin_cnt, const int* bins, int bin_cap,
+                                                  int slice, int& nq, int& nblocks) {
+    const int c = blockIdx.x;
+    if (guard && *guard) return false;
+    const unsigned filled = bin_cnt[(size_t)c * BIN_CNT_STRIDE];
+    const int nall = filled < (unsigned)bin_cap ? (int)filled : bin_cap;
+    const int jbeg = blockIdx.y * slice;   // a long bin is shared by the workgroups (c, 0), (c, 1), ... (slice <= RESCAN_SLICE entries each)
+    if (jbeg >= nall) return false;
+    nq = nall - jbeg < slice ? nall - jbeg : slice;
+    nblocks = (nq + 31) >> 5;
+    if (threadIdx.x == 0) S.lhit_n = 0;
+    const int* bin = bins + (size_t)c * bin_cap + jbeg;
+    for (int t = threadIdx.x; t < nblocks * 32; t += 256) S.lbin[t] = t < nq ? bin[t] : 0;
+    return true;
+}
+// One row into query q's list.  (The list's length stays as the selection / match_rescan_kernel left it during the kernel; the appended
+// rows are counted in hit_cnt, a line of their own per query, and added by match_rescan_close_kernel.)
+__device__ __forceinline__ void rescan_append(const RescanLists L, int q, unsigned entry, float up) {
+    const int pos = L.cand_cnt[q] + (int)atomicAdd(&L.hit_cnt[(size_t)q * BIN_CNT_STRIDE], 1u);
+    if (pos < L.cap) {
+        L.cand[(size_t)q * L.cap + pos] = entry;
+        L.cand_up[(size_t)q * L.cap + pos] = up;
+    }
+}
+// hit number `at` of the workgroup (row rr of chunk c for query q): staged, or -- more hits than the staging buffer holds
+// (duplicate-rich chunk) -- appended on the spot
+__device__ __forceinline__ void rescan_stage_hit(RescanStage& S, const RescanLists L, int at, int q, int c, int rr, float up) {
+    if (at < RESCAN_LHITS) {
+        S.lhq[at] = q;
+        S.lhr[at] = (unsigned char)rr;
+        S.lhu[at] = up;
+    } else {
+        rescan_append(L, q, ((unsigned)c << 8) | (unsigned)rr, up);
+    }
+}
+// End of a block: a full staging buffer is emptied before the next block adds to it.  (lhit_n is read by every thread between two
+// barriers that no atomic of another block can cross, so the branch is uniform.)
+__device__ __forceinline__ void rescan_flush(RescanStage& S, const RescanLists L, int c, bool last) {
+    __syncthreads();
+    if (S.lhit_n > RESCAN_LHITS / 2 || last) {
+        wait_vmcnt<0>();   // (the atomics below are compiler-tracked: nothing of the ring may be pending behind them)
+        const int nh = S.lhit_n < RESCAN_LHITS ? S.lhit_n : RESCAN_LHITS;
+        for (int i = threadIdx.x; i < nh; i += 256) rescan_append(L, S.lhq[i], ((unsigned)c << 8) | (unsigned)S.lhr[i], S.lhu[i]);
+        __syncthreads();
+        if (threadIdx.x == 0) S.lhit_n = 0;
+    }
+}
+// grid of a chunk-major rescan: one workgroup per (chunk, slice of its bin).  Short workgroups: one that walks a whole bin (~600 queries
+// on lifted descriptors) lives ~80 us on 160 registers x 4 waves and 61 KB, and while a grid of those is resident nothing as
+// register-heavy as a ViT GEMM wave (156 - 416 registers) is placed beside it -- in C3 as a pipeline the feature stage of the next pair
+// stood still behind this kernel (tools/trace_c3_pipe.sh).
+inline dim3 rescan_chunk_grid(const SearchWs& w, int nchunks, int& slice) {
+    slice = vfm_cfg().finish_short ? 128 : RESCAN_SLICE;
+    return dim3((unsigned)nchunks, (unsigned)((w.bin_cap + slice - 1) / slice));
+}
 template <int KS>
 constexpr int rescan_ring_depth() { return KS <= 16 ? 3 : 2; }
 template <int KS>
@@ -747,27 +823,12 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_kernel(int64_t n, int6
     constexpr unsigned SLOT = (unsigned)rescan_slot_bytes<KS>();
     constexpr int TILE_U4 = KS * 64;
     constexpr int NG = KS / 4;      // gathered 1 KiB pieces per wave and block (KS % 4 == 0)
-    __shared__ int lbin[RESCAN_SLICE];
-    // The workgroup's hits, staged: the global side (a returning atomic on the query's list length, then the entry) is done
-    // for all of them at once behind the loop.
-    __shared__ int lhq[RESCAN_LHITS];
-    __shared__ unsigned char lhr[RESCAN_LHITS];
-    __shared__ float lhu[RESCAN_LHITS];   // the row's upper bound (cand_up)
-    __shared__ int lhit_n;
+    __shared__ RescanStage S;
+    const RescanLists L{cand_cnt, cand, cand_up, hit_cnt, cap};
     const int c = blockIdx.x;
-    if (guard && *guard) return;   // half-width pass, too many survivors: match_gatepass_kernel has decided every query
-    const unsigned filled = bin_cnt[(size_t)c * BIN_CNT_STRIDE];
-    const int nall = filled < (unsigned)bin_cap ? (int)filled : bin_cap;
-    const int jbeg = blockIdx.y * slice;   // a long bin is shared by the workgroups (c, 0), (c, 1), ... (slice <= RESCAN_SLICE entries each)
-    if (jbeg >= nall) return;
-    const int nq = nall - jbeg < slice ? nall - jbeg : slice;
-    const int nblocks = (nq + 31) >> 5;
+    int nq, nblocks;
+    if (!rescan_take_slice(S, guard, bin_cnt, bins, bin_cap, slice, nq, nblocks)) return;   // (guard: match_gatepass_kernel has decided every query)
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) lhit_n = 0;
-    {
-        const int* bin = bins + (size_t)c * bin_cap + jbeg;
-        for (int t = threadIdx.x; t < nblocks * 32; t += 256) lbin[t] = t < nq ? bin[t] : 0;
-    }
     intx4 af[KS];
     {
         const uint4* asrc = b8 + ((size_t)c * 4 + wave) * TILE_U4 + lane;
@@ -782,12 +843,12 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_kernel(int64_t n, int6
     const int rr0 = wave * 32 + 4 * (lane >> 5);   // + (e & 3) + 8 (e >> 2): the chunk row of accumulator element e
     float bn16[16];                                // Euclidean mode: |b~| of the lane's sixteen rows
 #pragma unroll
-    for (int e = 0; e < 16; ++e) bn16[e] = l2.qn ? l2.bn[base + rr0 + (e & 3) + 8 * (e >> 2)] : 0.0f;
+    for (int e = 0; e < 16; ++e) bn16[e] = l2.qn ? l2.bn[base + chunk_row(rr0, e)] : 0.0f;
     __syncthreads();   // (drains the loads above: from here on the vector-memory queue holds DMA only)
     const unsigned lds_base = (unsigned)(uintptr_t)(LDS_AS unsigned char*)rescan_smem;
     // terms of a slot, rows of 64 dwords: [0] cand_cnt | qerr, [1] qstep | qmax, [2] qn | -   (lanes 0-31 | 32-63)
     auto issue = [&](int blk) {
-        const int qi = lbin[blk * 32 + (lane & 31)];
+        const int qi = S.lbin[blk * 32 + (lane & 31)];
         const unsigned slot = lds_base + (unsigned)(blk % D) * SLOT;
         if (qrows) {   // row-major int8 scan (Prepared::rows8): unit (k-step s, half h) of query qi = bytes 32 s + 16 h .. of its row
             const unsigned char* rsrc = qrows + (size_t)qi * (KS * 32) + (size_t)(2 * wave + (lane >> 5)) * 16;
@@ -819,7 +880,7 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_kernel(int64_t n, int6
         const uint4* l_qf = reinterpret_cast<const uint4*>(slot);
         const int* lt = reinterpret_cast<const int*>(slot + (size_t)KS * 1024);
         const int j = blk * 32 + (lane & 31);
-        const int qi = lbin[j];
+        const int qi = S.lbin[j];
         const bool live = j < nq && lt[lane & 31] >= 0;   // (-2: below the gate, -1: already with the all-pairs kernel)
         const float eq = __int_as_float(lt[32 + (lane & 31)]);
         const float sc = __int_as_float(lt[64 + (lane & 31)]) * bstep;   // the same expressions as match_rescan_kernel: the same rows pass
@@ -841,7 +902,7 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_kernel(int64_t n, int6
             int smax = -0x7fffffff;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const int rr = chunk_row(rr0, e);
                 if (base + rr < m) smax = max(smax, acc[e]);
             }
             smax = max(smax, __shfl_xor(smax, 32));   // the two half-waves hold the same query's other rows
@@ -853,53 +914,24 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_kernel(int64_t n, int6
         if (live) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const int rr = chunk_row(rr0, e);
                 float up = sc * (float)acc[e] + bound;
                 if (l2.qn) up = l2_upper_row(qn, bn16[e], up, l2.slack);
                 if (base + rr < m && up >= qlow) hits |= 1u << e;
             }
         }
         if (hits) {
-            int at = atomicAdd(&lhit_n, __popc(hits));
+            int at = atomicAdd(&S.lhit_n, __popc(hits));
             while (hits) {
                 const int e = __ffs(hits) - 1;
                 hits &= hits - 1u;
-                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const int rr = chunk_row(rr0, e);
                 // (a Euclidean search's bound is not symmetric about the score: its rows are never filtered -- +Inf)
                 const float upe = l2.qn ? __builtin_inff() : sc * (float)acc[e] + bound;
-                if (at < RESCAN_LHITS) {
-                    lhq[at] = qi;
-                    lhr[at] = (unsigned char)rr;
-                    lhu[at] = upe;
-                } else {   // more hits than the staging buffer holds (duplicate-rich chunk): on the spot
-                    const int pos = cand_cnt[qi] + (int)atomicAdd(&hit_cnt[(size_t)qi * BIN_CNT_STRIDE], 1u);
-                    if (pos < cap) {
-                        cand[(size_t)qi * cap + pos] = ((unsigned)c << 8) | (unsigned)rr;
-                        cand_up[(size_t)qi * cap + pos] = upe;
-                    }
-                }
-                ++at;
+                rescan_stage_hit(S, L, at++, qi, c, rr, upe);
             }
         }
-        // (a full staging buffer is emptied before the next block adds to it; lhit_n is read by every thread between two barriers
-        // that no atomic of another block can cross, so the branch is uniform)
-        __syncthreads();
-        if (lhit_n > RESCAN_LHITS / 2 || blk + 1 == nblocks) {
-            wait_vmcnt<0>();   // (the atomics below are compiler-tracked: nothing of the ring may be pending behind them)
-            const int nh = lhit_n < RESCAN_LHITS ? lhit_n : RESCAN_LHITS;
-            for (int i = threadIdx.x; i < nh; i += 256) {
-                // (the list's length stays as the selection / match_rescan_kernel left it during this kernel; the appended rows are
-                // counted in hit_cnt, a line of their own per query, and added by match_rescan_close_kernel)
-                const int hq = lhq[i];
-                const int pos = cand_cnt[hq] + (int)atomicAdd(&hit_cnt[(size_t)hq * BIN_CNT_STRIDE], 1u);
-                if (pos < cap) {
-                    cand[(size_t)hq * cap + pos] = ((unsigned)c << 8) | (unsigned)lhr[i];
-                    cand_up[(size_t)hq * cap + pos] = lhu[i];
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) lhit_n = 0;
-        }
+        rescan_flush(S, L, c, blk + 1 == nblocks);
     }
 }
 
@@ -913,12 +945,9 @@ int launch_rescan_chunk_ks(const SearchWs& w, int nchunks, int64_t n, int64_t m,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_mark(attr_set);
     }
-    // Short workgroups: a workgroup that walks a whole bin (~600 queries on lifted descriptors) lives ~80 us on 160 registers x 4 waves
-    // and 61 KB, and while a grid of those is resident nothing as register-heavy as a ViT GEMM wave (156 - 416 registers) is placed
-    // beside it -- in C3 as a pipeline the feature stage of the next pair stood still behind this kernel (tools/trace_c3_pipe.sh).
-    const int slice = vfm_cfg().finish_short ? 128 : RESCAN_SLICE;
-    hipLaunchKernelGGL(match_rescan_chunk_kernel<KS>, dim3((unsigned)nchunks, (unsigned)((w.bin_cap + slice - 1) / slice)),
-                       dim3(256), lds, st, n, m, ib, (const uint4*)Q.tiles8, (const uint4*)B.tiles8, (const unsigned*)w.qmax, w.cand_cnt,
+    int slice;
+    const dim3 grid = rescan_chunk_grid(w, nchunks, slice);
+    hipLaunchKernelGGL(match_rescan_chunk_kernel<KS>, grid, dim3(256), lds, st, n, m, ib, (const uint4*)Q.tiles8, (const uint4*)B.tiles8, (const unsigned*)w.qmax, w.cand_cnt,
                        w.cand, w.cap, (const unsigned*)w.bin_cnt, (const int*)w.bins, use_gate, gate, guard, l2, w.bin_cap, w.hit_cnt, w.cand_up,
                        slice, vfm_cfg().rescan_rows ? (const unsigned char*)Q.rows8 : (const unsigned char*)nullptr, pilot ? w.qmax : (unsigned*)nullptr);
     VFM_CHECK_LAUNCH("match_rescan_chunk_kernel");
@@ -956,23 +985,6 @@ int launch_rescan_chunk(const SearchWs& w, int nchunks, int64_t n, int64_t m, in
 // Hits are single-row entries (chunk << 8 | row) with their upper bound in cand_up, staged in the LDS and counted through hit_cnt as
 // the int8 kernel's are: match_rescan_close_kernel is reused as it stands.  Rows at or beyond m never hit; guard up: nothing to do.
 // ---------------------------------------------------------------------------------------------
-typedef int finish_intx8 __attribute__((ext_vector_type(8)));
-// one lane's operand of a k-step of v_mfma_scale_f32_32x32x64_f8f6f4 in e2m3: 32 codes in six registers (match_coarse_mx6.hip)
-struct Mx6Frag {
-    int c[6];
-};
-template <int S>
-__device__ __forceinline__ floatx16 mfma_mx6(const Mx6Frag& x, unsigned xs, const Mx6Frag& y, unsigned ys, floatx16 c) {
-    static_assert(S >= 0 && S < 4, "the scales of k-steps 0 .. 3 are the four bytes of one register");
-    finish_intx8 a, b;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        a[i] = x.c[i];
-        b[i] = y.c[i];
-    }
-    a[6] = a[7] = b[6] = b[7] = 0;   // not read: cbsz = blgp = 2 (e2m3) takes six registers per operand
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, S, (int)xs, S, (int)ys);
-}
 constexpr int rescan6_depth() { return 3; }   // ring slots (blocks of 32 queries)
 // A ring slot: [KS6][64] x 16 B = code plane A of every k-step as the MFMA lanes read it, [KS6][2][64] x 4 B = code plane B as its two
 // dwords (LDS-DMA moves 4 or 16 bytes per lane: the 8-byte units of the stored plane arrive as two dword gathers), [64] x 4 B = the
@@ -996,28 +1008,15 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_mx6h_kernel(int64_t n,
     constexpr int NI = 3 * KS6 + 3;                   // DMA instructions per block: KS6 plane A, 2 KS6 plane B, scales, two rows of terms
     constexpr int NG = (NI + 3) / 4;                  // ... per wave (a wave past the end repeats the last one: the same bytes again)
     __shared__ __attribute__((aligned(16))) unsigned char ring[D * SLOT];
-    __shared__ int lbin[RESCAN_SLICE];
-    __shared__ int lhq[RESCAN_LHITS];
-    __shared__ unsigned char lhr[RESCAN_LHITS];
-    __shared__ float lhu[RESCAN_LHITS];   // the row's upper bound (cand_up)
-    __shared__ int lhit_n;
+    __shared__ RescanStage S;
+    const RescanLists L{cand_cnt, cand, cand_up, hit_cnt, cap};
     const int c = blockIdx.x;
-    if (guard && *guard) return;   // too many survivors: match_guard_fallback_kernel has sent every query to the all-pairs kernel
-    const unsigned filled = bin_cnt[(size_t)c * BIN_CNT_STRIDE];
-    const int nall = filled < (unsigned)bin_cap ? (int)filled : bin_cap;
-    const int jbeg = blockIdx.y * slice;   // a long bin is shared by the workgroups (c, 0), (c, 1), ... (slice <= RESCAN_SLICE entries each)
-    if (jbeg >= nall) return;
-    const int nq = nall - jbeg < slice ? nall - jbeg : slice;
-    const int nblocks = (nq + 31) >> 5;
+    int nq, nblocks;
+    if (!rescan_take_slice(S, guard, bin_cnt, bins, bin_cap, slice, nq, nblocks)) return;   // (guard: match_guard_fallback_kernel has sent every query to the all-pairs kernel)
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x == 0) lhit_n = 0;
-    {
-        const int* bin = bins + (size_t)c * bin_cap + jbeg;
-        for (int t = threadIdx.x; t < nblocks * 32; t += 256) lbin[t] = t < nq ? bin[t] : 0;
-    }
     // tile `wave` of the chunk: the first operand
     Mx6Frag af[KS6];
-    unsigned as;
+    uint2 as = make_uint2(0u, 0u);   // (.x: the scales of k-steps 0 .. 3, all this kernel multiplies)
     {
         const unsigned char* tile = b6 + ((size_t)c * 4 + wave) * (size_t)IMG_TB;
 #pragma unroll
@@ -1026,27 +1025,27 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_mx6h_kernel(int64_t n,
             const uint2 hi = *reinterpret_cast<const uint2*>(tile + mx6_code_b(s, lane));
             af[s] = Mx6Frag{{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y}};
         }
-        as = *reinterpret_cast<const unsigned*>(tile + mx6_scale_at(2 * KS6, 0, lane));
+        as.x = *reinterpret_cast<const unsigned*>(tile + mx6_scale_at(2 * KS6, 0, lane));
     }
     const long long base = (long long)c * CHUNK_ROWS;
     const int rr0 = wave * 32 + 4 * (lane >> 5);   // + (e & 3) + 8 (e >> 2): the chunk row of accumulator element e
     float be16[16], br16[16];                      // err6h / rest of the lane's sixteen rows (rows of the padded operand always exist)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        be16[e] = berr[base + rr0 + (e & 3) + 8 * (e >> 2)];
-        br16[e] = brest[base + rr0 + (e & 3) + 8 * (e >> 2)];
+        be16[e] = berr[base + chunk_row(rr0, e)];
+        br16[e] = brest[base + chunk_row(rr0, e)];
     }
     // everything loaded above is in its registers before the first DMA goes out: from here on the vector-memory queue holds DMA only
 #pragma unroll
     for (int s = 0; s < KS6; ++s) asm volatile("" ::"v"(af[s].c[0]), "v"(af[s].c[1]), "v"(af[s].c[2]), "v"(af[s].c[3]), "v"(af[s].c[4]), "v"(af[s].c[5]));
-    asm volatile("" ::"v"(as));
+    asm volatile("" ::"v"(as.x));
 #pragma unroll
     for (int e = 0; e < 16; ++e) asm volatile("" ::"v"(be16[e]), "v"(br16[e]));
     wait_vmcnt<0>();
     __syncthreads();
     const unsigned lds_base = (unsigned)(uintptr_t)(LDS_AS unsigned char*)ring;
     auto issue = [&](int blk) {
-        const int qi = lbin[blk * 32 + (lane & 31)];
+        const int qi = S.lbin[blk * 32 + (lane & 31)];
         const unsigned slot = lds_base + (unsigned)(blk % D) * SLOT;
         // MFMA lane (h, p) of the block's operand = lane 32 h + (qi & 31) of the query's stored tile
         const unsigned char* qtile = q6 + (size_t)(qi >> 5) * (size_t)IMG_TB;
@@ -1081,11 +1080,11 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_mx6h_kernel(int64_t n,
         const unsigned char* slot = ring + (size_t)(blk % D) * SLOT;
         const int* lt = reinterpret_cast<const int*>(slot + (size_t)KS6 * 1536 + 256);
         const int j = blk * 32 + (lane & 31);
-        const int qi = lbin[j];
+        const int qi = S.lbin[j];
         const bool live = j < nq && lt[lane & 31] >= 0;   // (-1: already with the all-pairs kernel)
         const float eq = __int_as_float(lt[32 + (lane & 31)]);
         const float rq = __int_as_float(lt[64 + (lane & 31)]);
-        const unsigned qs = *reinterpret_cast<const unsigned*>(slot + (size_t)KS6 * 1536 + 4 * lane);
+        const uint2 qs = make_uint2(*reinterpret_cast<const unsigned*>(slot + (size_t)KS6 * 1536 + 4 * lane), 0u);
         floatx16 acc;
         auto kstep = [&](auto Sc) __attribute__((always_inline)) {
             constexpr int s = decltype(Sc)::value;
@@ -1112,53 +1111,37 @@ __global__ __launch_bounds__(256) void match_rescan_chunk_mx6h_kernel(int64_t n,
         if (live) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const int rr = chunk_row(rr0, e);
                 const float thr = ((gate - 1.0e-6f) - (fx_A + fx_mult * be16[e])) - (rq * br16[e] + 1.0e-6f);
                 if (base + rr < m && !(acc[e] < thr)) hits |= 1u << e;
             }
         }
         if (hits) {
-            int at = atomicAdd(&lhit_n, __popc(hits));
+            int at = atomicAdd(&S.lhit_n, __popc(hits));
             while (hits) {
                 const int e = __ffs(hits) - 1;
                 hits &= hits - 1u;
-                const int rr = rr0 + (e & 3) + 8 * (e >> 2);
+                const int rr = chunk_row(rr0, e);
                 const float upe = (acc[e] + (fx_A + fx_mult * be16[e])) + (rq * br16[e] + 2.0e-6f);
-                if (at < RESCAN_LHITS) {
-                    lhq[at] = qi;
-                    lhr[at] = (unsigned char)rr;
-                    lhu[at] = upe;
-                } else {   // more hits than the staging buffer holds (duplicate-rich chunk): on the spot
-                    const int pos = cand_cnt[qi] + (int)atomicAdd(&hit_cnt[(size_t)qi * BIN_CNT_STRIDE], 1u);
-                    if (pos < cap) {
-                        cand[(size_t)qi * cap + pos] = ((unsigned)c << 8) | (unsigned)rr;
-                        cand_up[(size_t)qi * cap + pos] = upe;
-                    }
-                }
-                ++at;
+                rescan_stage_hit(S, L, at++, qi, c, rr, upe);
             }
         }
-        // (a full staging buffer is emptied before the next block adds to it; lhit_n is read by every thread between two barriers
-        // that no atomic of another block can cross, so the branch is uniform)
-        __syncthreads();
-        if (lhit_n > RESCAN_LHITS / 2 || blk + 1 == nblocks) {
-            wait_vmcnt<0>();   // (the atomics below are compiler-tracked: nothing of the ring may be pending behind them)
-            const int nh = lhit_n < RESCAN_LHITS ? lhit_n : RESCAN_LHITS;
-            for (int i = threadIdx.x; i < nh; i += 256) {
-                // (the list's length stays as match_bin_survivors_kernel left it during this kernel; the appended rows are counted in
-                // hit_cnt, a line of their own per query, and added by match_rescan_close_kernel)
-                const int hq = lhq[i];
-                const int pos = cand_cnt[hq] + (int)atomicAdd(&hit_cnt[(size_t)hq * BIN_CNT_STRIDE], 1u);
-                if (pos < cap) {
-                    cand[(size_t)hq * cap + pos] = ((unsigned)c << 8) | (unsigned)lhr[i];
-                    cand_up[(size_t)hq * cap + pos] = lhu[i];
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) lhit_n = 0;
-        }
+        rescan_flush(S, L, c, blk + 1 == nblocks);
     }
 #endif   // __HIP_DEVICE_COMPILE__
+}
+
+template <int KS6>
+int launch_rescan_chunk_mx6h(const SearchWs& w, int nchunks, int64_t n, int64_t m, const Prepared& Q, const Prepared& B, float gate,
+                             const int* guard, hipStream_t st) {
+    int slice;
+    const dim3 grid = rescan_chunk_grid(w, nchunks, slice);
+    hipLaunchKernelGGL(match_rescan_chunk_mx6h_kernel<KS6>, grid, dim3(256), 0, st,
+                       n, m, reinterpret_cast<const unsigned char*>(Q.tiles6), reinterpret_cast<const unsigned char*>(B.tiles6),
+                       (const float*)Q.err6h, (const float*)Q.rest, (const float*)B.err6h, (const float*)B.rest, w.cand_cnt, w.cand, w.cap,
+                       (const unsigned*)w.bin_cnt, (const int*)w.bins, gate, guard, w.bin_cap, w.hit_cnt, w.cand_up, slice);
+    VFM_CHECK_LAUNCH("match_rescan_chunk_mx6h_kernel");
+    return VFM_OK;
 }
 
 // VFM_RECORDS_NO_I8, behind half_guard_kernel: with the guard up there is no int8 image for a gate pass -- every live query goes to the
@@ -1852,7 +1835,6 @@ __device__ __forceinline__ double dot_norm_f64(const float* __restrict__ qrow_n,
     return acc;
 }
 
-
 // Exact decision among the candidates: one workgroup (4 waves) owns 64 queries; thread t < 64 = query t.
 //   single-row candidates (the common case, ~1.3 per query): the block's (query, candidate) pairs are
 //   flattened and taken 64 at a time; per batch and per 96-wide k chunk the four waves compute the fp64
@@ -2185,7 +2167,6 @@ __global__ __launch_bounds__(1024) void threshold_compact_kernel(const float* __
     if (threadIdx.x == 0) *count = base;
 }
 
-
 // 1/|row| only (EXACT mode)
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int64_t rows, int d,
                                                        float* __restrict__ inv_out) {
@@ -2200,175 +2181,102 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__
 
 }  // namespace
 
-template <int KS6>
-int launch_rescan_chunk_mx6h(const SearchWs& w, int nchunks, int64_t n, int64_t m, const Prepared& Q, const Prepared& B, float gate,
-                             const int* guard, hipStream_t st) {
-    const int slice = vfm_cfg().finish_short ? 128 : RESCAN_SLICE;
-    hipLaunchKernelGGL(match_rescan_chunk_mx6h_kernel<KS6>, dim3((unsigned)nchunks, (unsigned)((w.bin_cap + slice - 1) / slice)), dim3(256), 0, st,
-                       n, m, reinterpret_cast<const unsigned char*>(Q.tiles6), reinterpret_cast<const unsigned char*>(B.tiles6),
-                       (const float*)Q.err6h, (const float*)Q.rest, (const float*)B.err6h, (const float*)B.rest, w.cand_cnt, w.cand, w.cap,
-                       (const unsigned*)w.bin_cnt, (const int*)w.bins, gate, guard, w.bin_cap, w.hit_cnt, w.cand_up, slice);
-    VFM_CHECK_LAUNCH("match_rescan_chunk_mx6h_kernel");
-    return VFM_OK;
-}
-
-// VFM_RECORDS_MX6_HALF_FUSED | VFM_RECORDS_NO_I8: the finish stage of operands without an int8 image.  No kernel launched here reads
-// tiles8 / tiles8h / rows8 / err / gstep / gerr of either operand: the survivors are binned (match_bin_survivors_kernel: the slots
-// only), the guard counts the bins, the rescan reads the fp6 half image with err6h / rest, the closing pass the counters, and the fp64
-// decision the rows themselves.
+// stage 2 of a search: candidate selection + exact fp64 decision (reads ws of stage 1), as the plan's steps in order
+// gated: the search was started by the gated family (do_search_coarse(..., gated)); gate: queries whose best similarity is
+// provably below it are reported as (-1, -2.0) instead of being resolved (int8 / fp6 passes only; -Inf = resolve every query)
+//
+// VFM_RECORDS_NO_I8 (plan.no_i8): no step of such a plan reads tiles8 / tiles8h / rows8 / err / gstep / gerr of either operand: the
+// survivors are binned (match_bin_survivors_kernel: the slots only), the guard counts the bins, the rescan reads the fp6 half image with
+// err6h / rest, the closing pass the counters, and the fp64 decision the rows themselves.
 //   whole-chunk entries (a full bin leaves chunk << 8 | 128 in the query's list): match_rescan_close_kernel changes lengths, never
 //     entries, and match_rescore_kernel scores such a chunk's 128 rows in fp64 -- they stay as they are;
 //   crowded queries: match_rescore_kernel takes any list up to `cap` (epochs of RS_PAIRS pairs) and decides it in fp64 with the
 //     oracle's tie rule; the fp32 refinement only ever shortened such a list.  The closing pass still notes them (rec_cnt,
-//     fb_count[6]); nothing reads that here;
+//     fb_count[6]); nothing reads that there;
 //   guard up: match_guard_fallback_kernel hands every live query to match_exact_kernel (include/vfmreg.h, VFM_RECORDS_NO_I8).
-static int finish_half_noi8(Rows q, const Prepared& Q, int64_t n, Rows b, const Prepared& B, int64_t m, int d, int64_t* idx_out,
-                            float* sim_out, const SearchWs& w, const CoarseArgs& a, float gate, hipStream_t st) {
-    const int* guard = w.fb_count + HALF_GUARD_FLAG;
-    hipLaunchKernelGGL(match_bin_survivors_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w.partials),
-                       mx6_survivor_slot_words(), (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
-    VFM_CHECK_LAUNCH("match_bin_survivors_kernel");
-    hipLaunchKernelGGL(half_guard_kernel, dim3(1), dim3(256), 0, st, w.fb_count, (const unsigned*)w.bin_cnt, a.nchunks, 1,
-                       (long long)HALF_GUARD_PER_QUERY * (long long)n);
-    VFM_CHECK_LAUNCH("half_guard_kernel");
-    hipLaunchKernelGGL(match_guard_fallback_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const float*)Q.inv, guard,
-                       w.cand_cnt, w.fb_count, w.fb_list);
-    VFM_CHECK_LAUNCH("match_guard_fallback_kernel");
-    const int rc = d == 384 ? launch_rescan_chunk_mx6h<3>(w, a.nchunks, n, m, Q, B, gate, guard, st)
-                            : launch_rescan_chunk_mx6h<2>(w, a.nchunks, n, m, Q, B, gate, guard, st);
-    if (rc != VFM_OK) return rc;
-    hipLaunchKernelGGL(match_rescan_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, w.cand_cnt, w.cap, w.fb_count,
-                       w.fb_list, reinterpret_cast<int*>(w.rec_cnt), (const float*)Q.inv, (const unsigned*)w.hit_cnt);
-    VFM_CHECK_LAUNCH("match_rescan_close_kernel");
-    {
-        const size_t lds = (size_t)(64 * RS_STRIDE + RS_PAIRS) * sizeof(double) + (size_t)d * sizeof(float);
-        static unsigned long long attr_set = 0ull;  // one bit per device
-        if (!attr_done(attr_set)) {
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr_mark(attr_set);
-        }
-        hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m, d,
-                           w.cand_cnt, w.cand, w.cap, idx_out, sim_out, gate);
-    }
-    VFM_CHECK_LAUNCH("match_rescore_kernel");
-    hipLaunchKernelGGL(match_exact_kernel, dim3(256), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q, Q.inv, b, B.inv, n, m,
-                       d, w.fb_list, w.fb_count, idx_out, sim_out);
-    VFM_CHECK_LAUNCH("match_exact_kernel(fallback)");
-    return VFM_OK;
-}
-
-// stage 2 of a search: candidate selection + exact fp64 decision (reads ws of stage 1)
-// gated: the search was started by the gated family (do_search_coarse(..., gated)); gate: queries whose best similarity is
-// provably below it are reported as (-1, -2.0) instead of being resolved (int8 pass only; -Inf = resolve every query)
 int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* bprep, int64_t m, int d,
                      int64_t* idx_out, float* sim_out, void* ws, hipStream_t st, bool gated, float gate, int records) {
+    SearchPlan plan;
+    VFM_TRY(resolve_search(plan, records, d, n, m, gated, true));
+    VFM_TRY(check_plan_gate(plan.gate_test, gate, "search_finish"));
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
     const CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
     const float w2 = 2.0f * (float)(d / 16 + 4 + 2) * 5.9604645e-8f;
-    const bool no_i8 = (records & VFM_RECORDS_NO_I8) != 0;   // an option beside the kind (VFM_RECORDS_MX6_HALF_FUSED only)
-    records &= ~VFM_RECORDS_NO_I8;
-    const bool i8 = records != VFM_RECORDS_F16 && use_i8(d, n, m, gated);
-    if (i8 && !gated) records = VFM_RECORDS_TOP2;  // as do_search_coarse chose
-    records = effective_records(records, d, n, m);
-    if (no_i8) {
-        // any other kind -- asked for, or what this shape makes of the one asked for -- reads the int8 image that was not written
-        if (!(i8 && gated && records == VFM_RECORDS_MX6_HALF_FUSED && mx6_width(d)))
-            return vfm_fail(VFM_EINVAL, "search_finish: VFM_RECORDS_NO_I8 needs a search that runs as VFM_RECORDS_MX6_HALF_FUSED at d = 256 / 384 (n %lld, m %lld, d %d)",
-                            (long long)n, (long long)m, d);
-        if (!(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_finish: VFM_RECORDS_HALF needs a finite gate");
-        return finish_half_noi8(q, Q, n, b, B, m, d, idx_out, sim_out, w, a, gate, st);
-    }
-    // the fp6 coarse kernel has left the survivors in its workgroups' slots (half width, or -- VFM_RECORDS_MX6_FUSED -- full width: behind
-    // the kernel the two are the same search: survivors of a gate test, binned, rescanned on the int8 image with the gate as hit test)
-    const bool fused6 = i8 && (records == VFM_RECORDS_MX6_HALF_FUSED || records == VFM_RECORDS_MX6_FUSED);
-    const bool fused = i8 && (records == VFM_RECORDS_HALF_FUSED || fused6);   // the coarse kernel has done the selection already
-    const bool mx6half = i8 && records == VFM_RECORDS_MX6_HALF;   // the half-width pass on the fp6 image: its bounds in the selection
-    const bool half = i8 && (records == VFM_RECORDS_HALF || fused || mx6half);
-    if (mx6half || fused6) records = VFM_RECORDS_HALF;
-    if (half && !(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "search_finish: VFM_RECORDS_HALF needs a finite gate");
-    if (!i8 && use_sparse(d, n, m)) {
-        hipLaunchKernelGGL(match_filter_refine_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q, Q.inv, b, B.inv, n, m, d,
-                           DEFAULT_WINDOW, w2, w.qmax, w.rec_cnt, w.rec, w.rcap, w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats);
-        VFM_CHECK_LAUNCH("match_filter_refine_kernel");
-    } else {
-        const int chunk_lds = i8 && (size_t)a.nchunks * sizeof(float2) <= 63 * 1024;  // (step, max E) of every chunk in LDS
-        bool use_bins = false;
-        // best-score records with many queries per map chunk: the rescan runs chunk-major (match_rescan_chunk_kernel)
-        // records of the fp6 pass: its own bounds in the selection; behind it the int8 image and bounds, as for the int8 kinds
-        const bool pilot = i8 && records == VFM_RECORDS_MX6_PILOT;
-        if (pilot) records = VFM_RECORDS_MX6;
-        const bool mx6 = i8 && (records == VFM_RECORDS_MX6 || records == VFM_RECORDS_MX6_TOP2);
-        const bool top2 = i8 && (records == VFM_RECORDS_TOP2 || records == VFM_RECORDS_MX6_TOP2);
-        if (mx6) records = top2 ? VFM_RECORDS_TOP2 : VFM_RECORDS_BEST;
-        const bool best = i8 && records == VFM_RECORDS_BEST && vfm_cfg().select_variant != 1;
-        // (the fused kinds have no choice: their coarse kernel -- or match_bin_survivors_kernel below -- has filed the survivors in the
-        // bins already, and a search that does not rescan the bins reports every one of those queries as below the gate.  That was
-        // the case under "coarse_variant" 21, and at factory settings where effective_records -- which counts the chunks that hold
-        // rows -- keeps the fused kind and the padded chunk count below, one larger when that count is odd, says n < 4 nchunks.)
-        use_bins = fused || ((best || half) && vfm_cfg().select_variant != 2 && n >= 4 * (int64_t)a.nchunks);
-        if (pilot && use_bins) {
-            // the pilot rescan: one chunk per query, scored exactly on the int8 image, raises qmax (match_rescan_chunk_kernel, pilot
-            // branch); the bins it used are emptied again for the selection
-            hipLaunchKernelGGL(match_pilot_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const unsigned long long*)w.qbest,
-                               (const float*)Q.inv, w.bin_cnt, w.bins, w.bin_cap, a.nchunks);
-            VFM_CHECK_LAUNCH("match_pilot_bin_kernel");
-            const int rc = launch_rescan_chunk(w, a.nchunks, n, m, d, i8_bounds(Q, B, true, VFM_RECORDS_BEST), Q, B, 0, gate, (const int*)nullptr,
-                                               L2Terms{nullptr, nullptr, 0.0f}, st, true);
-            if (rc != VFM_OK) return rc;
-            VFM_CHECK_HIP(hipMemsetAsync(w.bin_cnt, 0, (size_t)((a.nchunks + 63) / 64 * 64) * BIN_CNT_STRIDE * sizeof(unsigned), st));
-        }
-        if (fused6) {
-            hipLaunchKernelGGL(match_bin_survivors_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w.partials),
-                               mx6_survivor_slot_words(), (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
-        } else if (fused) {
-            // (nothing to select)
-        } else if (half) {
-            const int half_lds = (size_t)a.nchunks * 12 <= 63 * 1024;  // (step, max E, max |rest|) of every chunk in LDS
-            hipLaunchKernelGGL(match_select_half_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * 8), half_lds ? (size_t)a.nchunks * 12 : 0,
-                               st, reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, Q.inv,
-                               mx6half ? mx6_bounds_half(Q, B) : i8_bounds(Q, B, true, records), (const float*)Q.rest, (const float*)B.grest, gate, half_lds, w.cand_cnt, w.cand, w.cap, w.fb_count,
-                               w.fb_list, vfm_cfg().match_stats, use_bins ? w.bin_cnt : (unsigned*)nullptr, use_bins ? w.bins : (int*)nullptr,
-                               w.bin_cap);
-        } else if (top2 && vfm_cfg().select_variant != 1) {
-            hipLaunchKernelGGL(match_select_top2_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * SELECT_TOP2_WAVES),
-                               chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st, (const uint2*)w.partials, a.nchunks, n,
-                               a.first_pad_chunk, (const unsigned*)w.qmax, Q.inv, mx6 ? mx6_bounds(Q, B, 1) : i8_bounds(Q, B, true, records), gate, chunk_lds,
-                               w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats);
-        } else if (best) {
-            // (chunk_lds 2: room for the per-chunk histogram of the tile's candidates as well -- chunks must fit 16 bits of a staged entry)
-            const int best_lds = chunk_lds && use_bins && (size_t)a.nchunks * 12 <= 63 * 1024 && a.nchunks < 65536 ? 2 : chunk_lds;
-            hipLaunchKernelGGL(match_select_best_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * SELECT_BEST_WAVES),
-                               best_lds == 2 ? (size_t)a.nchunks * 12 : chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st, reinterpret_cast<const unsigned*>(w.partials),
-                               a.nchunks, n, (const unsigned*)w.qmax, Q.inv, mx6 ? mx6_bounds(Q, B) : i8_bounds(Q, B, true, records), gate,
-                               best_lds, w.cand_cnt,
-                               w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats, use_bins ? w.bin_cnt : (unsigned*)nullptr,
-                               use_bins ? w.bins : (int*)nullptr, a.first_pad_chunk, w.bin_cap);
-        } else
-        hipLaunchKernelGGL(match_select_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64 * SELECT_GROUPS),
-                           chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st, w.partials, a.nchunks, a.npad, n, a.first_pad_chunk, w.qmax,
-                           Q.inv, DEFAULT_WINDOW, mx6 ? mx6_bounds(Q, B, top2 ? 1 : 0) : i8_bounds(Q, B, i8, records), gate, chunk_lds, w.cand_cnt, w.cand, w.cap,
-                           w.fb_count, w.fb_list, vfm_cfg().match_stats);
-        VFM_CHECK_LAUNCH("match_select_kernel");
-        if (i8) {  // candidate chunks -> candidate rows (the record buffer of the fp16 pass is free: it holds the hit lists)
-            const int* guard = half ? w.fb_count + HALF_GUARD_FLAG : (const int*)nullptr;
-            if (half) {   // the device-side guard of the half-width pass (see half_guard_kernel)
-                hipLaunchKernelGGL(half_guard_kernel, dim3(1), dim3(256), 0, st, w.fb_count, (const unsigned*)w.bin_cnt, a.nchunks,
-                                   fused ? 1 : 0, (long long)HALF_GUARD_PER_QUERY * (long long)n);
-                VFM_CHECK_LAUNCH("half_guard_kernel");
+    const bool i8 = plan.quantised(), half = plan.gate_test, use_bins = plan.use_bins;
+    // records of the fp6 pass: its own bounds in the selection; behind it the int8 image and bounds, as for the int8 kinds
+    const I8Bounds sel_ib = plan_bounds(plan, Q, B), ib = i8_bounds(Q, B, i8, plan.top2 ? 1 : 0);
+    const int chunk_lds = i8 && (size_t)a.nchunks * sizeof(float2) <= 63 * 1024;  // (step, max E) of every chunk in LDS
+    const int* guard = half ? w.fb_count + HALF_GUARD_FLAG : (const int*)nullptr;
+    for (int i = 0; i < plan.nsteps; ++i) {
+        const FinishStep step = plan.steps[i];
+        switch (step) {
+            case FIN_FILTER_REFINE:
+                hipLaunchKernelGGL(match_filter_refine_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q, Q.inv, b, B.inv, n, m, d,
+                                   DEFAULT_WINDOW, w2, w.qmax, w.rec_cnt, w.rec, w.rcap, w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats);
+                break;
+            case FIN_PILOT_BIN:
+                // the pilot rescan: one chunk per query, scored exactly on the int8 image, raises qmax (match_rescan_chunk_kernel, pilot
+                // branch); the bins it used are emptied again for the selection
+                hipLaunchKernelGGL(match_pilot_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const unsigned long long*)w.qbest,
+                                   (const float*)Q.inv, w.bin_cnt, w.bins, w.bin_cap, a.nchunks);
+                break;
+            case FIN_PILOT_RESCAN:
+                VFM_TRY(launch_rescan_chunk(w, a.nchunks, n, m, d, i8_bounds(Q, B, true, VFM_RECORDS_BEST), Q, B, 0, gate, (const int*)nullptr,
+                                            L2Terms{nullptr, nullptr, 0.0f}, st, true));
+                VFM_CHECK_HIP(hipMemsetAsync(w.bin_cnt, 0, (size_t)((a.nchunks + 63) / 64 * 64) * BIN_CNT_STRIDE * sizeof(unsigned), st));
+                break;
+            case FIN_BIN_SURVIVORS:
+                hipLaunchKernelGGL(match_bin_survivors_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w.partials),
+                                   mx6_survivor_slot_words(), (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
+                break;
+            case FIN_SELECT_HALF: {
+                const int half_lds = (size_t)a.nchunks * 12 <= 63 * 1024;  // (step, max E, max |rest|) of every chunk in LDS
+                hipLaunchKernelGGL(match_select_half_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * 8), half_lds ? (size_t)a.nchunks * 12 : 0,
+                                   st, reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, Q.inv, sel_ib, (const float*)Q.rest,
+                                   (const float*)B.grest, gate, half_lds, w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats,
+                                   use_bins ? w.bin_cnt : (unsigned*)nullptr, use_bins ? w.bins : (int*)nullptr, w.bin_cap);
+                break;
             }
-            hipLaunchKernelGGL(match_rescan_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, m, d, i8_bounds(Q, B, true, records),
-                               (const uint4*)Q.tiles8, (const uint4*)B.tiles8, (const unsigned*)w.qmax, w.cand_cnt, w.cand, w.cap,
-                               reinterpret_cast<unsigned*>(w.rec), 2 * w.rcap, w.fb_count, w.fb_list, half ? 1 : 0, gate, guard,
-                               L2Terms{nullptr, nullptr, 0.0f});
-            VFM_CHECK_LAUNCH("match_rescan_kernel");
-            if (half) {
+            case FIN_SELECT_TOP2:
+                hipLaunchKernelGGL(match_select_top2_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * SELECT_TOP2_WAVES),
+                                   chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st, (const uint2*)w.partials, a.nchunks, n, a.first_pad_chunk,
+                                   (const unsigned*)w.qmax, Q.inv, sel_ib, gate, chunk_lds, w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats);
+                break;
+            case FIN_SELECT_BEST: {
+                // (chunk_lds 2: room for the per-chunk histogram of the tile's candidates as well -- chunks must fit 16 bits of a staged entry)
+                const int best_lds = chunk_lds && use_bins && (size_t)a.nchunks * 12 <= 63 * 1024 && a.nchunks < 65536 ? 2 : chunk_lds;
+                hipLaunchKernelGGL(match_select_best_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * SELECT_BEST_WAVES),
+                                   best_lds == 2 ? (size_t)a.nchunks * 12 : chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st,
+                                   reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, (const unsigned*)w.qmax, Q.inv, sel_ib, gate, best_lds,
+                                   w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats, use_bins ? w.bin_cnt : (unsigned*)nullptr,
+                                   use_bins ? w.bins : (int*)nullptr, a.first_pad_chunk, w.bin_cap);
+                break;
+            }
+            case FIN_SELECT:
+                hipLaunchKernelGGL(match_select_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64 * SELECT_GROUPS),
+                                   chunk_lds ? (size_t)a.nchunks * sizeof(float2) : 0, st, w.partials, a.nchunks, a.npad, n, a.first_pad_chunk, w.qmax,
+                                   Q.inv, DEFAULT_WINDOW, sel_ib, gate, chunk_lds, w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats);
+                break;
+            case FIN_HALF_GUARD:   // the device-side guard of the half-width pass (see half_guard_kernel)
+                hipLaunchKernelGGL(half_guard_kernel, dim3(1), dim3(256), 0, st, w.fb_count, (const unsigned*)w.bin_cnt, a.nchunks,
+                                   plan.fused ? 1 : 0, (long long)HALF_GUARD_PER_QUERY * (long long)n);
+                break;
+            case FIN_GUARD_FALLBACK:
+                hipLaunchKernelGGL(match_guard_fallback_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const float*)Q.inv, guard,
+                                   w.cand_cnt, w.fb_count, w.fb_list);
+                break;
+            case FIN_RESCAN:   // candidate chunks -> candidate rows (the record buffer of the fp16 pass is free: it holds the hit lists)
+                hipLaunchKernelGGL(match_rescan_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, m, d, ib,
+                                   (const uint4*)Q.tiles8, (const uint4*)B.tiles8, (const unsigned*)w.qmax, w.cand_cnt, w.cand, w.cap,
+                                   reinterpret_cast<unsigned*>(w.rec), 2 * w.rcap, w.fb_count, w.fb_list, half ? 1 : 0, gate, guard,
+                                   L2Terms{nullptr, nullptr, 0.0f});
+                break;
+            case FIN_GATEPASS:
 #define VFM_GATEPASS(KS)                                                                                                        \
-    hipLaunchKernelGGL(match_gatepass_kernel<KS>, dim3((unsigned)a.nchunks), dim3(256), 0, st, n, m, a.nq_tiles,                  \
-                       i8_bounds(Q, B, true, records), (const float*)Q.inv, (const uint4*)Q.tiles8, (const uint4*)B.tiles8, gate, \
-                       w.cand_cnt, w.cand, w.cap, guard, w.qmax)
+    hipLaunchKernelGGL(match_gatepass_kernel<KS>, dim3((unsigned)a.nchunks), dim3(256), 0, st, n, m, a.nq_tiles, ib, (const float*)Q.inv, \
+                       (const uint4*)Q.tiles8, (const uint4*)B.tiles8, gate, w.cand_cnt, w.cand, w.cap, guard, w.qmax)
                 switch (d / 32) {
                     case 8: VFM_GATEPASS(8); break;
                     case 12: VFM_GATEPASS(12); break;
@@ -2377,56 +2285,58 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
                     default: VFM_GATEPASS(24); break;
                 }
 #undef VFM_GATEPASS
-                VFM_CHECK_LAUNCH("match_gatepass_kernel");
-            }
-            if (use_bins) {
-                const int rc = launch_rescan_chunk(w, a.nchunks, n, m, d, i8_bounds(Q, B, true, records), Q, B, half ? 1 : 0, gate, guard,
-                                                   L2Terms{nullptr, nullptr, 0.0f}, st);
-                if (rc != VFM_OK) return rc;
-            }
-            hipLaunchKernelGGL(match_rescan_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, w.cand_cnt, w.cap,
-                               w.fb_count, w.fb_list, reinterpret_cast<int*>(w.rec_cnt), half ? (const float*)Q.inv : (const float*)nullptr,
-                               (const unsigned*)w.hit_cnt);
-            VFM_CHECK_LAUNCH("match_rescan_close_kernel");
-            // (rec_cnt, unused by the int8 pass, holds the list of crowded queries; fb_count[6] its length)
-            // (round 4: one wave per possible entry after all.  With 1024 workgroups striding over the list a wave had two or three
-            // queries of 30 - 40 us each and the kernel lasted as long as the unluckiest wave -- 137 us at 9891 crowded queries; a wave per
-            // entry is placed as slots come free: 125 us.  Handing the entries out through an atomic cursor was tried: 186 us -- 4096
-            // waves ask the same address at once and every later load of a wave waits behind its atomic.  The refinement is 124 registers
-            // since R4.5, and workgroups past the list's end return at once: ~2 us for 5000 of them.)
-            const unsigned grid = (unsigned)((n + 3) / 4);
+                break;
+            case FIN_RESCAN_CHUNK:
+                VFM_TRY(launch_rescan_chunk(w, a.nchunks, n, m, d, ib, Q, B, half ? 1 : 0, gate, guard, L2Terms{nullptr, nullptr, 0.0f}, st));
+                break;
+            case FIN_RESCAN_CHUNK_MX6H:
+                VFM_TRY(d == 384 ? launch_rescan_chunk_mx6h<3>(w, a.nchunks, n, m, Q, B, gate, guard, st)
+                                 : launch_rescan_chunk_mx6h<2>(w, a.nchunks, n, m, Q, B, gate, guard, st));
+                break;
+            case FIN_RESCAN_CLOSE:
+                // (rec_cnt, unused by the int8 pass, holds the list of crowded queries; fb_count[6] its length)
+                hipLaunchKernelGGL(match_rescan_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, w.cand_cnt, w.cap,
+                                   w.fb_count, w.fb_list, reinterpret_cast<int*>(w.rec_cnt), half ? (const float*)Q.inv : (const float*)nullptr,
+                                   (const unsigned*)w.hit_cnt);
+                break;
+            case FIN_REFINE: {
+                // (round 4: one wave per possible entry after all.  With 1024 workgroups striding over the list a wave had two or three
+                // queries of 30 - 40 us each and the kernel lasted as long as the unluckiest wave -- 137 us at 9891 crowded queries; a wave per
+                // entry is placed as slots come free: 125 us.  Handing the entries out through an atomic cursor was tried: 186 us -- 4096
+                // waves ask the same address at once and every later load of a wave waits behind its atomic.  The refinement is 124 registers
+                // since R4.5, and workgroups past the list's end return at once: ~2 us for 5000 of them.)
+                const unsigned grid = (unsigned)((n + 3) / 4);
 #define VFM_REFINE(NT)                                                                                                          \
     hipLaunchKernelGGL(match_refine_kernel<NT>, dim3(grid), dim3(256), 0, st, q, Q.inv, b, B.inv, n, m, d, w2, w.cand_cnt, w.cand, \
-                       w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats, (const int*)w.rec_cnt, (const int*)(w.fb_count + 6),            \
-                       use_bins ? (const float*)w.cand_up : (const float*)nullptr, (const unsigned*)w.hit_cnt,                     \
-                       i8_bounds(Q, B, true, records))
-            if (d <= 256) VFM_REFINE(4);
-            else if (d <= 384) VFM_REFINE(6);
-            else if (d <= 512) VFM_REFINE(8);
-            else VFM_REFINE(12);
+                       w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats, i8 ? (const int*)w.rec_cnt : (const int*)nullptr,      \
+                       i8 ? (const int*)(w.fb_count + 6) : (const int*)nullptr, use_bins ? (const float*)w.cand_up : (const float*)nullptr, \
+                       i8 ? (const unsigned*)w.hit_cnt : (const unsigned*)nullptr, ib)
+                if (!i8 || d > 512) VFM_REFINE(12);
+                else if (d <= 256) VFM_REFINE(4);
+                else if (d <= 384) VFM_REFINE(6);
+                else VFM_REFINE(8);
 #undef VFM_REFINE
-        } else {
-            hipLaunchKernelGGL(match_refine_kernel<12>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q, Q.inv, b, B.inv, n, m, d, w2,
-                               w.cand_cnt, w.cand, w.cap, w.fb_count, w.fb_list, vfm_cfg().match_stats, (const int*)nullptr, (const int*)nullptr,
-                               (const float*)nullptr, (const unsigned*)nullptr, I8Bounds{});
+                break;
+            }
+            case FIN_RESCORE: {
+                const size_t lds = (size_t)(64 * RS_STRIDE + RS_PAIRS) * sizeof(double) + (size_t)d * sizeof(float);
+                static unsigned long long attr_set = 0ull;  // one bit per device
+                if (!attr_done(attr_set)) {
+                    VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+                    attr_mark(attr_set);
+                }
+                hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m,
+                                   d, w.cand_cnt, w.cand, w.cap, idx_out, sim_out, half ? gate : -__builtin_inff());
+                break;
+            }
+            case FIN_EXACT:
+                hipLaunchKernelGGL(match_exact_kernel, dim3(256), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q, Q.inv,
+                                   b, B.inv, n, m, d, w.fb_list, w.fb_count, idx_out, sim_out);
+                break;
         }
-        VFM_CHECK_LAUNCH("match_refine_kernel");
+        VFM_CHECK_LAUNCH(finish_step_name(step));
     }
-    {
-        const size_t lds = (size_t)(64 * RS_STRIDE + RS_PAIRS) * sizeof(double) + (size_t)d * sizeof(float);
-        static unsigned long long attr_set = 0ull;  // one bit per device
-        if (!attr_done(attr_set)) {
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr_mark(attr_set);
-        }
-        hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m,
-                           d, w.cand_cnt, w.cand, w.cap, idx_out, sim_out, half ? gate : -__builtin_inff());
-    }
-    VFM_CHECK_LAUNCH("match_rescore_kernel");
-    hipLaunchKernelGGL(match_exact_kernel, dim3(256), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q, Q.inv,
-                       b, B.inv, n, m, d, w.fb_list, w.fb_count, idx_out, sim_out);
-    VFM_CHECK_LAUNCH("match_exact_kernel(fallback)");
     return VFM_OK;
 }
 
@@ -2449,14 +2359,14 @@ int launch_i8_rescans(const SearchWs& w, const CoarseArgs& a, const Prepared& Q,
 
 // vfm_match_search_probe_half: how many (query, chunk) pairs the half-width pass would leave for the rescan -- its coarse
 // pass has just run into ws (do_search_coarse(..., VFM_RECORDS_HALF)); only fb_count[5] is written
-int probe_half_select(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st) {
+int probe_half_select(const SearchPlan& plan, const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st) {
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
     const CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
     const int half_lds = (size_t)a.nchunks * 12 <= 63 * 1024;
     hipLaunchKernelGGL(match_select_half_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * 8), half_lds ? (size_t)a.nchunks * 12 : 0, st,
-                       reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, Q.inv, i8_bounds(Q, B, true, VFM_RECORDS_HALF),
+                       reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, Q.inv, plan_bounds(plan, Q, B),
                        (const float*)Q.rest, (const float*)B.grest, gate, half_lds, w.cand_cnt, (unsigned*)nullptr, w.cap, w.fb_count,
                        w.fb_list, 0, (unsigned*)nullptr, (int*)nullptr, w.bin_cap);
     VFM_CHECK_LAUNCH("match_select_half_kernel(probe)");

@@ -7,11 +7,11 @@
 #include <type_traits>
 #include <vector>
 
-
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef int intx4 __attribute__((ext_vector_type(4)));
+typedef int intx8 __attribute__((ext_vector_type(8)));
 typedef int intx16 __attribute__((ext_vector_type(16)));
 
 #define GLOBAL_AS __attribute__((address_space(1)))
@@ -44,7 +44,6 @@ __host__ __device__ inline int rescan_bin_cap(int64_t npad, int64_t nchunks) {
 // 345 at 920 000).
 constexpr int BIN_CNT_STRIDE = 32;
 constexpr int RESCAN_SLICE = 256;    // bin entries one workgroup of match_rescan_chunk_kernel takes (grid.y slices a long bin; 1024 until the end of round 4: the longest workgroups -- 32 blocks of 2.6 us -- were the kernel, 155 -> 140 us at 590 queries per chunk; 128 pays more prologues than it balances)
-constexpr int RESCAN_BATCH = 64;     // ... of which match_rescan_chunk_kernel stages this many in LDS at a time
 // Half-width pass, device-side guard: a search whose bound leaves more than this many (query, chunk) pairs per query -- descriptors
 // that are all alike: every chunk survives -- does not rescan them (31 million 128-row rescans at C2: 171 ms) but falls through,
 // inside the same _finish call, to match_gatepass_kernel: one full-width int8 MFMA pass with the gate as hit test (2-3 ms).
@@ -116,7 +115,6 @@ __device__ __forceinline__ float inv_norm_from_sumsq(float nr) {
     float s = sqrtf(nr);  // __builtin_sqrtf: correctly rounded (HIP default); __fsqrt_rn is the native approximation
     return (float)(1.0 / (double)s);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // coarse pass
@@ -330,8 +328,6 @@ __device__ __forceinline__ unsigned coarse_emit_chunk_best(const CoarseArgs& a, 
     return w1;
 }
 
-// QSETS = 32-query sets resident per wave: 1 -> 8 waves (2 per SIMD), 2 -> 4 waves (1 per SIMD,
-
 // arg-max over a wavefront, ties -> lowest index (the oracle's rule)
 __device__ __forceinline__ void wave_argmax(double& s, long long& j) {
 #pragma unroll
@@ -377,12 +373,6 @@ constexpr int64_t ROWS8_MAX_ROWS = 131072;
 // widths the int8 coarse pass exists for (match_coarse_pipe_kernel<d/32, false, true>; d = 128 has too few k-steps for the
 // fragment ring)
 inline bool i8_capable(int d) { return d == 256 || d == 384 || d == 512 || d == 640 || d == 768; }
-// shapes the half-width pass (VFM_RECORDS_HALF) has a kernel for (every int8 width: the 64-queries-per-wave kernel for d <= 384
-// with more than 2048 queries, the one-set kernel with four tiles per step elsewhere)
-inline bool half_capable(int d, int64_t n) {
-    (void)n;
-    return i8_capable(d);
-}
 // widths the fp6 pass (VFM_RECORDS_MX6) has a kernel for: two resident query sets of d / 64 x 8 registers
 inline bool mx6_width(int d) { return d == 256 || d == 384; }
 // widths whose HALF-width pass has an fp6 kernel (d / 128 k-steps of queries in registers): the fp6 image exists for these
@@ -407,22 +397,27 @@ __host__ __device__ inline size_t mx6_code_b(int s, int lane) { return (size_t)M
 __host__ __device__ inline size_t mx6_scale_at(int ks, int s, int lane) {
     return (s < 8 ? 0 : (size_t)MX6_SCALE_PLANE + (size_t)ks * MX6_KSTEP_BYTES) + (size_t)lane * 8 + (size_t)(s & 7);
 }
-// the fused form exists where the 64-queries-per-wave kernel runs and a map chunk collects several queries (chunk-major rescan)
-inline int effective_records(int records, int d, int64_t n, int64_t m) {
-    if (records == VFM_RECORDS_HALF_FUSED && !((d == 256 || d == 384) && n > 2048 && n >= 4 * ((m + CHUNK_ROWS - 1) / CHUNK_ROWS)))
-        records = VFM_RECORDS_HALF;
-    // (the pilot rescan is chunk-major: several queries per map chunk)
-    if (records == VFM_RECORDS_MX6_PILOT && !(n >= 4 * ((m + CHUNK_ROWS - 1) / CHUNK_ROWS))) records = VFM_RECORDS_MX6;
-    // (the fused full-width form: the chunk-major rescan behind it, like the other fused kinds)
-    if (records == VFM_RECORDS_MX6_FUSED && !(n >= 4 * ((m + CHUNK_ROWS - 1) / CHUNK_ROWS))) records = VFM_RECORDS_MX6;
-    if ((records == VFM_RECORDS_MX6 || records == VFM_RECORDS_MX6_PILOT || records == VFM_RECORDS_MX6_FUSED) && !(mx6_width(d) && n > 2048)) records = VFM_RECORDS_BEST;   // (the one-set kernels have no fp6 form)
-    if (records == VFM_RECORDS_MX6_TOP2 && !(mx6_width(d) && n > 2048)) records = VFM_RECORDS_TOP2;
-    if (records == VFM_RECORDS_MX6_HALF && !(mx6_half_width(d) && n > 2048)) records = VFM_RECORDS_BEST;   // (such operands carry no int8 half image)
-    // the fused form needs the chunk-major rescan behind it (several queries per map chunk), like VFM_RECORDS_HALF_FUSED
-    if (records == VFM_RECORDS_MX6_HALF_FUSED)
-        records = !(mx6_half_width(d) && n > 2048) ? VFM_RECORDS_BEST
-                  : (n >= 4 * ((m + CHUNK_ROWS - 1) / CHUNK_ROWS) ? VFM_RECORDS_MX6_HALF_FUSED : VFM_RECORDS_MX6_HALF);
-    return (records == VFM_RECORDS_HALF && !half_capable(d, n)) ? VFM_RECORDS_BEST : records;
+// one lane's operand of a k-step of v_mfma_scale_f32_32x32x64_f8f6f4 in e2m3: 32 codes in six registers (the instruction reads v[n:n+5])
+struct Mx6Frag {
+    int c[6];
+};
+// k-step S (0 .. 7) of the scaled MFMA: xs / ys hold the lane's eight E8M0 scales, byte S & 3 of .x (S < 4) or .y (a kernel that
+// multiplies four k-steps at the most leaves .y unset: it is never read)
+template <int S>
+__device__ __forceinline__ floatx16 mfma_mx6(const Mx6Frag& x, const uint2& xs, const Mx6Frag& y, const uint2& ys, floatx16 c) {
+    intx8 a, b;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        a[i] = x.c[i];
+        b[i] = y.c[i];
+    }
+    a[6] = a[7] = b[6] = b[7] = 0;   // not read: cbsz = blgp = 2 (e2m3) takes six registers per operand
+#ifdef VFM_ABL_NOSCALE   // (timing experiment, tools/ablate6.py: the unscaled instruction -- results are garbage)
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, 0, 0, 0, 0);
+#else
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, S & 3, (int)(S < 4 ? xs.x : xs.y), S & 3,
+                                                           (int)(S < 4 ? ys.x : ys.y));
+#endif
 }
 
 inline Prepared carve_prepared(void* p, int64_t rows, int d) {
@@ -594,9 +589,129 @@ struct CoarseKernelName {
 };
 extern thread_local const CoarseKernelName* g_last_coarse_kernel;
 
-// which coarse pass / record kind a search takes (match_api.hip)
+// size and policy rules of the passes (match_api.hip)
 bool use_sparse(int d, int64_t n, int64_t m);
 bool use_i8(int d, int64_t n, int64_t m, bool gated);
+
+// ---------------------------------------------------------------------------------------------
+// What a search does, resolved ONCE from what the caller passed and the calling thread's vfm_cfg(): do_search_coarse, do_search_finish
+// and the read-back vfm_debug_search_plan all branch on this and on nothing else, so the two stages cannot disagree.
+// ---------------------------------------------------------------------------------------------
+// the two chunk counts of a map of m rows: the 128-row chunks that hold at least one row, and the chunks of the map padded to ROW_PAD
+// rows (what the kernels walk: one more when the first count is odd)
+inline int64_t chunks_with_rows(int64_t m) { return (m + CHUNK_ROWS - 1) / CHUNK_ROWS; }
+inline int64_t chunks_padded(int64_t m) { return rows_padded(m) / CHUNK_ROWS; }
+
+enum SearchPass { PASS_F16_DENSE, PASS_F16_SPARSE, PASS_I8, PASS_MX6 };
+enum SearchBounds { BOUNDS_NONE, BOUNDS_I8, BOUNDS_MX6, BOUNDS_MX6_HALF };   // i8_bounds / mx6_bounds / mx6_bounds_half
+// the finish stage's launches (do_search_finish runs plan.steps in order; finish_step_name spells them)
+enum FinishStep : unsigned char {
+    FIN_FILTER_REFINE, FIN_PILOT_BIN, FIN_PILOT_RESCAN, FIN_BIN_SURVIVORS, FIN_SELECT_HALF, FIN_SELECT_TOP2, FIN_SELECT_BEST, FIN_SELECT,
+    FIN_HALF_GUARD, FIN_GUARD_FALLBACK, FIN_RESCAN, FIN_GATEPASS, FIN_RESCAN_CHUNK, FIN_RESCAN_CHUNK_MX6H, FIN_RESCAN_CLOSE, FIN_REFINE,
+    FIN_RESCORE, FIN_EXACT
+};
+inline const char* finish_step_name(FinishStep s) {
+    static const char* const names[] = {"match_filter_refine_kernel", "match_pilot_bin_kernel", "match_rescan_chunk_kernel", "match_bin_survivors_kernel",
+                                        "match_select_half_kernel", "match_select_top2_kernel", "match_select_best_kernel", "match_select_kernel",
+                                        "half_guard_kernel", "match_guard_fallback_kernel", "match_rescan_kernel", "match_gatepass_kernel",
+                                        "match_rescan_chunk_kernel", "match_rescan_chunk_mx6h_kernel", "match_rescan_close_kernel", "match_refine_kernel",
+                                        "match_rescore_kernel", "match_exact_kernel"};
+    return names[s];
+}
+struct SearchPlan {
+    int pass = PASS_F16_DENSE;
+    int kind = VFM_RECORDS_F16;   // the kind the search runs as, after every fallback (VFM_RECORDS_F16: an fp16 pass)
+    bool half = false;            // the coarse pass multiplies the first d / 2 columns
+    bool fused = false;           // ... and does the selection itself: the gate is needed at the coarse call already
+    bool top2 = false;            // packed top-2 records
+    bool pilot = false;           // VFM_RECORDS_MX6_PILOT: the coarse pass notes every query's best chunk
+    bool gate_test = false;       // behind the selection the gate itself is the hit test (half-width and fused kinds): needs a finite gate
+    bool use_bins = false;        // the chunk-major rescan walks the chunks' bins
+    bool no_i8 = false;           // VFM_RECORDS_NO_I8: nothing may read the int8 image
+    int bounds = BOUNDS_NONE;     // of the records: the coarse kernel's and the selection's (the int8 rescans use i8_bounds)
+    FinishStep steps[12] = {};
+    int nsteps = 0;
+    bool quantised() const { return pass == PASS_I8 || pass == PASS_MX6; }
+};
+
+// records: as passed (a kind, VFM_RECORDS_NO_I8 beside it or not).  A combination no kernel serves is refused here, once.
+inline int resolve_search(SearchPlan& p, int records, int d, int64_t n, int64_t m, bool gated, bool inner_product) {
+    p = SearchPlan{};
+    p.no_i8 = (records & VFM_RECORDS_NO_I8) != 0;
+    int kind = records & ~VFM_RECORDS_NO_I8;
+    if (kind < VFM_RECORDS_BEST || kind > VFM_RECORDS_MX6_FUSED) return vfm_fail(VFM_EINVAL, "search: unknown record kind %d", records);
+    auto add = [&p](FinishStep s) { p.steps[p.nsteps++] = s; };
+    if (inner_product && kind != VFM_RECORDS_F16 && use_i8(d, n, m, gated)) {
+        if (!gated) kind = VFM_RECORDS_TOP2;  // no feedback loop behind an ungated call: the robust record kind
+        // The fallbacks.  The fused kinds and the pilot need the chunk-major rescan behind them: several queries per map chunk.
+        // The fp6 kernels and the fused int8 kernel hold 64 queries per wave: more than 2048 queries, d = 256 / 384 (the one-set
+        // kernels have no fp6 form; half width in fp6: 512 / 768 too, and such operands carry no int8 half image).
+        const bool many = n >= 4 * chunks_with_rows(m), q2 = n > 2048;
+        if (kind == VFM_RECORDS_HALF_FUSED && !((d == 256 || d == 384) && q2 && many)) kind = VFM_RECORDS_HALF;
+        if ((kind == VFM_RECORDS_MX6_PILOT || kind == VFM_RECORDS_MX6_FUSED) && !many) kind = VFM_RECORDS_MX6;
+        if ((kind == VFM_RECORDS_MX6 || kind == VFM_RECORDS_MX6_PILOT || kind == VFM_RECORDS_MX6_FUSED) && !(mx6_width(d) && q2)) kind = VFM_RECORDS_BEST;
+        if (kind == VFM_RECORDS_MX6_TOP2 && !(mx6_width(d) && q2)) kind = VFM_RECORDS_TOP2;
+        if ((kind == VFM_RECORDS_MX6_HALF || kind == VFM_RECORDS_MX6_HALF_FUSED) && !(mx6_half_width(d) && q2)) kind = VFM_RECORDS_BEST;
+        if (kind == VFM_RECORDS_MX6_HALF_FUSED && !many) kind = VFM_RECORDS_MX6_HALF;
+        p.kind = kind;
+        p.pass = kind >= VFM_RECORDS_MX6 ? PASS_MX6 : PASS_I8;
+        p.half = kind == VFM_RECORDS_HALF || kind == VFM_RECORDS_HALF_FUSED || kind == VFM_RECORDS_MX6_HALF || kind == VFM_RECORDS_MX6_HALF_FUSED;
+        p.fused = kind == VFM_RECORDS_HALF_FUSED || kind == VFM_RECORDS_MX6_HALF_FUSED || kind == VFM_RECORDS_MX6_FUSED;
+        p.top2 = kind == VFM_RECORDS_TOP2 || kind == VFM_RECORDS_MX6_TOP2;
+        p.pilot = kind == VFM_RECORDS_MX6_PILOT;
+        p.gate_test = p.half || p.fused;
+        p.bounds = p.pass == PASS_I8 ? BOUNDS_I8 : (p.half ? BOUNDS_MX6_HALF : BOUNDS_MX6);
+    } else if (inner_product && use_sparse(d, n, m)) {
+        p.pass = PASS_F16_SPARSE;
+    }
+    // any other kind -- asked for, or what this shape makes of the one asked for -- reads the int8 image that was not written
+    if (p.no_i8 && !(gated && p.kind == VFM_RECORDS_MX6_HALF_FUSED && mx6_width(d)))
+        return vfm_fail(VFM_EINVAL, "search: VFM_RECORDS_NO_I8 needs a search that runs as VFM_RECORDS_MX6_HALF_FUSED at d = 256 / 384 (records %d, n %lld, m %lld, d %d)",
+                        records, (long long)n, (long long)m, d);
+    if (!inner_product) return VFM_OK;   // (the Euclidean search finishes in match_l2.hip)
+    if (p.pass == PASS_F16_SPARSE) {
+        add(FIN_FILTER_REFINE);
+    } else if (!p.quantised()) {
+        add(FIN_SELECT);
+        add(FIN_REFINE);
+    } else {
+        const int variant = vfm_cfg().select_variant;
+        const bool best = !p.top2 && !p.gate_test && variant != 1;
+        // Best-score records with many queries per map chunk: the rescan runs chunk-major.  A fused kind has no choice: its coarse kernel
+        // -- or match_bin_survivors_kernel -- has filed the survivors in the bins already, and a search that does not rescan the bins
+        // reports every one of those queries as below the gate ("coarse_variant" 21; and n between four times the two chunk counts).
+        p.use_bins = p.fused || ((best || p.gate_test) && variant != 2 && n >= 4 * chunks_padded(m));
+        if (p.pilot && p.use_bins) {
+            add(FIN_PILOT_BIN);
+            add(FIN_PILOT_RESCAN);
+        }
+        if (p.fused) {   // nothing to select; the fp6 coarse kernel has left the survivors in its workgroups' slots
+            if (p.pass == PASS_MX6) add(FIN_BIN_SURVIVORS);
+        } else {
+            add(p.gate_test ? FIN_SELECT_HALF : (p.top2 && variant != 1) ? FIN_SELECT_TOP2 : best ? FIN_SELECT_BEST : FIN_SELECT);
+        }
+        if (p.gate_test) add(FIN_HALF_GUARD);
+        if (p.no_i8) {   // survivors rescanned on the fp6 half image; guard up: every live query to the all-pairs kernel
+            add(FIN_GUARD_FALLBACK);
+            add(FIN_RESCAN_CHUNK_MX6H);
+            add(FIN_RESCAN_CLOSE);
+        } else {         // candidate chunks -> candidate rows on the int8 image; guard up: one full-width gate pass
+            add(FIN_RESCAN);
+            if (p.gate_test) add(FIN_GATEPASS);
+            if (p.use_bins) add(FIN_RESCAN_CHUNK);
+            add(FIN_RESCAN_CLOSE);
+            add(FIN_REFINE);
+        }
+    }
+    add(FIN_RESCORE);
+    add(FIN_EXACT);
+    return VFM_OK;
+}
+// a finite gate where the plan tests against it: at the coarse call for the fused kinds, at the finish call for every gate-tested kind
+inline int check_plan_gate(bool needed, float gate, const char* who) {
+    if (needed && !(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "%s: the half-width and fused record kinds need a finite gate", who);
+    return VFM_OK;
+}
 int coarse_qblock(int d);
 int choose_slices(int nqb, int nchunks);
 inline I8Bounds i8_bounds(const Prepared& Q, const Prepared& B, bool on, int top2 = 0) {
@@ -607,6 +722,12 @@ inline I8Bounds mx6_bounds(const Prepared& Q, const Prepared& B, int top2 = 0) {
 // ... of the half-width fp6 kinds: the residual norms over the columns the pass multiplies (tighter, and all a VFM_PREPARE_MX6_HALF
 // operand carries: its full-width E is infinite)
 inline I8Bounds mx6_bounds_half(const Prepared& Q, const Prepared& B) { return I8Bounds{Q.err6h, Q.gstep6, B.gstep6, B.gerr6h, 0}; }
+// ... of the records a plan's coarse pass writes (SearchPlan::bounds)
+inline I8Bounds plan_bounds(const SearchPlan& p, const Prepared& Q, const Prepared& B) {
+    if (p.bounds == BOUNDS_MX6_HALF) return mx6_bounds_half(Q, B);
+    if (p.bounds == BOUNDS_MX6) return mx6_bounds(Q, B, p.top2 ? 1 : 0);
+    return i8_bounds(Q, B, p.bounds == BOUNDS_I8, p.top2 ? 1 : 0);
+}
 CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m, int qblock = QBLOCK);
 
 // match_prep.hip
@@ -651,7 +772,7 @@ int launch_select_dense(const SearchWs& w, const CoarseArgs& a, const float* qin
 // closing pass (over-long lists to the all-pairs fallback); l2.qn != NULL: the Euclidean hit test, qmax = float_key(qlow)
 int launch_i8_rescans(const SearchWs& w, const CoarseArgs& a, const Prepared& Q, const Prepared& B, int64_t n, int64_t m, int d,
                       bool use_bins, L2Terms l2, hipStream_t st);
-int probe_half_select(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st);
+int probe_half_select(const SearchPlan& plan, const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st);
 int exact_ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, int64_t* idx_out, float* sim_out, void* ws,
                   hipStream_t st);
 

@@ -129,6 +129,7 @@ DEBUG_SIGNATURES = {
     "vfm_prof_events_destroy": (C.c_int, [c_vp, c_vp]),
     "vfm_debug_last_coarse_kernel": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_coarse_kernel_names": (C.c_int, [C.c_char_p, C.c_int]),
+    "vfm_debug_search_plan": (C.c_int, [C.c_int, C.c_int, c_i64, c_i64, C.c_int, C.c_char_p, C.c_int]),
     "vfm_debug_match_stats": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "vfm_debug_i8_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_mx6_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp]),
@@ -283,6 +284,18 @@ def coarse_kernel_names() -> list:
     buf = C.create_string_buffer(1 << 14)
     check(load().vfm_debug_coarse_kernel_names(buf, len(buf)), "coarse_kernel_names")
     return buf.value.decode().split("\n") if buf.value else []
+
+
+def search_plan(records: int, d: int, n: int, m: int, gated: bool = True) -> dict:
+    """What a search of these arguments would do under the calling thread's Config (include/vfmreg_debug.h, vfm_debug_search_plan):
+    {"pass": str, "kind": int, "half" / "fused" / "top2" / "pilot" / "bins" / "no_i8": bool, "finish": [kernel names in launch order]}.
+    Raises RuntimeError with the library's message where the search itself would refuse.  Touches no device."""
+    buf = C.create_string_buffer(1024)
+    check(load().vfm_debug_search_plan(records, d, n, m, int(gated), buf, len(buf)), "search_plan")
+    plan = dict(item.split("=", 1) for item in buf.value.decode().split(" "))
+    out = {k: bool(int(v)) for k, v in plan.items() if k not in ("pass", "kind", "finish")}
+    out.update({"pass": plan["pass"], "kind": int(plan["kind"]), "finish": plan["finish"].split(",")})
+    return out
 
 
 def check(rc: int, what: str = "") -> None:

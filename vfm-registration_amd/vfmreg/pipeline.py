@@ -32,6 +32,7 @@ pass, with a probe one step back every ``REPROBE`` registrations.  ``gate=False`
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import numpy as np
@@ -246,9 +247,18 @@ class RegistrationPipeline:
         # `auto` only: when such a search's guard goes up (descriptors that are all alike) its queries are decided by the all-pairs kernel
         # -- tens of milliseconds --, and it is `auto`'s feedback that leaves kind 8 after that search; a pinned "mx6-half" has no way out
         # and keeps the int8 image, whose gate pass bounds such a registration at a few milliseconds
-        self._noi8_shape = coarse == "auto" and d in (256, 384) and n > 2048 and n >= 4 * ((m + 127) // 128)
+        self._noi8_shape = coarse == "auto" and self._resolves(8 | 0x200)
         self.last_prep_schedule: Optional[int] = None   # `schedule` of the last registration's vfm_match_prepare2_gated_* call (None: another call)
         self.last_records: Optional[int] = None         # record kind of the last registration's search, option bits included (None: fp16 pass)
+
+    def _resolves(self, records: int) -> bool:
+        """Does the library run a gated search of this pipeline's shape with these `records` (under this pipeline's policy), or refuse it?"""
+        try:
+            with _lib.using(self.config) if self.config is not None else contextlib.nullcontext():
+                _lib.search_plan(records, self.d, self.n, self.m)
+            return True
+        except RuntimeError:
+            return False
 
     def prepare_map(self, b_desc: torch.Tensor) -> None:
         """IndexFlatIP.add: normalise + convert the map once (it is immutable per scene); every buffer
