@@ -109,6 +109,8 @@ int vfm_l2norm_rows_f32(float *x, int64_t n, int d, float *inv_out, vfm_stream_t
 /* precision modes of the top-1 search */
 #define VFM_MATCH_FAST 0  /* fp16 MFMA coarse pass + exact fp64 re-decision (indices == EXACT) */
 #define VFM_MATCH_EXACT 1 /* all-pairs fp64 on the vector ALUs (small sizes / cross-check) */
+#define VFM_MATCH_NARROW 2 /* vfm_match_mutual_l2 only, d <= VFM_L2_NARROW_MAX_D: f32 MFMA screening + the fp64 decision inline */
+#define VFM_L2_NARROW_MAX_D 64
 
 /* faiss::IndexFlatIP(d).add(m, xb) + .search(n, xq, k=1, D, I) on rows that are L2-normalised
  * first (the whole of VHM:469-495).  q, b: RAW (un-normalised) fp32 descriptors, row-major
@@ -365,7 +367,16 @@ int vfm_threshold_compact(const float *sim, const int64_t *idx, int64_t n, doubl
  * term in two appended columns (d <= 510) or in the accumulator start of each map row (wider), then the
  * fp64 decision among the candidates inside the proven error window -- same results as VFM_MATCH_EXACT
  * (all-pairs fp64), which descriptors wider than 768 fall back to.  For d = 256 ... 768 in steps of 128 the a -> b direction
- * runs the int8 coarse pass instead (map rows sorted by norm; csrc/match_l2.hip), the full b -> a direction the fp16 pass. */
+ * runs the int8 coarse pass instead (map rows sorted by norm; csrc/match_l2.hip), the full b -> a direction the fp16 pass.
+ * prec_mode VFM_MATCH_NARROW (1 <= d <= VFM_L2_NARROW_MAX_D = 64; a wider d fails with VFM_EINVAL before anything is launched):
+ * one sweep per direction on the f32-input MFMA (csrc/match_l2_narrow.hip).  |b~|^2 - 2 a~.b~ of the commonly scaled rows is
+ * screened in f32 inside a proven window of (8 Kp + 16) 2^-24 (Kp = d rounded up to even), and every row inside the
+ * window of the smallest screened value so far is decided at once by the fp64 distance above on the original rows -- no candidate
+ * lists, no all-pairs fallback, identical rows are all evaluated.  Same contract, bit for bit: nn_ab[i] = the arg-min over j of
+ * acc = acc + t * t, t = (double)a[i][k] - (double)b[j][k], k ascending, no contraction, ties -> lowest j; d2_ab[i] = that value;
+ * nn_ba the same with the roles swapped.  The workspace is sized by vfm_match_mutual_l2_workspace_bytes alone.
+ * All modes: the inputs must be finite (no NaN, no infinity), and row norms below 1.8e19 keep the fp32 norms the scale is taken
+ * from finite (beyond that NARROW evaluates every pair exactly). */
 size_t vfm_match_mutual_l2_workspace_bytes(int64_t n, int64_t m, int d, int prec_mode, int mutual);
 int vfm_match_mutual_l2(const float *a, int64_t n, const float *b, int64_t m, int d, int prec_mode,
                         int64_t *nn_ab, double *d2_ab, int64_t *nn_ba, void *ws, size_t ws_bytes,
@@ -377,7 +388,8 @@ int vfm_match_mutual_l2(const float *a, int64_t n, const float *b, int64_t m, in
  * vfm_match_mutual_l2 returns them.  The filter reads the reverse direction only at the matched map rows, so the reverse search
  * runs on n gathered queries instead of all m rows.  d = 256 ... 768 in steps of 128 run the int8 coarse pass both ways (map
  * rows sorted by norm, exact fp64 decision on the original rows: same pairs as the all-pairs fp64 search) -- 20 000 x 200 000 x
- * 384: see DESIGN.md 4.1 "Row A6"; other widths take vfm_match_mutual_l2's path and filter its result. */
+ * 384: see DESIGN.md 4.1 "Row A6".  d <= 64 (FPFH's 33 columns): both directions in VFM_MATCH_NARROW, the reverse one again on the n
+ * matched rows only.  Other widths take vfm_match_mutual_l2's path and filter its result.  Finite inputs, as there. */
 size_t vfm_match_mutual_pairs_workspace_bytes(int64_t n, int64_t m, int d);
 int vfm_match_mutual_pairs(const float *a, int64_t n, const float *b, int64_t m, int d, int64_t *idx0_out,
                            int64_t *idx1_out, int64_t *count_out, int64_t *nn_ab_out, double *d2_ab_out, void *ws,

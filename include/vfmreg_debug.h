@@ -12,6 +12,7 @@
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
  *   - vfm_debug_search_plan  reads the calling thread's vfm_config and nothing else; host memory only.
+ *   - vfm_debug_l2_narrow_slices  host arithmetic only; vfm_debug_l2_narrow_evals  reads a workspace's counters and synchronises the device.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
  */
@@ -99,6 +100,14 @@ int vfm_debug_ransac_state(const void *ws, int64_t c_max, int32_t n_iter, int32_
  * by the forward's own carving routine.  After a forward the buffers hold what the LAST block left: q / k / vt are not written under
  * "vit_fused_qkv", h is not written under "vit_fused_mlp".  Does not touch the device. */
 int vfm_debug_vit_workspace_layout(const vfm_vit_config *cfg, int B, int64_t *offsets_host, int64_t *bytes_host);
+
+/* VFM_MATCH_NARROW (csrc/match_l2_narrow.hip).  vfm_debug_l2_narrow_slices: the number of map slices the host rule gives a search of n
+ * queries among m map rows (the grid is ceil(n / 256) query blocks x slices); 0 for n or m <= 0.  Host only, no device is touched.
+ * vfm_debug_l2_narrow_evals: how many (query, map row) pairs the last vfm_match_mutual_l2(VFM_MATCH_NARROW) or vfm_match_mutual_pairs
+ * (d <= 64) in workspace `ws` decided by the exact fp64 distance -- out2_host: HOST int64[2], [0] the a -> b direction, [1] the reverse
+ * one (0 if it did not run).  Synchronises the device. */
+int vfm_debug_l2_narrow_slices(int64_t n, int64_t m);
+int vfm_debug_l2_narrow_evals(const void *ws, int64_t *out2_host);
 
 #ifdef __cplusplus
 }

@@ -328,6 +328,17 @@ __device__ __forceinline__ unsigned coarse_emit_chunk_best(const CoarseArgs& a, 
     return w1;
 }
 
+// the common scale of a Euclidean search (l2_maxnorm_kernel leaves the largest fp32 sum of squares of both sets in max_bits):
+// 2^-k with 2^k >= sqrt(max sum of squares) * 1.01 (the fp32 sums above are good to ~1e-6)
+__device__ __forceinline__ float l2_scale(const unsigned* max_bits) {
+    const float mx = __uint_as_float(*max_bits);
+    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.0f;
+    const float s = sqrtf(mx) * 1.01f;
+    int e;
+    (void)frexpf(s, &e);  // s = f * 2^e, f in [0.5, 1)  =>  2^e > s
+    return ldexpf(1.0f, -e);
+}
+
 // arg-max over a wavefront, ties -> lowest index (the oracle's rule)
 __device__ __forceinline__ void wave_argmax(double& s, long long& j) {
 #pragma unroll
@@ -775,5 +786,12 @@ int launch_i8_rescans(const SearchWs& w, const CoarseArgs& a, const Prepared& Q,
 int probe_half_select(const SearchPlan& plan, const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st);
 int exact_ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, int64_t* idx_out, float* sim_out, void* ws,
                   hipStream_t st);
+// match_l2_narrow.hip (VFM_MATCH_NARROW, d <= VFM_L2_NARROW_MAX_D): one direction of the f32-MFMA Euclidean search -- query i = row
+// (qperm ? qperm[i] : i) of q, among the m rows of b -- in a workspace of l2n_dir_bytes(nq, m, d); max_bits as l2_maxnorm_kernel left it
+// for BOTH sets; *evals (device) is incremented by the number of exact evaluations
+int l2n_slices(int64_t nq, int64_t m);
+size_t l2n_dir_bytes(int64_t nq, int64_t m, int d);
+int l2n_search(const float* q, const int* qperm, int64_t nq, const float* b, int64_t m, int d, const unsigned* max_bits, int64_t* nn,
+               double* d2, void* ws_dir, unsigned long long* evals, hipStream_t st);
 
 }  // namespace vfmm

@@ -1,6 +1,7 @@
 // match_l2.hip -- exact Euclidean nearest neighbours both ways (row A6: find_correspondences, registration_node.py:482-538)
 // on the fp16 coarse pass: common power-of-two scale, the norm term in two appended fp16 columns (or a row bias in the
-// accumulator start), fp64 decision in the oracle's order ("Row A6").
+// accumulator start), fp64 decision in the oracle's order ("Row A6").  Rows of at most 64 columns have a search of
+// their own on the f32 MFMA (VFM_MATCH_NARROW, match_l2_narrow.hip); the entry points below route to it.
 #include <hipcub/hipcub.hpp>
 
 #include "match_internal.h"
@@ -72,10 +73,7 @@ __global__ __launch_bounds__(256) void nn_l2_kernel(const float* __restrict__ a,
 // same window / select apply; the decision among the candidates is the oracle's fp64 squared
 // distance (sequential k), ties -> lowest index.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void l2_maxnorm_kernel(const float* __restrict__ x, int64_t rows, int d,
-                                                         unsigned* __restrict__ max_bits) {
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
+__device__ __forceinline__ void l2_maxnorm_row(const float* __restrict__ x, int64_t r, int d, unsigned* __restrict__ max_bits) {
     float p = 0.f;
     for (int k = lane_id(); k < d; k += 64) {
         const float v = x[r * (int64_t)d + k];
@@ -87,16 +85,23 @@ __global__ __launch_bounds__(256) void l2_maxnorm_kernel(const float* __restrict
     if (lane_id() == 0 && __float_as_uint(p) > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         atomicMax(max_bits, __float_as_uint(p));
 }
-
-// 2^-k with 2^k >= sqrt(max sum of squares) * 1.01 (the fp32 sums above are good to ~1e-6)
-__device__ __forceinline__ float l2_scale(const unsigned* max_bits) {
-    const float mx = __uint_as_float(*max_bits);
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.0f;
-    const float s = sqrtf(mx) * 1.01f;
-    int e;
-    (void)frexpf(s, &e);  // s = f * 2^e, f in [0.5, 1)  =>  2^e > s
-    return ldexpf(1.0f, -e);
+__global__ __launch_bounds__(256) void l2_maxnorm_kernel(const float* __restrict__ x, int64_t rows, int d,
+                                                         unsigned* __restrict__ max_bits) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    l2_maxnorm_row(x, r, d, max_bits);
 }
+// both sets in one launch (the narrow search: a 5000 x 5000 call is a handful of launches long)
+__global__ __launch_bounds__(256) void l2_maxnorm2_kernel(const float* __restrict__ a, int64_t n, const float* __restrict__ b, int64_t m, int d,
+                                                          unsigned* __restrict__ max_bits) {
+    const int64_t na = (n + 3) / 4;
+    const bool second = (int64_t)blockIdx.x >= na;
+    const int64_t r = ((int64_t)blockIdx.x - (second ? na : 0)) * 4 + (threadIdx.x >> 6);
+    if (r >= (second ? m : n)) return;
+    l2_maxnorm_row(second ? b : a, r, d, max_bits);
+}
+
+// (l2_scale: match_internal.h -- shared with the f32 search of match_l2_narrow.hip)
 
 // one workgroup (4 waves) per 32-row tile; role 0 = query (extra columns 1, 1), 1 = map (-hi, -lo)
 // aug = 1: the norm term travels in two appended columns (d + 2 <= kp); aug = 0 (d > 510, kp = d rounded up
@@ -664,6 +669,48 @@ int l2_search(const float* q, void* qprep, int64_t n, const float* b, void* bpre
 }
 
 
+// ---- VFM_MATCH_NARROW (match_l2_narrow.hip): [evaluation counters | max_bits | forward | reverse]; pairs: the reverse direction has
+// the n matched map rows as queries and a as map, and the filter's arrays follow
+inline bool l2_narrow(int d) { return d >= 1 && d <= VFM_L2_NARROW_MAX_D; }
+struct L2NarrowWs {
+    unsigned long long* evals;   // [0] forward, [1] reverse (first in the workspace: vfm_debug_l2_narrow_evals)
+    unsigned* max_bits;
+    void* fwd;
+    void* rev;
+    int64_t* nn_ab;   // pairs only
+    int64_t* nn_rev;
+    int* qperm;
+    size_t bytes;
+};
+// reverse: 0 = none, 1 = every row of b among a (vfm_match_mutual_l2), 2 = the n matched rows of b among a + the filter (vfm_match_mutual_pairs)
+inline L2NarrowWs carve_l2_narrow(void* p, int64_t n, int64_t m, int d, int reverse) {
+    VfmCarver c(p);
+    L2NarrowWs w;
+    w.evals = c.take<unsigned long long>(32);
+    w.max_bits = c.take<unsigned>(64);
+    w.fwd = c.take<unsigned char>(l2n_dir_bytes(n, m, d));
+    w.rev = nullptr;
+    w.nn_ab = w.nn_rev = nullptr;
+    w.qperm = nullptr;
+    if (reverse == 1) w.rev = c.take<unsigned char>(l2n_dir_bytes(m, n, d));
+    if (reverse == 2) {
+        w.rev = c.take<unsigned char>(l2n_dir_bytes(n, n, d));
+        w.nn_ab = c.take<int64_t>((size_t)n);
+        w.nn_rev = c.take<int64_t>((size_t)n);
+        w.qperm = c.take<int>((size_t)n);
+    }
+    w.bytes = c.used();
+    return w;
+}
+// the common scale of both sets, and the counters cleared
+int l2_narrow_begin(const float* a, int64_t n, const float* b, int64_t m, int d, const L2NarrowWs& w, hipStream_t st) {
+    // (the counters' 256 bytes and max_bits are neighbours in the carved layout: one fill)
+    VFM_CHECK_HIP(hipMemsetAsync(w.evals, 0, (size_t)(reinterpret_cast<unsigned char*>(w.max_bits) - reinterpret_cast<unsigned char*>(w.evals)) + sizeof(unsigned), st));
+    hipLaunchKernelGGL(l2_maxnorm2_kernel, dim3((unsigned)((n + 3) / 4 + (m + 3) / 4)), dim3(256), 0, st, a, n, b, m, d, w.max_bits);
+    VFM_CHECK_LAUNCH("l2_maxnorm2_kernel");
+    return VFM_OK;
+}
+
 // ---- int8 Euclidean search (see the block comment above match_select_l2_kernel)
 inline bool l2_i8(int d) { return i8_capable(d); }
 
@@ -805,6 +852,7 @@ int l2i8_forward(const float* a, int64_t n, const float* b, int64_t m, int d, co
 using namespace vfmm;
 
 VFM_EXPORT size_t vfm_match_mutual_l2_workspace_bytes(int64_t n, int64_t m, int d, int prec_mode, int mutual) {
+    if (prec_mode == VFM_MATCH_NARROW) return (l2_narrow(d) && n > 0 && m > 0) ? carve_l2_narrow(nullptr, n, m, d, mutual != 0).bytes : 256;
     if (prec_mode == VFM_MATCH_EXACT || l2_padded_k(d) == 0 || n <= 0 || m <= 0) return 256;
     // int8-capable widths: the forward direction runs the int8 pass (its workspace sits behind the fp16 path's, which still
     // serves the full reverse direction nn_ba)
@@ -814,6 +862,7 @@ VFM_EXPORT size_t vfm_match_mutual_l2_workspace_bytes(int64_t n, int64_t m, int 
 VFM_EXPORT size_t vfm_match_mutual_pairs_workspace_bytes(int64_t n, int64_t m, int d) {
     if (n <= 0 || m <= 0 || d <= 0) return 256;
     if (l2_i8(d)) return carve_l2i8(nullptr, n, m, d, 1).bytes;
+    if (l2_narrow(d)) return carve_l2_narrow(nullptr, n, m, d, 2).bytes;
     // other widths: nn_ab / nn_ba by vfm_match_mutual_l2 (FAST where it exists) + the filter
     return vfm_align_up((size_t)n * sizeof(int64_t), 256) * 2 + vfm_align_up((size_t)m * sizeof(int64_t), 256) + 512 +
            vfm_match_mutual_l2_workspace_bytes(n, m, d, l2_padded_k(d) ? VFM_MATCH_FAST : VFM_MATCH_EXACT, 1);
@@ -826,6 +875,20 @@ VFM_EXPORT int vfm_match_mutual_pairs(const float* a, int64_t n, const float* b,
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "mutual_pairs: more than 2^31 rows");
     if (ws_bytes < vfm_match_mutual_pairs_workspace_bytes(n, m, d)) return vfm_fail(VFM_EWORKSPACE, "mutual_pairs: workspace too small");
     hipStream_t st = (hipStream_t)stream;
+    if (l2_narrow(d)) {
+        // both directions on the f32 MFMA (match_l2_narrow.hip); the reverse one restricted to what the filter reads: queries = the
+        // matched map rows b[nn_ab[i]], map = a
+        const L2NarrowWs w = carve_l2_narrow(ws, n, m, d, 2);
+        int64_t* nn_ab = nn_ab_out ? nn_ab_out : w.nn_ab;
+        if (int rc = l2_narrow_begin(a, n, b, m, d, w, st)) return rc;
+        if (int rc = l2n_search(a, nullptr, n, b, m, d, w.max_bits, nn_ab, d2_ab_out, w.fwd, w.evals, st)) return rc;
+        hipLaunchKernelGGL(l2i8_to_int_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int64_t*)nn_ab, w.qperm, n);
+        if (int rc = l2n_search(b, w.qperm, n, a, n, d, w.max_bits, w.nn_rev, nullptr, w.rev, w.evals + 1, st)) return rc;
+        hipLaunchKernelGGL(l2_mutual_pairs_kernel, dim3(1), dim3(1024), 0, st, (const int64_t*)nn_ab, (const int64_t*)w.nn_rev, n, idx0_out,
+                           idx1_out, count_out);
+        VFM_CHECK_LAUNCH("l2_mutual_pairs_kernel");
+        return VFM_OK;
+    }
     if (!l2_i8(d)) {
         VfmCarver c(ws);
         int64_t* nn_ab = c.take<int64_t>((size_t)n);
@@ -869,12 +932,24 @@ VFM_EXPORT int vfm_match_mutual_l2(const float* a, int64_t n, const float* b, in
                                    int64_t* nn_ab, double* d2_ab, int64_t* nn_ba, void* ws, size_t ws_bytes,
                                    vfm_stream_t stream) {
     VFM_CHECK_ARG(n > 0 && m > 0 && d > 0 && a && b && nn_ab, "mutual_l2: bad arguments");
-    VFM_CHECK_ARG(prec_mode == VFM_MATCH_FAST || prec_mode == VFM_MATCH_EXACT, "mutual_l2: unknown prec_mode %d", prec_mode);
+    VFM_CHECK_ARG(prec_mode == VFM_MATCH_FAST || prec_mode == VFM_MATCH_EXACT || prec_mode == VFM_MATCH_NARROW, "mutual_l2: unknown prec_mode %d",
+                  prec_mode);
+    VFM_CHECK_ARG(prec_mode != VFM_MATCH_NARROW || l2_narrow(d), "mutual_l2: VFM_MATCH_NARROW serves d <= %d (VFM_L2_NARROW_MAX_D), got d = %d",
+                  VFM_L2_NARROW_MAX_D, d);
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "mutual_l2: more than 2^31 rows");
     // (checked on every path, the all-pairs one included: a caller sizes the workspace by vfm_match_mutual_l2_workspace_bytes alone)
     if (ws_bytes < vfm_match_mutual_l2_workspace_bytes(n, m, d, prec_mode, nn_ba != nullptr))
         return vfm_fail(VFM_EWORKSPACE, "mutual_l2: workspace too small");
     hipStream_t st = (hipStream_t)stream;
+    if (prec_mode == VFM_MATCH_NARROW) {
+        VFM_CHECK_ARG(ws, "mutual_l2: workspace required in NARROW mode");
+        const L2NarrowWs w = carve_l2_narrow(ws, n, m, d, nn_ba != nullptr);
+        if (int rc = l2_narrow_begin(a, n, b, m, d, w, st)) return rc;
+        if (int rc = l2n_search(a, nullptr, n, b, m, d, w.max_bits, nn_ab, d2_ab, w.fwd, w.evals, st)) return rc;
+        if (nn_ba)
+            if (int rc = l2n_search(b, nullptr, m, a, n, d, w.max_bits, nn_ba, nullptr, w.rev, w.evals + 1, st)) return rc;
+        return VFM_OK;
+    }
     const int kp = l2_padded_k(d);
     if (prec_mode == VFM_MATCH_EXACT || kp == 0) {
         // all-pairs fp64 (also the path for descriptors wider than 768)

@@ -138,6 +138,8 @@ DEBUG_SIGNATURES = {
     "vfm_debug_ransac_counts": (C.c_int, [c_vp, c_i64, C.c_int, c_vp]),
     "vfm_debug_ransac_state": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_vit_workspace_layout": (C.c_int, [C.POINTER(VitConfig), C.c_int, C.POINTER(c_i64), C.POINTER(c_i64)]),
+    "vfm_debug_l2_narrow_slices": (C.c_int, [c_i64, c_i64]),
+    "vfm_debug_l2_narrow_evals": (C.c_int, [c_vp, C.POINTER(c_i64)]),
 }
 
 

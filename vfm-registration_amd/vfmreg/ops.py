@@ -16,6 +16,8 @@ from . import _lib
 
 FAST = 0
 EXACT = 1
+NARROW = 2          # match_mutual_l2 only: rows of at most NARROW_MAX_D columns on the f32 MFMA (VFM_MATCH_NARROW)
+NARROW_MAX_D = 64
 
 PROJ_NCLT, PROJ_ROBOTCAR, PROJ_KITTI = 0, 1, 2
 
@@ -194,12 +196,15 @@ def threshold_compact(sim: torch.Tensor, idx: Optional[torch.Tensor], thr: float
 
 
 def match_mutual_l2(a: torch.Tensor, b: torch.Tensor, mutual: bool = True, prec: int = FAST):
-    """Exact Euclidean 1-NN a->b (and b->a) (registration_node.py:485-496).  FAST and EXACT return the same
-    indices and distances; FAST runs the all-pairs part on the matrix cores."""
+    """Exact Euclidean 1-NN a->b (and b->a) (registration_node.py:485-496).  FAST, EXACT and NARROW return the same
+    indices and distances; FAST runs the all-pairs part on the fp16 matrix cores, NARROW (rows of at most 64 columns)
+    on the f32 ones with the exact decision inline."""
     _chk(a, torch.float32, "a")
     _chk(b, torch.float32, "b")
     if a.shape[1] != b.shape[1]:
         raise ValueError("Invalid shape")
+    if prec == NARROW and a.shape[1] > NARROW_MAX_D:
+        raise ValueError(f"match_mutual_l2: NARROW serves rows of at most {NARROW_MAX_D} columns, got {a.shape[1]}")
     lib = _lib.load()
     n, m, d = a.shape[0], b.shape[0], a.shape[1]
     nn_ab = torch.empty(n, dtype=torch.int64, device=a.device)

@@ -58,6 +58,18 @@ def find_correspondences(feats0: np.ndarray, feats1: np.ndarray, n_points: int =
     return i0.cpu().numpy(), i1.cpu().numpy()
 
 
+# Rows of at most 64 columns have a search of their own on the f32 matrix cores (ops.NARROW).  On FPFH features it beats the fp16 search
+# (ops.FAST) at every size measured -- 2x at 275 x 2751, 33x at 17 651 x 176 073 --, on well-separated random rows it ties up to 2000 x
+# 2000 and loses from 5000 x 5000 on (profiles/l2_narrow_timing.md).  The forward search takes it from this many rows on:
+# the first power of two above the random shape that lost.
+NARROW_MIN_ROWS = 8192
+
+
+def l2_search_mode(n: int, m: int, d: int) -> int:
+    """The precision mode ``find_correspondences_device`` passes to ``ops.match_mutual_l2`` for n queries among m rows of d columns."""
+    return ops.NARROW if d <= ops.NARROW_MAX_D and max(n, m) >= NARROW_MIN_ROWS else ops.FAST
+
+
 def find_correspondences_device(f0: torch.Tensor, f1: torch.Tensor, n_points: int = 5000, mutual_filter: bool = True):
     """``find_correspondences`` on float32 rows that are on the device: the two index lists as device tensors, in the same order."""
     if mutual_filter:   # RN:520-532 in one call: the reverse direction is searched only at the matched rows of feats1
@@ -65,7 +77,8 @@ def find_correspondences_device(f0: torch.Tensor, f1: torch.Tensor, n_points: in
         k = int(count.item())
         return i0[:k], i1[:k]
     # RN:505-518: the n_points pairs with the smallest distance (numpy's argpartition decides which and in what order: on the host)
-    nn01, d2, _ = ops.match_mutual_l2(f0, f1, mutual=False)
+    # (same indices and distances in every mode; ops.match_mutual_pairs above runs rows of at most 64 columns in NARROW at every size)
+    nn01, d2, _ = ops.match_mutual_l2(f0, f1, mutual=False, prec=l2_search_mode(f0.shape[0], f1.shape[0], f0.shape[1]))
     dists = np.sqrt(d2.cpu().numpy())
     n = min(n_points, len(dists) - 1)
     top = torch.from_numpy(np.argpartition(dists, n)[:n]).to(nn01.device)
