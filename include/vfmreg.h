@@ -90,7 +90,7 @@ const char *vfm_build_info(void);
  *                        fifths full: a single round runs in lockstep and ends level with the two kernels --, n > 0
  *                        from n images per call on, -1 never
  *   and the single fields behind the codes: "coarse_qsets", "seed_units", "select_variant", "mx6_t4", "mx6_ns3", "prep_form" (0, 1, 3, 4),
- *   "finish_short", "rescan_rows", "vit_*", "voxel_replay2", "voxel_one_launch", "voxel_trace", "voxel_grid_ppt" (vfm_config_get reads these;
+ *   "finish_short", "rescan_rows", "rescore_block" (64 / 256: queries per workgroup of the fp64 decision, the same bits; anything else is refused; an untouched config reads 0: 256 behind the half-width record kinds, 64 elsewhere), "vit_*", "voxel_replay2", "voxel_one_launch", "voxel_trace", "voxel_grid_ppt" (vfm_config_get reads these;
  *   cfg == NULL there: what the calling thread's entry points would read now). */
 typedef struct vfm_config vfm_config_t;
 int vfm_config_create(vfm_config_t **out);

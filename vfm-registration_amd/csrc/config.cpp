@@ -30,7 +30,7 @@ const Field k_fields[] = {
     {"mx6_tune", &VfmConfig::mx6_tune},
     {"mx6_ns3", &VfmConfig::mx6_ns3},                {"prep_form", &VfmConfig::prep_stream},
     {"finish_short", &VfmConfig::finish_short},      {"rescan_rows", &VfmConfig::rescan_rows},
-    {"half_noi8", &VfmConfig::half_noi8},
+    {"half_noi8", &VfmConfig::half_noi8},            {"rescore_block", &VfmConfig::rescore_block},
     {"vit_preprocess_patch", &VfmConfig::vit_preprocess_patch}, {"vit_xcd", &VfmConfig::vit_xcd},
     {"vit_cfg_narrow", &VfmConfig::vit_cfg_narrow},  {"vit_cfg_wide", &VfmConfig::vit_cfg_wide},
     {"vit_wpw", &VfmConfig::vit_wpw},                {"vit_hot_a", &VfmConfig::vit_hot_a},
@@ -108,6 +108,8 @@ VFM_EXPORT int vfm_config_set(vfm_config_t* cfg, const char* key, int64_t value)
     // (the by-width choice between the two older preparation forms is gone: DESIGN.md R5.10)
     if ((!strcmp(key, "coarse_variant") && value == 42) || (!strcmp(key, "prep_form") && value == 2))
         return vfm_fail(VFM_EINVAL, "config_set: %s %lld (fp6 operand preparation by width) has been removed", key, (long long)value);
+    if (!strcmp(key, "rescore_block") && value != 64 && value != 256)
+        return vfm_fail(VFM_EINVAL, "config_set: rescore_block %lld (a workgroup of match_rescore_kernel owns 64 or 256 queries)", (long long)value);
     if (!strcmp(key, "coarse_variant")) { set_coarse_variant(cfg->c, (int)value); return VFM_OK; }
     if (!strcmp(key, "voxel_small")) { set_voxel_small(cfg->c, (int)value); return VFM_OK; }
     if (!strcmp(key, "vit_gemm")) { set_vit_gemm(cfg->c, (int)(value >> 32), (int)(int32_t)(uint32_t)(value & 0xffffffffll)); return VFM_OK; }

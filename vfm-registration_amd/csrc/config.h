@@ -18,6 +18,9 @@ struct VfmConfig {
     int finish_short = 0;      // "coarse_variant" 50 / 51: chunk-major rescan as long-lived (default) / short workgroups
     int half_noi8 = 1;         // 1 (default): callers that follow the policy (vfmreg/pipeline.py) run VFM_RECORDS_MX6_HALF_FUSED without the int8 image
                                // (VFM_PREPARE_NO_I8 + VFM_RECORDS_NO_I8); 0: with it, as before (A/B).  The library itself only stores the key.
+    int rescore_block = 0;     // queries per workgroup of match_rescore_kernel: 64 (wave 0 owns them) / 256 (thread = query, lane = pair, a quarter of the
+                               // workgroups, no product staging in the LDS); the same bits either way.  0 (an untouched config; "rescore_block" itself takes
+                               // 64 / 256 only): by the plan -- 256 behind the half-width passes, whose lists are short, 64 elsewhere
     int rescan_rows = 1;       // "coarse_variant" 60 / 61: rescan gathers its queries from the fragment tiles / the row-major int8 scan (default)
     int mx6_tune = 0;          // (A/B) bit 0: s_setprio 1 for waves 4 - 7 of the fp6 coarse kernel; bit 1: its ring five steps deep (headline shape);
                                // bit 2: query sets past the end of the scan are multiplied as copies of tile 0 again (default: they do no matrix work)

@@ -1835,6 +1835,40 @@ __device__ __forceinline__ double dot_norm_f64(const float* __restrict__ qrow_n,
     return acc;
 }
 
+// exact score of ONE pair by one lane: the products of match_rescore_kernel's batches (fp32 normalisation, exact fp64 product), added
+// in ascending k.  Two buffers of 32 columns: the loads of the next 32 are in flight while a buffer's products are added.
+__device__ __forceinline__ double dot_pair_f64(Rows q, int64_t qe, float iq, Rows b, int64_t be, float ib, int d) {
+    double acc = 0.0;
+    auto add4 = [&](const float4& qv, const float4& bv) __attribute__((always_inline)) {
+        acc = acc + (double)(qv.x * iq) * (double)(bv.x * ib);
+        acc = acc + (double)(qv.y * iq) * (double)(bv.y * ib);
+        acc = acc + (double)(qv.z * iq) * (double)(bv.z * ib);
+        acc = acc + (double)(qv.w * iq) * (double)(bv.w * ib);
+    };
+    float4 q0[8], b0[8], q1[8], b1[8];
+    auto fetch = [&](float4 (&qq)[8], float4 (&bb)[8], int k) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            qq[i] = q.ld4(qe + k + 4 * i);
+            bb[i] = b.ld4(be + k + 4 * i);
+        }
+    };
+    auto use = [&](const float4 (&qq)[8], const float4 (&bb)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) add4(qq[i], bb[i]);
+    };
+    const int dmain = d & ~63;
+    if (dmain) fetch(q0, b0, 0);
+    for (int k = 0; k < dmain; k += 64) {
+        fetch(q1, b1, k + 32);
+        use(q0, b0);
+        if (k + 64 < dmain) fetch(q0, b0, k + 64);
+        use(q1, b1);
+    }
+    for (int k = dmain; k < d; k += 4) add4(q.ld4(qe + k), b.ld4(be + k));   // d % 4 == 0
+    return acc;
+}
+
 // Exact decision among the candidates: one workgroup (4 waves) owns 64 queries; thread t < 64 = query t.
 //   single-row candidates (the common case, ~1.3 per query): the block's (query, candidate) pairs are
 //   flattened and taken 64 at a time; per batch and per 96-wide k chunk the four waves compute the fp64
@@ -1843,29 +1877,43 @@ __device__ __forceinline__ double dot_norm_f64(const float* __restrict__ qrow_n,
 //   products in ascending k -- 64 different in-order chains at once instead of one chain per wavefront.
 //   whole-chunk candidates (rare): per flagged query, the lanes of wave 0 score their own rows of the chunk.
 // The accumulation order is the oracle's (sequential k), ties -> lowest index, sim = (float)score.
+//
+// QB ("rescore_block"): queries per workgroup.  64: as above -- wave 0 owns the queries, ceil(n / 64) workgroups of 65 KB of LDS each, on
+// D.2 data about 32 pairs per workgroup: half a batch, three waves at barriers, more than one workgroup per compute unit for ~10 000 dot
+// products.  256: thread t = query t, the pair counts are prefix-summed over the four waves (per wave, then the waves' totals through
+// the LDS), and an epoch's pairs are dealt to the four waves in equal runs, LANE = PAIR: a lane reads its query row and its map row
+// itself (64 bytes of each per step, the next step's loads in flight) and adds the products in ascending k (dot_pair_f64) -- no product
+// staging, no barrier inside an epoch, 14 KB of LDS, a quarter of the workgroups.  Every fp64 sum is the same chain of the same values
+// and every query folds its own pairs in the same order: idx / sim are bit-identical.  Whole-chunk entries: each wave takes its own
+// flagged queries (a normalised row per wave in the LDS).
 constexpr int RS_KC = 96;             // k values per chunk (24 float4 per row)
 constexpr int RS_STRIDE = RS_KC + 1;  // doubles per LDS row: 194 words == 2 (mod 64) -> conflict-free ds_read_b64
 constexpr int RS_PAIRS = 1024;        // pair slots per epoch (a block has ~80 pairs; more run in further epochs)
+template <int QB>
 __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float* __restrict__ invq,
                                                             Rows b, const float* __restrict__ invb,
                                                             int64_t n, int64_t m, int d, const int* __restrict__ cand_cnt,
                                                             const unsigned* __restrict__ cand, int cap,
                                                             int64_t* __restrict__ idx_out, float* __restrict__ sim_out, float min_sim) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double* P = reinterpret_cast<double*>(smem);               // [64][RS_STRIDE] products
-    double* pscore = P + 64 * RS_STRIDE;                       // [RS_PAIRS] exact score per pair of the epoch
-    float* qn = reinterpret_cast<float*>(pscore + RS_PAIRS);   // [d] normalised query row (chunk rescans)
+    double* P = reinterpret_cast<double*>(smem);               // [64][RS_STRIDE] products (QB 64 only)
+    double* pscore = P + (QB > 64 ? 0 : 64 * RS_STRIDE);       // [RS_PAIRS] exact score per pair of the epoch
+    float* qn = reinterpret_cast<float*>(pscore + RS_PAIRS);   // [QB / 64][d] normalised query row (chunk rescans), one per owning wave
+    constexpr int NW = QB / 64;                                // waves that own queries
+    static_assert(QB == 64 || QB == 256, "a workgroup's queries: wave 0's lanes, or its 256 threads (p_q holds a query as a byte)");
     __shared__ unsigned p_j[RS_PAIRS];                         // pair -> map row
-    __shared__ unsigned char p_q[RS_PAIRS];                    // pair -> query lane
-    __shared__ long long s_j[64];
-    __shared__ float s_iq[64], s_ib[64];
-    __shared__ int s_ql[64];
-    __shared__ int s_total;
+    __shared__ unsigned char p_q[RS_PAIRS];                    // pair -> query of the block
+    __shared__ long long s_j[QB > 64 ? 1 : 64];                // (QB 64) the batch's slots
+    __shared__ float s_iq[QB > 64 ? 1 : 64], s_ib[QB > 64 ? 1 : 64];
+    __shared__ int s_ql[QB > 64 ? 1 : 64];
+    __shared__ int s_wsum[4];                                  // pairs of each owning wave's queries
+    __shared__ float s_qinv[QB > 64 ? QB : 1];                 // (QB 256) 1 / |q| of every query of the block: a pair's query may live in another wave
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int64_t q0 = (int64_t)blockIdx.x * 64;
-    // per-query state lives in wave 0 (lane = query)
-    const int64_t qi = q0 + lane;
-    const bool owner = wave == 0;
+    const int64_t q0 = (int64_t)blockIdx.x * QB;
+    // per-query state lives in the owning waves: wave 0 (lane = query, and the batches' slots and chains), or all four (thread = query)
+    const int myq = QB > 64 ? (int)threadIdx.x : lane;         // the thread's query of the block
+    const int64_t qi = q0 + myq;
+    const bool owner = wave < NW, lead = wave == 0;
     const bool have = owner && qi < n;
     const float iq = have ? invq[qi] : 0.0f;
     int cnt = have ? cand_cnt[qi] : 0;
@@ -1888,10 +1936,17 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
             if (lane >= off) incl += v;
         }
         my_off = incl - my_pairs;
-        if (lane == 63) s_total = incl;
+        if (lane == 63) s_wsum[wave] = incl;
+        if constexpr (QB > 64) s_qinv[myq] = iq;
     }
     __syncthreads();
-    const int total = s_total;
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const int ws = s_wsum[w];
+        if (w < wave) my_off += ws;
+        total += ws;
+    }
     double best = 0.0;
     long long bj = -1;
     for (int E0 = 0; E0 < total; E0 += RS_PAIRS) {  // one epoch unless a block has > RS_PAIRS pairs
@@ -1903,16 +1958,28 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
                 if ((ce & 128u) || row_of(ce) >= m) continue;
                 if (k >= E0 && k < E0 + RS_PAIRS) {
                     p_j[k - E0] = (unsigned)row_of(ce);
-                    p_q[k - E0] = (unsigned char)lane;
+                    p_q[k - E0] = (unsigned char)myq;
                 }
                 ++k;
             }
         }
         __syncthreads();
-        for (int p0 = 0; p0 < ecount; p0 += 64) {
+        if constexpr (QB > 64) {
+            // wave w takes pairs [w per, (w + 1) per) of the epoch, 64 at a time: lane = pair
+            const int per = (ecount + 3) >> 2, wend = min(ecount, (wave + 1) * per);
+            for (int p0 = wave * per; p0 < wend; p0 += 64) {
+                const int pid = p0 + lane;
+                if (pid < wend) {
+                    const long long j = (long long)p_j[pid];
+                    const int ql = (int)p_q[pid];
+                    pscore[pid] = dot_pair_f64(q, (q0 + ql) * (int64_t)d, s_qinv[ql], b, j * (int64_t)d, invb[j], d);
+                }
+            }
+        } else {
+        for (int p0 = 0; p0 < ecount; p0 += 64) {   // (the loop keeps the parent's indentation)
             // slot `lane` of this batch = pair p0 + lane of the epoch
             long long j = -1;
-            if (owner) {
+            if (lead) {
                 const int pid = p0 + lane;
                 const int ql = (pid < ecount) ? (int)p_q[pid] : 0;
                 const float iqq = __shfl(iq, ql);  // all lanes of wave 0 take part
@@ -1961,7 +2028,7 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
                 }
                 __syncthreads();
                 if (k0 + RS_KC < d) fetch(k0 + RS_KC);
-                if (owner && j >= 0) {
+                if (lead && j >= 0) {
                     const double* src = P + lane * RS_STRIDE;
                     int k = 0;
                     for (; k + 8 <= kn; k += 8) {  // reads first, then the in-order chain
@@ -1975,7 +2042,8 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
                 }
                 __syncthreads();
             }
-            if (owner && j >= 0) pscore[p0 + lane] = acc;
+            if (lead && j >= 0) pscore[p0 + lane] = acc;
+        }
         }
         __syncthreads();
         if (owner) {  // every query folds its own pairs of this epoch: best score, ties -> lowest index
@@ -1992,11 +2060,12 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
         __syncthreads();
     }
     if (!owner) return;
-    // whole-chunk candidates: wave 0 takes the flagged queries one by one
+    // whole-chunk candidates: an owning wave takes its flagged queries one by one
     if (__any(any_rescan)) {
+        if constexpr (QB > 64) qn += (size_t)wave * d;
         for (int ql = 0; ql < 64; ++ql) {
             if (!__shfl((int)any_rescan, ql)) continue;  // wave-uniform
-            const int64_t qq = q0 + ql;
+            const int64_t qq = q0 + (myq - lane) + ql;
             const float iqq = __shfl(iq, ql);
             const int cq = __shfl(cnt, ql);
             __builtin_amdgcn_wave_barrier();
@@ -2179,6 +2248,21 @@ __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__
     if (lane_id() == 0) inv_out[r] = (nr > 0.0f) ? inv : 1.0f;
 }
 
+template <int QB>
+int launch_rescore(Rows q, const Prepared& Q, Rows b, const Prepared& B, int64_t n, int64_t m, int d, const SearchWs& w,
+                   int64_t* idx_out, float* sim_out, float min_sim, hipStream_t st) {
+    const size_t lds = (size_t)((QB > 64 ? 0 : 64 * RS_STRIDE) + RS_PAIRS) * sizeof(double) + (size_t)(QB / 64) * d * sizeof(float);
+    static unsigned long long attr_set = 0ull;  // one bit per device
+    if (!attr_done(attr_set)) {
+        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel<QB>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_mark(attr_set);
+    }
+    hipLaunchKernelGGL(match_rescore_kernel<QB>, dim3((unsigned)((n + QB - 1) / QB)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m, d,
+                       w.cand_cnt, w.cand, w.cap, idx_out, sim_out, min_sim);
+    return VFM_OK;
+}
+
 }  // namespace
 
 // stage 2 of a search: candidate selection + exact fp64 decision (reads ws of stage 1), as the plan's steps in order
@@ -2318,18 +2402,13 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
 #undef VFM_REFINE
                 break;
             }
-            case FIN_RESCORE: {
-                const size_t lds = (size_t)(64 * RS_STRIDE + RS_PAIRS) * sizeof(double) + (size_t)d * sizeof(float);
-                static unsigned long long attr_set = 0ull;  // one bit per device
-                if (!attr_done(attr_set)) {
-                    VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_rescore_kernel),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                    attr_mark(attr_set);
-                }
-                hipLaunchKernelGGL(match_rescore_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), lds, st, q, Q.inv, b, B.inv, n, m,
-                                   d, w.cand_cnt, w.cand, w.cap, idx_out, sim_out, half ? gate : -__builtin_inff());
+            case FIN_RESCORE:   // ("rescore_block": the queries a workgroup owns; unset: 256 behind a half-width pass -- it is taken where few
+                                // (query, chunk) pairs survive, ~0.5 a query: a lane per pair over a quarter of the workgroups is enough --, 64
+                                // elsewhere: crowded lists want the workgroups (C3's pipeline lost 2.7 % with 256 everywhere))
+                VFM_TRY((vfm_cfg().rescore_block ? vfm_cfg().rescore_block : plan.half ? 256 : 64) == 256
+                            ? launch_rescore<256>(q, Q, b, B, n, m, d, w, idx_out, sim_out, half ? gate : -__builtin_inff(), st)
+                            : launch_rescore<64>(q, Q, b, B, n, m, d, w, idx_out, sim_out, half ? gate : -__builtin_inff(), st));
                 break;
-            }
             case FIN_EXACT:
                 hipLaunchKernelGGL(match_exact_kernel, dim3(256), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q, Q.inv,
                                    b, B.inv, n, m, d, w.fb_list, w.fb_count, idx_out, sim_out);
