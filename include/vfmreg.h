@@ -678,6 +678,38 @@ int vfm_mreach_mst(const int64_t *keys, const int32_t *order, const double *sort
 int vfm_hdbscan_labels_host(const int32_t *lo, const int32_t *hi, const double *w2, int64_t n, int min_cluster_size,
                             int32_t *labels_out);
 
+/* ------------------------------------------------------------------ descriptor PCA and the colour gate (IF:162-192, RN:696-702)
+ * csrc/pca.hip, DESIGN 7.6.  Rows x (n x d, row-major) are fp32 or fp16 (VFM_ROWS_F32 / VFM_ROWS_F16); both widen exactly to fp64, and
+ * everything below is fp64 and unfused.  1 <= d <= 768, n >= 1.  Every result is a pure function of the arguments: no floating-point
+ * atomics, the same bits from run to run and under every vfm_config_t.
+ *
+ * vfm_pca_moments: mean_out[d] = the column sums / n (fixed order of addition) and scatter_out[d x d] =
+ * sum_n (x_n - mean)(x_n - mean)^T on the fp64 matrix cores, exactly symmetric.  The workspace holds partial sums of row slabs whose
+ * number depends on d alone: vfm_pca_moments_workspace_bytes(d) does not grow with n and is below 40 MiB for every d <= 768
+ * (0 for a d outside the limits). */
+size_t vfm_pca_moments_workspace_bytes(int d);
+int vfm_pca_moments(const void *x, int dtype, int64_t n, int d, double *mean_out, double *scatter_out, void *ws, size_t ws_bytes,
+                    vfm_stream_t stream);
+/* y_out[n x k] = (x - mean) . components^T for components[k x d], 1 <= k <= 8, k <= d.  Per row and component the terms
+ * t_c = (double(x[c]) - mean[c]) * components[j][c] are added in this order (part of the contract): lane l = 0..63 starts from +0.0 and
+ * adds t_l, t_{l+64}, t_{l+128}, ... ascending; then for s = 32, 16, 8, 4, 2, 1 every lane sets p_l = p_l + p_{l xor s}.
+ * zero_rows_out[n]: 1 where every feature of the row compares equal to 0.  min_out[k], max_out[k]: over all rows, exact.
+ * The workspace (vfm_pca_project_workspace_bytes(): a constant, 256 KiB) holds per-workgroup minima and maxima. */
+size_t vfm_pca_project_workspace_bytes(void);
+int vfm_pca_project(const void *x, int dtype, int64_t n, int d, const double *mean, const double *components, int k, double *y_out,
+                    uint8_t *zero_rows_out, double *min_out, double *max_out, void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* v = (y - min[j]) / (max[j] - min[j]): the shift first, then the division by the largest shifted value, as FeatUp's pca does.
+ * values_out (nullable, n x k fp32): v rounded to fp32.  rgb_out (nullable, n x 3 uint8; needs k == 3 and zero_rows): v * 255.0
+ * truncated, black where zero_rows is set.  A component with max == min gives NaN in values_out and 0 in rgb_out.
+ * One of the two outputs at least. */
+int vfm_pca_colours(const double *y, const uint8_t *zero_rows, int64_t n, int k, const double *min, const double *max,
+                    float *values_out, uint8_t *rgb_out, vfm_stream_t stream);
+/* The colour gate of RN:696-702: for each of the m colours gate_colours[m x 3] (fp64) the rows of colours[n x 3] (uint8) with
+ * (dr*dr + dg*dg) + db*db < radius * radius in fp64, ascending, in idx_out[c * n ...]; counts_out[c] says how many.  idx_out is
+ * m x n int64; entries behind a colour's count are not written. */
+int vfm_colour_gate(const uint8_t *colours, int64_t n, const double *gate_colours, int m, double radius, int64_t *idx_out,
+                    int64_t *counts_out, vfm_stream_t stream);
+
 /* ------------------------------------------------------------------ DINOv2 ViT-S/14 (row A1) */
 
 /* self.model.model(img) of IF:101 incl. the transform of IF:67-77: bilinear resize (antialias

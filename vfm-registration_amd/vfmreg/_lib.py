@@ -113,6 +113,12 @@ SIGNATURES = {
     "vfm_mreach_mst_workspace_bytes": (C.c_size_t, [c_i64]),
     "vfm_mreach_mst": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_hdbscan_labels_host": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp]),
+    "vfm_pca_moments_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "vfm_pca_moments": (C.c_int, [c_vp, C.c_int, c_i64, C.c_int, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_pca_project_workspace_bytes": (C.c_size_t, []),
+    "vfm_pca_project": (C.c_int, [c_vp, C.c_int, c_i64, C.c_int, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_pca_colours": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vfm_colour_gate": (C.c_int, [c_vp, c_i64, c_vp, C.c_int, C.c_double, c_vp, c_vp, c_vp]),
     "vfm_vit_weights_bytes": (C.c_size_t, [C.POINTER(VitConfig)]),
     "vfm_vit_weights_layout": (C.c_int, [C.POINTER(VitConfig), C.POINTER(c_i64), C.POINTER(c_i64), C.c_int]),
     "vfm_vit_workspace_bytes": (C.c_size_t, [C.POINTER(VitConfig), C.c_int]),

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import h5lite
 from .registration import RegistrationNode
-from .utils import transform_pcl
+from .utils import TREE_COLOURS, filter_map_semantic, transform_pcl
 from .voxelization import voxel_down_sample
 
 SUCCESS_THRESHOLDS = [(.3, 15), (.6, 1.5), (2, 5)]  # (RTE m, RRE deg): PointDSC, GCL, D3Feat/SpinNet (RN:973-977)
@@ -167,7 +167,8 @@ class Evaluation:
 
 def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = None,
                    evaluation: Optional[Evaluation] = None, run_icp: bool = True, icp_ground_truth: bool = False,
-                   icp_baseline: bool = False, baselines=()) -> Evaluation:
+                   icp_baseline: bool = False, baselines=(), cluster_removal_prob: float = 0.0, remove_classes=None,
+                   pca=None) -> Evaluation:
     """The VFM + RANSAC (+ ICP) branch of make_step for one scene (RN:587-589, 593, 860-882, 943-951):
     every scan is registered against the accumulated map with the identity as initial guess and
     compared with its ground-truth pose.  ``icp_ground_truth``: that pose is the stored one refined by ICP against the map, as the
@@ -175,13 +176,27 @@ def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = No
     table.  Both are off by default (the stored pose, no ``icp`` row).  ``baselines`` (default ``()``): the baseline descriptors of
     RN:867-874 to run before ``vfm`` -- ``("fpfh",)`` adds the rows ``fpfh_ransac`` and, with ``run_icp``, ``fpfh_ransac_icp``; the node
     must have been created with the same ``baseline_methods``.  The map's baseline features are computed at the first scan of the
-    scene and kept for the others (RN:876-877)."""
+    scene and kept for the others (RN:876-877).
+
+    ``cluster_removal_prob`` (default 0.0: nothing changes): above 0 the seasonal-change experiment of RN:684-792 runs in front of every
+    scan's registration -- ``utils.filter_map_semantic`` on the scene's map with ``remove_classes`` (default ``[utils.TREE_COLOURS]``),
+    this chance and one ``np.random.RandomState(42)`` per scene shared by its scans (RN:584); the scan is registered against the
+    filtered map, the map's baseline features are dropped at every scan (RN:876-877) and ``points_in_map`` records the filtered size
+    (RN:792).  ``pca``: what has ``run_pca`` (an ``ImageFeatureGenerator`` or a ``pca.DescriptorPCA``, e.g. one whose ``fit_pca[3]`` holds
+    the reference's fit); default a fresh ``pca.DescriptorPCA``, fitted on the first scan's map."""
     node = node or RegistrationNode(cache_map=True, baseline_methods=tuple(baselines))   # local_map below is built here and never edited: one map per scene (RN:556-589)
     ev = evaluation or Evaluation()
     n_desc = scene["map_point_clouds"][0].shape[1] - 3
     local_map = build_local_map(scene["map_poses"], scene["map_point_clouds"], n_descriptors=n_desc)
     # the 3-D map both ICP calls register against: built once per scene and kept with the handle (the reference rebuilds it per call)
     icp_map = node.set_map(np.ascontiguousarray(local_map[:, :3])) if (icp_ground_truth or icp_baseline) else None
+    filtering = cluster_removal_prob > 0                                             # RN:684
+    if filtering:
+        from .pca import DescriptorPCA
+        pca = pca if pca is not None else DescriptorPCA()
+        remove_classes = [TREE_COLOURS] if remove_classes is None else remove_classes
+        rng_cluster_removal = np.random.RandomState(seed=42)                         # RN:584
+        scene_local_map = local_map
     for i, (gt_pose, point_cloud) in enumerate(zip(scene["scene_poses"], scene["scene_point_clouds"])):
         point_cloud = voxel_down_sample(point_cloud, .1).astype(point_cloud.dtype)   # RN:593
         if icp_ground_truth:
@@ -189,7 +204,10 @@ def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = No
         initial_pose = np.eye(4)                                                     # RN:858
         point_cloud = transform_pcl(point_cloud, initial_pose)                       # RN:863
         results = {}
-        if i == 0:
+        if filtering:                                                                # RN:693-792, from the whole map at every scan (RN:673)
+            local_map, _, _ = filter_map_semantic(scene_local_map, pca, remove_classes, cluster_removal_prob, rng_cluster_removal)
+            node.invalidate_map()                                                    # (the kept map is another one at every scan)
+        if i == 0 or filtering:
             node.clear_map_descriptors()                                             # RN:876-877
         for method in baselines:                                                     # RN:867-883, in the reference's order
             results[f"{method}_ransac"], results[f"{method}_ransac_icp"] = node.ransac_registration(local_map, point_cloud, method, run_icp)

@@ -21,11 +21,12 @@ import torch
 
 from . import ops
 from . import vit as V
+from .pca import DescriptorPCA, normalised
 
 
 class ImageFeatureGenerator:
     def __init__(self, foundation_model: str, use_featup: bool = True, weights: Optional[Dict[str, np.ndarray]] = None,
-                 device="cuda"):
+                 device="cuda", fit_pca_file=None):
         self.foundation_model_name = foundation_model
         self.use_featup = use_featup
         self.device = device
@@ -52,6 +53,7 @@ class ImageFeatureGenerator:
         self.feature_size = weights["patch_embed.proj.weight"].shape[0]
         self._models: Dict[tuple, V.ViTS14] = {}
         self.image_shape = (-1, -1)
+        self._pca = DescriptorPCA(fit_pca_file)   # image_features.py:58-65; no file by default: nothing is read or written
 
     def create_transform_(self, img_h, img_w) -> None:  # image_features.py:67-77
         scale = (self.patch_size * self.patch_h) / img_h
@@ -95,3 +97,41 @@ class ImageFeatureGenerator:
                 cache_file.parent.mkdir(parents=True, exist_ok=True)
                 np.save(cache_file, features)
         return features
+
+    # ------------------------------------------------------------------------------------------ PCA (image_features.py:119-192)
+    @property
+    def fit_pca(self) -> dict:
+        """``fit_pca[n_components]``: the fit ``run_pca`` / ``get_image_features_pca`` made, or one put there -- anything with
+        ``mean_`` and ``components_``, e.g. an entry of the reference's ``pca_fit.pkl`` (vfmreg/pca.py)."""
+        return self._pca.fit_pca
+
+    def run_pca(self, features, refit_pca: bool = False, n_components: int = 3):
+        """image_features.py:162-192 on csrc/pca.hip: the fit is kept per ``n_components`` and made only once (after
+        ``refit_pca=True`` the entry stays None and every later call fits again, IF:170-178); uint8 RGB for three components, black for
+        rows without features, float32 otherwise."""
+        return self._pca.run_pca(features, refit_pca=refit_pca, n_components=n_components)
+
+    def _upsample(self, grid: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """F.interpolate(bilinear, align_corners=False) of a [gh, gw, C] fp32 grid to [H, W, C] by the gather kernel."""
+        vv, uu = torch.meshgrid(torch.arange(H, dtype=torch.int32, device=self.device),
+                                torch.arange(W, dtype=torch.int32, device=self.device), indexing="ij")
+        k = H * W
+        out = torch.zeros((k, grid.shape[-1]), dtype=torch.float32, device=self.device)
+        filled = torch.zeros(k, dtype=torch.uint8, device=self.device)
+        ops.gather_bilinear(grid.contiguous(), H, W, 0, None, uu.reshape(-1).contiguous(), vv.reshape(-1).contiguous(),
+                            torch.arange(k, dtype=torch.int64, device=self.device), None, out, filled)
+        return out.reshape(H, W, -1)
+
+    def get_image_features_pca(self, image, upsample: bool = False, n_components: int = 3):
+        """image_features.py:119-160: ``(features, pca_features)`` of the 16 x pw patch grid; the PCA is fitted on the first image and
+        kept.  With ``upsample`` both go through the bilinear upsample to H x W before the ``* 255`` (IF:143-158).  ``pca_features`` is
+        uint8 RGB for three components, float32 otherwise; unlike ``run_pca`` nothing is blacked out."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        H, W = image.shape[:2]
+        grid = self.patch_features_device(torch.from_numpy(image).to(self.device).unsqueeze(0))[0].contiguous()
+        pca_features = normalised(grid, self._pca.fit_once(grid, n_components))
+        if upsample:
+            grid, pca_features = self._upsample(grid, H, W), self._upsample(pca_features, H, W)
+        if n_components == 3:
+            pca_features = (pca_features * 255.0).to(torch.uint8)   # truncates, as .astype(np.uint8) does
+        return grid.cpu().numpy(), pca_features.cpu().numpy()

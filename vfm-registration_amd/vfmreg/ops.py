@@ -699,3 +699,90 @@ def hdbscan_labels_host(lo, hi, w2, min_cluster_size: int):
     _lib.check(_lib.load().vfm_hdbscan_labels_host(lo.ctypes.data, hi.ctypes.data, w2.ctypes.data, len(lo) + 1, int(min_cluster_size),
                                                    labels.ctypes.data), "hdbscan_labels_host")
     return labels
+
+
+# ------------------------------------------------------------------------------------- descriptor PCA and the colour gate (csrc/pca.hip)
+PCA_MAX_D = 768
+PCA_MAX_K = 8
+ROWS_F32, ROWS_F16 = 0, 1      # VFM_ROWS_F32 / VFM_ROWS_F16
+
+
+def _pca_rows(x: torch.Tensor) -> int:
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("x: expected a tensor on the ROCm device (no CPU path exists)")
+    if x.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"x: expected float32 or float16 rows, got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("x: must be a contiguous n x d matrix")
+    return ROWS_F16 if x.dtype == torch.float16 else ROWS_F32
+
+
+def pca_moments(x: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vfm_pca_moments: (mean fp64[d], scatter fp64[d, d]) of the rows x (n x d, float32 or float16): the column means and
+    ``sum_n (x_n - mean)(x_n - mean)^T`` on the fp64 matrix cores, exactly symmetric, the same bits on every run.  No read-back."""
+    dtype = _pca_rows(x)
+    n, d = x.shape
+    lib = _lib.load()
+    mean = torch.empty(d, dtype=torch.float64, device=x.device)
+    scatter = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    need = lib.vfm_pca_moments_workspace_bytes(d)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, x.device)
+    _lib.check(lib.vfm_pca_moments(x.data_ptr(), dtype, n, d, mean.data_ptr(), scatter.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "pca_moments")
+    return mean, scatter
+
+
+def pca_project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor, ws: Optional[torch.Tensor] = None):
+    """vfm_pca_project: (y fp64[n, k], zero_rows uint8[n], min fp64[k], max fp64[k]) for mean fp64[d] and components fp64[k, d]:
+    ``y = (x - mean) . components^T`` in the order of addition DESIGN §7.6 fixes, the rows whose features are all zero, and the
+    extremes of every component over all rows.  No read-back."""
+    dtype = _pca_rows(x)
+    n, d = x.shape
+    _chk(mean, torch.float64, "mean")
+    _chk(components, torch.float64, "components")
+    if mean.shape != (d,) or components.dim() != 2 or components.shape[1] != d:
+        raise ValueError(f"expected mean [{d}] and components [k, {d}], got {tuple(mean.shape)} and {tuple(components.shape)}")
+    k = components.shape[0]
+    lib = _lib.load()
+    dev = x.device
+    y = torch.empty((n, k), dtype=torch.float64, device=dev)
+    zero = torch.empty(n, dtype=torch.uint8, device=dev)
+    lo = torch.empty(k, dtype=torch.float64, device=dev)
+    hi = torch.empty(k, dtype=torch.float64, device=dev)
+    need = lib.vfm_pca_project_workspace_bytes()
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    _lib.check(lib.vfm_pca_project(x.data_ptr(), dtype, n, d, mean.data_ptr(), components.data_ptr(), k, y.data_ptr(), zero.data_ptr(),
+                                   lo.data_ptr(), hi.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "pca_project")
+    return y, zero, lo, hi
+
+
+def pca_colours(y: torch.Tensor, zero_rows: Optional[torch.Tensor], lo: torch.Tensor, hi: torch.Tensor, rgb: bool) -> torch.Tensor:
+    """vfm_pca_colours: ``(y - min) / (max - min)`` as float32 [n, k], or with ``rgb`` (k == 3) as the uint8 colours of
+    image_features.py:184-190: times 255.0, truncated, black where ``zero_rows`` is set."""
+    _chk(y, torch.float64, "y")
+    _chk(lo, torch.float64, "min")
+    _chk(hi, torch.float64, "max")
+    n, k = y.shape
+    if rgb:
+        _chk(zero_rows, torch.uint8, "zero_rows")
+    out = torch.empty((n, k), dtype=torch.uint8 if rgb else torch.float32, device=y.device)
+    _lib.check(_lib.load().vfm_pca_colours(y.data_ptr(), _ptr(zero_rows), n, k, lo.data_ptr(), hi.data_ptr(), None if rgb else out.data_ptr(),
+                                           out.data_ptr() if rgb else None, _stream()), "pca_colours")
+    return out
+
+
+def colour_gate(colours: torch.Tensor, gate_colours: torch.Tensor, radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vfm_colour_gate: (idx int64[m, n], counts int64[m]) -- per colour of ``gate_colours`` (fp64 [m, 3]) the rows of ``colours``
+    (uint8 [n, 3]) nearer than ``radius``, ascending, in the first ``counts[c]`` entries of ``idx[c]``.  No read-back."""
+    _chk(colours, torch.uint8, "colours")
+    _chk(gate_colours, torch.float64, "gate_colours")
+    if colours.dim() != 2 or colours.shape[1] != 3 or gate_colours.dim() != 2 or gate_colours.shape[1] != 3:
+        raise ValueError("expected colours [n, 3] and gate_colours [m, 3]")
+    n, m = colours.shape[0], gate_colours.shape[0]
+    idx = torch.empty((m, n), dtype=torch.int64, device=colours.device)
+    counts = torch.empty(m, dtype=torch.int64, device=colours.device)
+    _lib.check(_lib.load().vfm_colour_gate(colours.data_ptr(), n, gate_colours.data_ptr(), m, float(radius), idx.data_ptr(), counts.data_ptr(),
+                                           _stream()), "colour_gate")
+    return idx, counts

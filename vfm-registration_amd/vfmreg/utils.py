@@ -1,6 +1,7 @@
 """Mirror of the hot-path helpers of vfm_reg.utils: ``transform_pcl`` (vfm_reg/utils.py:47-54) and ``FaissKNeighbors``
-(vfm_reg/utils.py:19-44) with the map filter that uses it (registration_node.py:704-778: ``grow_deletion_set``, ``remove_clusters``
-and both around the clustering in ``filter_map_clusters``)."""
+(vfm_reg/utils.py:19-44) with the map filter that uses it (registration_node.py:684-792: the colour gate ``colour_gate``,
+``grow_deletion_set``, ``remove_clusters``, both around the clustering in ``filter_map_clusters``, and the whole of it behind
+``run_pca`` in ``filter_map_semantic``)."""
 from __future__ import annotations
 
 import math
@@ -150,11 +151,50 @@ def filter_map_clusters(local_map_xyz: np.ndarray, del_idx: np.ndarray, remove_c
                         min_samples: int = 25):
     """registration_node.py:704-778 in one call: ``grow_deletion_set``, then ``HDBSCAN(100, 25)`` on the grown set's float32
     coordinates (vfmreg.clustering: exact, on the GPU), then ``remove_clusters``.  Starts from ``del_idx`` as ``grow_deletion_set``
-    does: the colour gate in front (RN:694-702) is a choice of colours on a projection with a sign-ambiguous SVD and stays with the
-    caller.  Returns ``(del_idx, keep_idx)`` as RN:777-778 leave them."""
+    does: the colour gate in front (RN:694-702) is ``colour_gate``, and ``filter_map_semantic`` runs both.  Returns
+    ``(del_idx, keep_idx)`` as RN:777-778 leave them."""
     from .clustering import HDBSCAN
     xyz = np.asarray(local_map_xyz)[:, :3]
     grown, _ = grow_deletion_set(xyz, del_idx)
     labels = HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples).fit_predict(xyz[grown].astype(np.float32))
     removed, _ = remove_clusters(grown, labels, remove_chance, rng)
     return removed, _rows_without(xyz.shape[0], removed)
+
+
+# The "tree (broadleaf and coniferous)" class of registration_node.py:685-688: two colours of the reference's PCA image of its maps.
+# They mean something only under the reference's own fit -- the arrays of its ``pca_fit.pkl`` put into ``fit_pca[3]`` (vfmreg/pca.py):
+# a fit made here has other axes and, by its sign rule, possibly other signs, and its colours of a tree are whatever that fit gives.
+TREE_COLOURS = np.array([[217, 60, 165], [118, 105, 57]], dtype=np.float32)
+
+
+def colour_gate(colours, remove_class, radius: float = 50.) -> np.ndarray:
+    """The colour gate of registration_node.py:696-702: for every colour of ``remove_class`` ([m, 3]) the rows of ``colours`` (uint8
+    [n, 3], numpy or a device tensor) with ``norm(row - colour) < radius``, ascending, concatenated in the colours' order -- a row near
+    two colours appears twice.  On the GPU (csrc/pca.hip): the squared distance in fp64 against ``radius * radius``, which for
+    integer-valued colours decides exactly as the reference's float32 ``norm < 50`` does.  Returns int64 numpy."""
+    t = colours if isinstance(colours, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(colours))
+    if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"colours: expected uint8 [n, 3], got {t.dtype} {tuple(t.shape)}")
+    gate = np.ascontiguousarray(np.asarray(remove_class, dtype=np.float64).reshape(-1, 3))
+    if t.shape[0] == 0 or gate.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    t = t.cuda().contiguous()
+    idx, counts = ops.colour_gate(t, torch.from_numpy(gate).cuda(), float(radius))
+    counts = counts.cpu().numpy()
+    return np.concatenate([idx[c, :int(counts[c])].cpu().numpy() for c in range(len(counts))])
+
+
+def filter_map_semantic(local_map: np.ndarray, pca, remove_classes, remove_chance: float, rng):
+    """registration_node.py:693-792 in one call.  ``local_map`` is N x (3 + C); ``pca`` has ``run_pca`` (an ``ImageFeatureGenerator``, a
+    ``pca.DescriptorPCA``).  The map's descriptors get their RGB colours (RN:694); then, per class of ``remove_classes`` (each [m, 3]
+    colours, e.g. ``[TREE_COLOURS]``), ``colour_gate`` picks the candidates, ``filter_map_clusters`` decides which of them go, and the
+    map and its colours are cut down before the next class (RN:790-791).  ``rng`` is the coin's ``np.random.RandomState`` (RN:584).
+    Returns ``(local_map[keep_idx], local_map_pca[keep_idx], keep_idx)``, ``keep_idx`` being rows of the map given."""
+    local_map = np.asarray(local_map)
+    local_map_pca = pca.run_pca(local_map[:, 3:], n_components=3)
+    keep_idx = np.arange(local_map.shape[0])
+    for remove_class in remove_classes:
+        del_idx = colour_gate(local_map_pca, remove_class)
+        _, keep = filter_map_clusters(local_map[:, :3], del_idx, remove_chance, rng)
+        local_map, local_map_pca, keep_idx = local_map[keep], local_map_pca[keep], keep_idx[keep]
+    return local_map, local_map_pca, keep_idx
