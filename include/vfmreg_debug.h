@@ -11,7 +11,7 @@
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
- *   - vfm_debug_search_plan  reads the calling thread's vfm_config and nothing else; host memory only.
+ *   - vfm_debug_search_plan / vfm_debug_prepare_plan  read the calling thread's vfm_config and nothing else; host memory only.
  *   - vfm_debug_l2_narrow_slices  host arithmetic only; vfm_debug_l2_narrow_evals  reads a workspace's counters and synchronises the device.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
@@ -51,6 +51,31 @@ int vfm_debug_coarse_kernel_names(char *buf_host, int cap);
  *     finish=<the kernels of the finish stage in launch order, separated by ','>
  * A combination the search refuses fails here with the same error.  Host memory only: no device is touched. */
 int vfm_debug_search_plan(int records, int d, int64_t n, int64_t m, int gated, char *buf_host, int cap);
+
+/* tests / tools: what a preparation would do under the calling thread's vfm_config, resolved by the same function the entry points use.
+ * entry: which of them is asked about -- the six exported ones, and the two forms the library uses inside vfm_match_mutual_l2 (one operand,
+ * the int8 image alone) and the ungated vfm_match_ip_top1; schedule / dtype1 / dtype2: as passed to the entry (0 where it takes none);
+ * rows2 = 0 for the one-operand entries; zero: the search workspace ranges of vfm_match_prepare2_gated_z ride along.  One line of text to
+ * buf_host[cap]:
+ *     images=<the images written, ','-separated: f16, i8, fp6 or fp6h (the first d / 2 columns only)>
+ *     kernels=<the launches in order, ','-separated, each instantiation spelled from its template arguments: prep_chunk_kernel<false,2,true,8>,
+ *              prep_once_kernel<384,half,persist,noi8>, ...>
+ *     grid=<workgroups of the first launch: group (one per 128 rows) | tile (per 32 rows) | cu (one per compute unit) | 2cu-stream (two per
+ *           compute unit of the stream's mask) | n>
+ *     zero=<none | inside (the preparation kernel clears the ranges) | behind (prep_zero_kernel does)>
+ * A combination the entry refuses fails here with the same error.  Host memory only: no device is touched. */
+enum vfm_debug_prepare_entry {
+    VFM_PREP_ENTRY_PREPARE = 0,   /* vfm_match_prepare */
+    VFM_PREP_ENTRY_PREPARE2,      /* vfm_match_prepare2 */
+    VFM_PREP_ENTRY_GATED,         /* vfm_match_prepare2_gated (and the gated vfm_match_ip_top1_gated) */
+    VFM_PREP_ENTRY_GATED_P,       /* vfm_match_prepare2_gated_p */
+    VFM_PREP_ENTRY_GATED_Z,       /* vfm_match_prepare2_gated_z */
+    VFM_PREP_ENTRY_GATED_T,       /* vfm_match_prepare2_gated_t */
+    VFM_PREP_ENTRY_PERM,          /* inside vfm_match_mutual_l2 */
+    VFM_PREP_ENTRY_ONESHOT        /* inside vfm_match_ip_top1 */
+};
+int vfm_debug_prepare_plan(int entry, int schedule, int d, int64_t rows1, int dtype1, int64_t rows2, int dtype2, int zero, char *buf_host,
+                           int cap);
 
 /* counters of the last FAST search that used workspace `ws` (candidate histogram, refined / fallback queries;
  * see csrc/match_finish.hip).  out64_host: HOST int32[64].  Synchronises the device. */

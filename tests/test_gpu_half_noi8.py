@@ -15,6 +15,7 @@ from oracle import oracle as orc  # noqa: E402
 from tests.guarded import GuardedBuffer  # noqa: E402
 from vfmreg import _lib, synth  # noqa: E402
 
+from .prepared_layout import _al, prepared_layout  # noqa: E402
 from .test_gpu_int8 import _gate_contract  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -26,30 +27,6 @@ NO_I8 = 0x200              # VFM_RECORDS_NO_I8
 GATE = float(np.nextafter(np.float32(0.8), np.float32(-np.inf)))
 N = 2100
 SHAPES = [(d, N, m) for d in (256, 384) for m in (1000, 4096)]   # m = 1000: a padded last chunk
-
-
-def _al(x, a=256):
-    return (x + a - 1) // a * a
-
-
-def prepared_layout(rows, d):
-    """{region: (offset, bytes)} of a prepared operand -- carve_prepared (csrc/match_internal.h), d = 256 / 384"""
-    rp = _al(rows)
-    ks = d // 64
-    tile6 = 512 + ks * 1536 + (512 if ks > 8 else 0)
-    sizes = [("inv", 4 * rp), ("tiles", rp // 32 * (d // 16) * 64 * 16), ("err", 4 * rp), ("gstep", 4 * rp // 128), ("gerr", 4 * rp // 128),
-             ("tiles8", rp // 32 * (d // 32) * 64 * 16), ("tiles8h", rp // 32 * (d // 64) * 64 * 16), ("rest", 4 * rp), ("grest", 4 * rp // 128),
-             ("tiles6", rp // 32 * tile6), ("err6", 4 * rp), ("gerr6", 4 * rp // 128), ("gstep6", 4 * rp // 128), ("err6h", 4 * rp),
-             ("gerr6h", 4 * rp // 128)]
-    if rp <= 131072:
-        sizes.append(("rows8", rp * d))
-    out, off = {}, 0
-    for name, nbytes in sizes:
-        off = _al(off)
-        out[name] = (off, nbytes)
-        off += nbytes
-    out["_end"] = (_al(off), 0)
-    return out
 
 
 KEPT = ("inv", "tiles6", "err6h", "gerr6h", "err6", "gerr6", "gstep6", "rest", "grest")

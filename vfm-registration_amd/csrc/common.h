@@ -1,6 +1,8 @@
 // common.h -- shared host-side helpers for the libvfmreg_hip.so translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -37,6 +39,19 @@ int vfm_fail(int code, const char *fmt, ...);
         const int rc__ = (call);         \
         if (rc__ != VFM_OK) return rc__; \
     } while (0)
+
+// compute units of the current device, asked for once per device (256 where the runtime cannot say)
+static inline int vfm_compute_units() {
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int n = cus[dev & 63].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev & 63].store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
 
 static inline size_t vfm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

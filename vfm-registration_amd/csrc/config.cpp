@@ -28,7 +28,7 @@ const Field k_fields[] = {
     {"coarse_qsets", &VfmConfig::coarse_qsets},      {"seed_units", &VfmConfig::seed_units},
     {"select_variant", &VfmConfig::select_variant},  {"mx6_t4", &VfmConfig::mx6_t4},
     {"mx6_tune", &VfmConfig::mx6_tune},
-    {"mx6_ns3", &VfmConfig::mx6_ns3},                {"prep_form", &VfmConfig::prep_stream},
+    {"mx6_ns3", &VfmConfig::mx6_ns3},                {"prep_form", &VfmConfig::prep_form},
     {"finish_short", &VfmConfig::finish_short},      {"rescan_rows", &VfmConfig::rescan_rows},
     {"half_noi8", &VfmConfig::half_noi8},            {"rescore_block", &VfmConfig::rescore_block},
     {"vit_preprocess_patch", &VfmConfig::vit_preprocess_patch}, {"vit_xcd", &VfmConfig::vit_xcd},
@@ -47,7 +47,7 @@ const Field k_fields[] = {
 void set_coarse_variant(VfmConfig& c, int v) {
     if (v == 60 || v == 61) { c.rescan_rows = v == 61 ? 1 : 0; return; }
     if (v == 50 || v == 51) { c.finish_short = v == 51 ? 1 : 0; return; }
-    if (v >= 40 && v <= 44) { c.prep_stream = v == 44 ? 4 : v == 43 ? 3 : v == 41 ? 1 : 0; return; }
+    if (v >= 40 && v <= 44) { c.prep_form = v == 44 ? 4 : v == 43 ? 3 : v == 41 ? 1 : 0; return; }
     if (v == 32 || v == 33) { c.mx6_ns3 = v == 33 ? 1 : 0; return; }
     if (v == 30 || v == 31) { c.mx6_t4 = v == 30 ? 1 : 0; return; }
     c.seed_units = v == 7 ? 0 : 1;

@@ -13,7 +13,7 @@ struct VfmConfig {
     int select_variant = 0;    // "coarse_variant" 20 / 21: general select kernel / no chunk-major rescan
     int mx6_t4 = 1;            // "coarse_variant" 30 / 31: fused fp6 half-width kernel with one (default) / two chunks per barrier
     int mx6_ns3 = 1;           // "coarse_variant" 32 / 33: ... with two / three (default) query tiles per wave at d = 384
-    int prep_stream = 3;       // "coarse_variant" 40, 41, 43, 44: fp6 operand preparation by prep_chunk_kernel (0) / prep_stream_kernel (1) / prep_once_kernel (3, default) /
+    int prep_form = 3;         // "coarse_variant" 40, 41, 43, 44: fp6 operand preparation by prep_chunk_kernel (0) / prep_stream_kernel (1) / prep_once_kernel (3, default) /
                                // prep_once_kernel as a persistent grid, the next group's loads under a group's second pass (4)
     int finish_short = 0;      // "coarse_variant" 50 / 51: chunk-major rescan as long-lived (default) / short workgroups
     int half_noi8 = 1;         // 1 (default): callers that follow the policy (vfmreg/pipeline.py) run VFM_RECORDS_MX6_HALF_FUSED without the int8 image

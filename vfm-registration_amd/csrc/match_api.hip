@@ -183,47 +183,29 @@ using namespace vfmm;
 
 VFM_EXPORT size_t vfm_match_prepared_bytes(int64_t rows, int d) { return carve_prepared(nullptr, rows, d).bytes; }
 
+// The preparation entries: pointer (and workspace size) checks here; every other refusal, and what is launched, is resolve_prepare's.
 VFM_EXPORT int vfm_match_prepare(const float* x, int64_t rows, int d, void* prepared, vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x && prepared, "prepare: null pointer");
-    return do_prepare(x, rows, d, prepared, (hipStream_t)stream);
+    return do_prepare2(VFM_PREP_ENTRY_PREPARE, 0, x, rows, prepared, Rows(), 0, nullptr, d, (hipStream_t)stream);
 }
 
 VFM_EXPORT int vfm_match_prepare2(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2, void* prepared2,
                                   int d, vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
-    return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream);
+    return do_prepare2(VFM_PREP_ENTRY_PREPARE2, 0, x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream);
 }
 
+// (map, scan): where the gated search of x2 in x1 runs a quantised pass, the fp16 image is not written
 VFM_EXPORT int vfm_match_prepare2_gated(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2,
                                         void* prepared2, int d, vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
-    // (map, scan): where the gated search of x2 in x1 runs the int8 pass, the fp16 image is never read
-    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
-    return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16);
-}
-
-// VFM_PREPARE_NO_I8 (host-side part; do_prepare2 checks what depends on the policy): only beside the half-width fp6 image, d = 256 / 384
-static int check_no_i8(int schedule, int d) {
-    if (!(schedule & VFM_PREPARE_NO_I8)) return VFM_OK;
-    VFM_CHECK_ARG((schedule & VFM_PREPARE_MX6) && (schedule & VFM_PREPARE_MX6_HALF),
-                  "prepare2: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF (schedule %d)", schedule);
-    VFM_CHECK_ARG(d == 256 || d == 384, "prepare2: VFM_PREPARE_NO_I8 exists for d = 256 / 384, got %d", d);
-    return VFM_OK;
+    return do_prepare2(VFM_PREP_ENTRY_GATED, 0, x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream);
 }
 
 VFM_EXPORT int vfm_match_prepare2_gated_p(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2,
                                           void* prepared2, int d, int schedule, vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
-                  "prepare2: unknown schedule %d", schedule);
-    if (int rc = check_no_i8(schedule, d)) return rc;
-    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
-    return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule);
+    return do_prepare2(VFM_PREP_ENTRY_GATED_P, schedule, x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream);
 }
 
 // ... which also clears, on `stream`, what a coarse pass of n queries in m map rows wants zero in the search workspace `ws` -- the
@@ -233,32 +215,18 @@ VFM_EXPORT int vfm_match_prepare2_gated_p(const float* x1, int64_t rows1, void* 
 VFM_EXPORT int vfm_match_prepare2_gated_z(const float* x1, int64_t rows1, void* prepared1, const float* x2, int64_t rows2,
                                           void* prepared2, int d, int schedule, void* ws, size_t ws_bytes, int64_t n, int64_t m,
                                           vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2 && ws, "prepare2: null pointer");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
-                  "prepare2: unknown schedule %d", schedule);
-    if (int rc = check_no_i8(schedule, d)) return rc;
     VFM_CHECK_ARG(n > 0 && m > 0 && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "prepare2: bad search size (n=%lld m=%lld)", (long long)n, (long long)m);
     if (ws_bytes < carve_search(nullptr, n, m).bytes) return vfm_fail(VFM_EWORKSPACE, "prepare2: search workspace too small");
-    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
-    return do_prepare2(x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, want_f16, schedule, prep_zero(ws, n, m));
+    return do_prepare2(VFM_PREP_ENTRY_GATED_Z, schedule, x1, rows1, prepared1, x2, rows2, prepared2, d, (hipStream_t)stream, prep_zero(ws, n, m));
 }
 
 // the gated pair with the rows' storage type stated (VFM_ROWS_F32 / VFM_ROWS_F16): fp16 rows are widened to fp32 element by element as
 // they are loaded, everything else is the fp32 path
 VFM_EXPORT int vfm_match_prepare2_gated_t(const void* x1, int dtype1, int64_t rows1, void* prepared1, const void* x2, int dtype2,
                                           int64_t rows2, void* prepared2, int d, int schedule, vfm_stream_t stream) {
-    VFM_CHECK_ARG(rows1 > 0 && rows2 > 0 && d % 128 == 0 && d >= 128 && d <= 768, "prepare2: d must be in {128,256,384,512,640,768}");
     VFM_CHECK_ARG(x1 && x2 && prepared1 && prepared2, "prepare2: null pointer");
-    VFM_CHECK_ARG((dtype1 == VFM_ROWS_F32 || dtype1 == VFM_ROWS_F16) && (dtype2 == VFM_ROWS_F32 || dtype2 == VFM_ROWS_F16), "prepare2: unknown row type");
-    VFM_CHECK_ARG((schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) >= VFM_PREPARE_DEFAULT &&
-                      (schedule & ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8)) <= VFM_PREPARE_INTERLEAVED,
-                  "prepare2: unknown schedule %d", schedule);
-    VFM_CHECK_ARG(!(schedule & VFM_PREPARE_NO_I8), "prepare2: VFM_PREPARE_NO_I8 is for fp32 rows (vfm_match_prepare2_gated_p / _z)");
-    const bool want_f16 = !runs_quantised(VFM_RECORDS_BEST, d, rows2, rows1, true);
-    return do_prepare2(Rows(x1, dtype1 == VFM_ROWS_F16), rows1, prepared1, Rows(x2, dtype2 == VFM_ROWS_F16), rows2, prepared2, d,
-                       (hipStream_t)stream, want_f16, schedule);
+    return do_prepare2(VFM_PREP_ENTRY_GATED_T, schedule, Rows(x1, dtype1), rows1, prepared1, Rows(x2, dtype2), rows2, prepared2, d, (hipStream_t)stream);
 }
 
 VFM_EXPORT size_t vfm_match_search_workspace_bytes(int64_t n, int64_t m, int d) {
@@ -402,7 +370,7 @@ static int ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, 
     void* bprep = p + vfm_match_prepared_bytes(n, d);
     void* sws = p + vfm_match_prepared_bytes(n, d) + vfm_match_prepared_bytes(m, d);
     VFM_CHECK_ARG(m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "match: more than 2^31 rows");
-    int rc = do_prepare2(b, m, bprep, q, n, qprep, d, st, !runs_quantised(VFM_RECORDS_TOP2, d, n, m, gated));
+    int rc = do_prepare2(gated ? VFM_PREP_ENTRY_GATED : VFM_PREP_ENTRY_ONESHOT, 0, b, m, bprep, q, n, qprep, d, st);
     if (rc) return rc;
     // one-shot calls have no feedback loop: packed top-2 records, the robust kind (real lifted descriptors are duplicate-rich)
     rc = do_search_coarse(qprep, n, bprep, m, d, sws, st, false, true, gated, VFM_RECORDS_TOP2);
@@ -537,6 +505,24 @@ VFM_EXPORT int vfm_debug_coarse_kernel_names(char* buf_host, int cap) {
     std::string all;
     for (const std::string& s : names) all += (all.empty() ? "" : "\n") + s;
     return copy_out(all, buf_host, cap, "coarse_kernel_names");
+}
+
+// The plan of a preparation (match_internal.h, resolve_prepare) as one line of text; a refused combination fails as the entry would.
+VFM_EXPORT int vfm_debug_prepare_plan(int entry, int schedule, int d, int64_t rows1, int dtype1, int64_t rows2, int dtype2, int zero,
+                                      char* buf_host, int cap) {
+    PrepPlan plan;
+    VFM_TRY(resolve_prepare(plan, entry, schedule, d, rows1, dtype1, rows2, dtype2, zero != 0));
+    std::string line = "images=";
+    const char* const images[] = {plan.f16 ? "f16" : "", plan.i8 ? "i8" : "", plan.fp6_half ? "fp6h" : plan.fp6 ? "fp6" : ""};
+    for (const char* im : images)
+        if (*im) line += (line.back() == '=' ? "" : ",") + std::string(im);
+    line += " kernels=";
+    for (int i = 0; i < plan.nlaunches; ++i) line += (i ? "," : "") + std::string(prep_inst_name(plan.launches[i].inst));
+    const PrepLaunch& l = plan.launches[0];
+    static const char* const zero_at[] = {"none", "inside", "behind"};
+    line += " grid=" + (l.rule == PREP_GRID_ROWS ? std::string(l.n == TILE_ROWS ? "tile" : "group") : l.rule == PREP_GRID_CU ? std::string("cu") :
+                        l.rule == PREP_GRID_2CU_STREAM ? std::string("2cu-stream") : std::to_string(l.n)) + " zero=" + zero_at[plan.zero];
+    return copy_out(line, buf_host, cap, "prepare_plan");
 }
 
 // The plan of a search (match_internal.h, resolve_search) as one line of text; a refused combination fails as the search would.

@@ -581,14 +581,7 @@ int launch_coarse_mx6(CoarseArgs& a, int d, bool top2, bool half, bool fuse, hip
         // 0.370; 47 = 4.96 rounds 0.367; 19 slices = 2.004 rounds 0.445).  Near the count above, take the slice count whose last round is
         // (almost) full -- at most 4 above, 12 below; in the pipeline 56 against 60 is +1 % over 200 steps, even in the 20-step form.
         {
-            static std::atomic<int> ncu{0};
-            int cus = ncu.load(std::memory_order_relaxed);
-            if (cus == 0) {
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-                ncu.store(cus, std::memory_order_relaxed);
-            }
+            const int cus = vfm_compute_units();
             int best = s;
             double best_fill = 0.0;
             for (int t = (s + 4 < smax ? s + 4 : smax); t >= 1 && t >= s - 12; --t) {

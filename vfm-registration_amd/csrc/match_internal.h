@@ -3,6 +3,7 @@
 // host functions that cross translation units.  Kernels live in anonymous namespaces of the file that launches them.
 #pragma once
 #include "common.h"
+#include "../../include/vfmreg_debug.h"
 
 #include <type_traits>
 #include <vector>
@@ -759,9 +760,131 @@ inline PrepZero prep_zero(void* ws, int64_t n, int64_t m) {
     z.nb = (size_t)rows_padded(n) * sizeof(int) / 16;
     return z;
 }
-int do_prepare2(Rows x1, int64_t rows1, void* prepared1, Rows x2, int64_t rows2, void* prepared2, int d,
-                hipStream_t st, bool want_f16 = true, int grid_mode = 0 /* VFM_PREPARE_DEFAULT */, PrepZero zero = PrepZero{});
-int do_prepare(const float* x, int64_t rows, int d, void* prepared, hipStream_t st);
+// ---------------------------------------------------------------------------------------------
+// What a preparation does, resolved ONCE from what the caller passed and the calling thread's vfm_cfg(): the launcher (match_prep.hip,
+// do_prepare2 / do_prepare_perm) walks plan.launches and the read-back vfm_debug_prepare_plan prints them.  No HIP call in here: a
+// grid is a RULE, turned into a number at launch.
+//
+// Which kernels.  d = 128 has no int8 image: prep_rows_kernel (fp16 tiles).  Elsewhere prep_chunk_kernel holds a 128-row group in the
+// registers of 16 fat waves, one workgroup per compute unit: <true, 2> writes both images from one read (d <= 384; 144 KB of LDS),
+// <false, 2 | 3> the int8 image alone, the fp16 image then by prep_rows_kernel.  With the fp6 image (VFM_PREPARE_MX6) at d = 256 / 384
+// the form is vfm_cfg().prep_form ("coarse_variant" 40, 41, 43, 44; tools/ab_prep_r5.py, ab_prep_r6.py, DESIGN.md R6.2 and the section
+// on the persistent form): 3 (default since round 6) prep_once_kernel -- one read of fp32 rows, the fp16 copy of a wave's tile in
+// registers, two short workgroups per compute unit; 4 the same kernel as a persistent grid with the next group's loads under a group's
+// second pass; 1 prep_stream_kernel, built to run BESIDE a coarse workgroup of round 4 (332 of a SIMD's 512 registers, 90 KiB), every
+// row read twice; anything else, and fp16 rows under every form, prep_chunk_kernel<false, 2, true, 8>.  d = 512 / 768 get the fp6 image
+// by kernels of their own behind the int8 one; d = 128 / 640 have none and ignore the flag.
+// ---------------------------------------------------------------------------------------------
+enum PrepInst : unsigned char {   // one per kernel instantiation in match_prep.hip; prep_inst_name and launch_prepare's switch follow this order
+    PREP_ROWS, PREP_CHUNK_BOTH, PREP_CHUNK_2, PREP_CHUNK_3, PREP_CHUNK_MX6,
+    PREP_STREAM,                        // + 2 (d == 384) + half
+    PREP_ONCE = PREP_STREAM + 4,        // + 4 (d == 384) + 2 half + persist
+    PREP_ONCE_NOI8 = PREP_ONCE + 8,     // + 2 (d == 384) + persist
+    PREP_MX6_ROWS_16 = PREP_ONCE_NOI8 + 4, PREP_MX6_ROWS_32, PREP_MX6_GROUP, PREP_INST_COUNT
+};
+inline const char* prep_inst_name(int inst) {
+    static const char* const names[PREP_INST_COUNT] = {
+        "prep_rows_kernel", "prep_chunk_kernel<true,2>", "prep_chunk_kernel<false,2>", "prep_chunk_kernel<false,3>", "prep_chunk_kernel<false,2,true,8>",
+        "prep_stream_kernel<256,full>", "prep_stream_kernel<256,half>", "prep_stream_kernel<384,full>", "prep_stream_kernel<384,half>",
+        "prep_once_kernel<256,full,short>", "prep_once_kernel<256,full,persist>", "prep_once_kernel<256,half,short>", "prep_once_kernel<256,half,persist>",
+        "prep_once_kernel<384,full,short>", "prep_once_kernel<384,full,persist>", "prep_once_kernel<384,half,short>", "prep_once_kernel<384,half,persist>",
+        "prep_once_kernel<256,half,short,noi8>", "prep_once_kernel<256,half,persist,noi8>", "prep_once_kernel<384,half,short,noi8>",
+        "prep_once_kernel<384,half,persist,noi8>", "prep_mx6_rows_kernel<16>", "prep_mx6_rows_kernel<32>", "prep_mx6_group_kernel"};
+    return names[inst];
+}
+// workgroups of a launch: one per n padded rows of both operands (128: per group, 32: per tile); or, never more than the groups, one
+// per compute unit, two per compute unit of the stream's mask, or n
+enum PrepGridRule : unsigned char { PREP_GRID_ROWS, PREP_GRID_CU, PREP_GRID_2CU_STREAM, PREP_GRID_N };
+enum PrepZeroAt : unsigned char { PREP_ZERO_NONE, PREP_ZERO_INSIDE, PREP_ZERO_BEHIND };   // INSIDE: the one-read kernel clears the ranges; BEHIND: prep_zero_kernel
+struct PrepLaunch {
+    int inst;       // PrepInst
+    bool half6;     // PrepOut::mx6_half of the launch (the fp6 kernels under VFM_PREPARE_MX6_HALF)
+    int block, lds;
+    int rule, n;    // PrepGridRule and its n
+};
+struct PrepPlan {
+    bool f16 = false, i8 = false, fp6 = false, fp6_half = false;   // the images written (fp6_half: of the first d / 2 columns only)
+    PrepLaunch launches[4] = {};
+    int nlaunches = 0;
+    int zero = PREP_ZERO_NONE;
+};
+
+// entry: a VFM_PREP_ENTRY_* (include/vfmreg_debug.h); schedule, row types: as passed; rows2 = 0: no second operand; zero: search
+// workspace ranges ride along.  Every refusal of a preparation is made here, once.
+inline int resolve_prepare(PrepPlan& p, int entry, int schedule, int d, int64_t rows1, int dtype1, int64_t rows2, int dtype2, bool zero) {
+    p = PrepPlan{};
+    const bool single = entry == VFM_PREP_ENTRY_PREPARE || entry == VFM_PREP_ENTRY_PERM;
+    const bool gated = entry >= VFM_PREP_ENTRY_GATED && entry <= VFM_PREP_ENTRY_GATED_T;
+    const bool scheduled = entry >= VFM_PREP_ENTRY_GATED_P && entry <= VFM_PREP_ENTRY_GATED_T;
+    if (entry < VFM_PREP_ENTRY_PREPARE || entry > VFM_PREP_ENTRY_ONESHOT) return vfm_fail(VFM_EINVAL, "prepare: unknown entry %d", entry);
+    if (!(rows1 > 0 && (single ? rows2 == 0 : rows2 > 0) && d % 128 == 0 && d >= 128 && d <= 768))
+        return vfm_fail(VFM_EINVAL, "%s: d must be in {128,256,384,512,640,768}", entry == VFM_PREP_ENTRY_PREPARE ? "prepare" : "prepare2");
+    if (entry == VFM_PREP_ENTRY_PERM && !i8_capable(d)) return vfm_fail(VFM_EINVAL, "prepare(perm): no int8 image for d = %d", d);
+    VFM_CHECK_ARG((dtype1 == VFM_ROWS_F32 || dtype1 == VFM_ROWS_F16) && (dtype2 == VFM_ROWS_F32 || dtype2 == VFM_ROWS_F16) &&
+                      (entry == VFM_PREP_ENTRY_GATED_T || (dtype1 == VFM_ROWS_F32 && dtype2 == VFM_ROWS_F32)), "prepare2: unknown row type");
+    const int flags = VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF | VFM_PREPARE_NO_I8;
+    const int mode = schedule & ~flags;   // the low bits: the chunk kernel's grid and nothing else
+    VFM_CHECK_ARG(scheduled ? mode >= VFM_PREPARE_DEFAULT && mode <= VFM_PREPARE_INTERLEAVED : schedule == 0, "prepare2: unknown schedule %d", schedule);
+    const bool no_i8 = (schedule & VFM_PREPARE_NO_I8) != 0;
+    const bool half6 = (schedule & VFM_PREPARE_MX6_HALF) != 0;               // (implies VFM_PREPARE_MX6)
+    const bool mx6 = half6 || (schedule & VFM_PREPARE_MX6) != 0;
+    const bool any_f16 = dtype1 == VFM_ROWS_F16 || (rows2 > 0 && dtype2 == VFM_ROWS_F16);
+    const int form = vfm_cfg().prep_form;
+    const bool once = mx6 && mx6_width(d) && !any_f16 && (form == 3 || form == 4);
+    if (no_i8) {   // prep_once_kernel<., true, ., true> or nothing: no other form leaves the int8 image out
+        VFM_CHECK_ARG(entry != VFM_PREP_ENTRY_GATED_T, "prepare2: VFM_PREPARE_NO_I8 is for fp32 rows (vfm_match_prepare2_gated_p / _z)");
+        VFM_CHECK_ARG((schedule & VFM_PREPARE_MX6) && half6, "prepare2: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF (schedule %d)", schedule);
+        VFM_CHECK_ARG(mx6_width(d), "prepare2: VFM_PREPARE_NO_I8 exists for d = 256 / 384, got %d", d);
+    }
+    // (map, scan): where the search of x2 in x1 runs a quantised pass, the fp16 image is never read.  fp16 rows are widened on load by
+    // prep_chunk_kernel and prep_mx6_rows_kernel only: the int8 and fp6 images of the gated family
+    const bool want_f16 = entry == VFM_PREP_ENTRY_PERM ? false : (gated || entry == VFM_PREP_ENTRY_ONESHOT) ? !use_i8(d, rows2, rows1, gated) : true;
+    if (any_f16 && (want_f16 || !i8_capable(d)))
+        return vfm_fail(VFM_EINVAL, "prepare: fp16 rows are taken by the gated int8 / fp6 searches (d in {256 .. 768}, more queries than the fp16 pass' limit)");
+    if (no_i8 && !(once && rows2 > 0))
+        return vfm_fail(VFM_EINVAL, "prepare: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6_HALF, d = 256 / 384, fp32 rows of both operands and the "
+                                    "one-read preparation (prep_form 3 / 4)");
+    auto add = [&p](int inst, bool h6, int block, int lds, int rule, int n) { p.launches[p.nlaunches++] = PrepLaunch{inst, h6, block, lds, rule, n}; };
+    auto add_rows = [&] { add(PREP_ROWS, false, 256, d * 64, PREP_GRID_ROWS, TILE_ROWS); };
+    p.zero = !zero ? PREP_ZERO_NONE : once ? PREP_ZERO_INSIDE : PREP_ZERO_BEHIND;
+    p.f16 = want_f16 || !i8_capable(d);
+    if (!i8_capable(d)) {
+        add_rows();
+        return VFM_OK;
+    }
+    p.i8 = !no_i8;
+    p.fp6 = mx6 && mx6_half_width(d);
+    p.fp6_half = p.fp6 && half6;
+    // prep_chunk_kernel's grid: DEFAULT the "prep_grid" key, PERSISTENT one per compute unit, INTERLEAVED one per group
+    const int knob = mode == VFM_PREPARE_DEFAULT ? vfm_cfg().prep_grid : (mode == VFM_PREPARE_PERSISTENT ? 0 : -1);
+    const int crule = knob > 0 ? PREP_GRID_N : (knob < 0 ? PREP_GRID_ROWS : PREP_GRID_CU), cn = knob > 0 ? knob : I8_GROUP;
+    const int d384 = d == 384;
+    if (once) {   // the persistent form: "prep_grid" n > 0, or two workgroups per compute unit of the stream's mask
+        const int persist = form == 4, n = vfm_cfg().prep_grid;
+        add(no_i8 ? PREP_ONCE_NOI8 + 2 * d384 + persist : PREP_ONCE + 4 * d384 + 2 * half6 + persist, half6, 256, 0,
+            !persist ? PREP_GRID_ROWS : (n > 0 ? PREP_GRID_N : PREP_GRID_2CU_STREAM), persist && n > 0 ? n : I8_GROUP);
+    } else if (mx6 && mx6_width(d) && form == 1 && !any_f16) {
+        add(PREP_STREAM + 2 * d384 + half6, half6, 256, 0, PREP_GRID_ROWS, I8_GROUP);
+    } else if (mx6 && mx6_width(d)) {
+        add(PREP_CHUNK_MX6, half6, 512, I8_GROUP * (d * 3 + d / 8 + 16), crule, cn);
+    } else if (want_f16 && d <= 384) {
+        add(PREP_CHUNK_BOTH, false, 1024, I8_GROUP * d * 3, crule, cn);
+        return VFM_OK;
+    } else {
+        add(d <= 512 ? PREP_CHUNK_2 : PREP_CHUNK_3, false, 1024, I8_GROUP * d, crule, cn);
+    }
+    if (want_f16) add_rows();
+    if (p.fp6 && !mx6_width(d)) {   // d = 512, 768: 16 / 8 rows per workgroup, then the groups' maxima (four groups per workgroup)
+        add(d == 512 ? PREP_MX6_ROWS_16 : PREP_MX6_ROWS_32, half6, 256, (d == 512 ? 16 : 8) * d * 4, PREP_GRID_ROWS, d == 512 ? 16 : 8);
+        add(PREP_MX6_GROUP, half6, 256, 0, PREP_GRID_ROWS, 4 * I8_GROUP);
+    }
+    return VFM_OK;
+}
+
+// one or two operands (rows2 = 0: one) as `entry` with `schedule` prepares them; zero: ranges of a search workspace to clear on `st`
+// with the preparation (none by default)
+int do_prepare2(int entry, int schedule, Rows x1, int64_t rows1, void* prepared1, Rows x2, int64_t rows2, void* prepared2, int d,
+                hipStream_t st, PrepZero zero = PrepZero{});
 // int8 image alone of ONE operand whose row r is x[perm[r]] (perm == NULL: identity) -- the Euclidean search prepares its map
 // sorted by norm and the queries of its reverse direction gathered by the forward result
 int do_prepare_perm(const float* x, int64_t rows, const int* perm, int d, void* prepared, hipStream_t st);

@@ -1452,37 +1452,23 @@ inline PrepOut prep_out(const Prepared& p, const int* perm = nullptr, int mx6_ha
                    p.err6h, p.gerr6h, p.rows8, mx6_half};
 }
 
-// Workgroups of prep_chunk_kernel (vfm_debug_set_prep_grid): -1 (default) = one per 128-row group; 0 = one per compute unit,
-// each walking ceil(groups / grid) groups with the next group's rows read under the current group's quantisation and store
-// (the kernel's registers admit one workgroup per compute unit, so nothing else overlaps them); n > 0 = n workgroups.
-// Alone on the GPU the persistent form is the faster one (C2: 81 vs 109 us, 5.2 vs 3.9 TB/s); beside the coarse kernel of the
-// previous registration -- whose workgroups need a whole compute unit each -- the short workgroups interleave better
-// (791 vs 783 registrations/s over 300 steps, same box), and that is where the pipeline runs it.
-inline int prep_grid(int groups, int mode) {
-    static thread_local int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    const int knob = mode == VFM_PREPARE_DEFAULT ? vfm_cfg().prep_grid : (mode == VFM_PREPARE_PERSISTENT ? 0 : -1);
-    int g = knob > 0 ? knob : (knob < 0 ? groups : cus);
-    return g < groups ? g : groups;
-}
-
-// Workgroups of the persistent one-read form (prep_once_kernel<., ., true>): two per compute unit the stream may use -- what the
-// kernel's registers and LDS admit (__launch_bounds__(256, 2); 2 x 33 KB) --, or vfm_debug_set_prep_grid's n > 0.  The stream's
-// mask is asked for once per (thread, stream): a stale answer costs a badly sized grid, never a wrong result (static striding).
-inline int prep_persist_grid(int groups, hipStream_t st) {
-    static thread_local hipStream_t last_st = nullptr;
-    static thread_local int last_cus = 0;
-    const int knob = vfm_cfg().prep_grid;
-    int g = knob;
-    if (knob <= 0) {
+// Workgroups of a launch (PrepGridRule).  prep_chunk_kernel ("prep_grid": -1 (default) = one per 128-row group; 0 = one per compute
+// unit, each walking ceil(groups / grid) groups with the next group's rows read under the current group's quantisation and store -- the
+// kernel's registers admit one workgroup per compute unit, so nothing else overlaps them; n > 0 = n workgroups): alone on the GPU the
+// persistent form is the faster one (C2: 81 vs 109 us, 5.2 vs 3.9 TB/s); beside the coarse kernel of the previous registration -- whose
+// workgroups need a whole compute unit each -- the short workgroups interleave better (791 vs 783 registrations/s over 300 steps, same
+// box), and that is where the pipeline runs it.  The persistent one-read form (prep_once_kernel<., ., true>): two per compute unit the
+// stream may use -- what the kernel's registers and LDS admit (__launch_bounds__(256, 2); 2 x 33 KB) --, or "prep_grid" n > 0.  The
+// stream's mask is asked for once per (thread, stream): a stale answer costs a badly sized grid, never a wrong result (static striding).
+static unsigned prep_grid(const PrepLaunch& l, int64_t rows_pad, hipStream_t st) {
+    if (l.rule == PREP_GRID_ROWS) return (unsigned)((rows_pad + l.n - 1) / l.n);
+    int g = l.n;
+    if (l.rule == PREP_GRID_CU) g = vfm_compute_units();
+    if (l.rule == PREP_GRID_2CU_STREAM) {
+        static thread_local hipStream_t last_st = nullptr;
+        static thread_local int last_cus = 0;
         if (!last_cus || last_st != st) {
-            int cus = 0, dev = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+            int cus = vfm_compute_units();
             uint32_t mask[16] = {0};
             if (hipExtStreamGetCUMask(st, 16, mask) == hipSuccess) {
                 int bits = 0;
@@ -1496,164 +1482,86 @@ inline int prep_persist_grid(int groups, hipStream_t st) {
         }
         g = 2 * last_cus;
     }
-    return g < groups ? g : groups;
+    const int groups = (int)(rows_pad / I8_GROUP);
+    return (unsigned)(g < groups ? g : groups);
 }
 
-// one or two operands (x2 may be NULL) in one launch.  want_f16 = false: only the int8 image (d = 256, 384), for operands that
-// will meet in an int8 search (use_i8): a third of the bytes written, a third of the LDS.
-// zero: ranges of a search workspace to clear on `st` with the preparation (none by default) -- inside the preparation kernel where
-// that is prep_once_kernel, by prep_zero_kernel behind the others.
-int do_prepare2(Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows2, void* prepared2, int d,
-                hipStream_t st, bool want_f16, int grid_mode, PrepZero zero) {
-    bool zero_pending = zero.na + zero.nb != 0;   // (cleared where the preparation kernel takes the ranges along)
-    auto zero_behind = [&]() {
-        if (!zero_pending) return VFM_OK;
-        const size_t nz = zero.na + zero.nb;
-        hipLaunchKernelGGL(prep_zero_kernel, dim3((unsigned)((nz + 255) / 256 < 1024 ? (nz + 255) / 256 : 1024)), dim3(256), 0, st, zero);
-        VFM_CHECK_LAUNCH("prep_zero_kernel");
-        return VFM_OK;
-    };
-    // fp16 rows (VFM_ROWS_F16): the kernels that widen on load are prep_chunk_kernel and prep_mx6_rows_kernel -- the int8 and fp6
-    // images of the gated family; the fp16-tile image (ungated fp16 pass) and the streamed fp6 form read fp32 rows only
-    const bool any_f16 = x1r.f16 || (x2r.p && x2r.f16);
-    if (any_f16 && (want_f16 || !i8_capable(d)))
-        return vfm_fail(VFM_EINVAL, "prepare: fp16 rows are taken by the gated int8 / fp6 searches (d in {256 .. 768}, more queries than the fp16 pass' limit)");
-    const float* x1 = static_cast<const float*>(x1r.p);   // (read as fp32 only where !any_f16)
+// carve, resolve, walk the plan's launches: the one launcher of every preparation (perm: do_prepare_perm's gather of the first operand)
+static int launch_prepare(int entry, int schedule, Rows x1r, int64_t rows1, void* prepared1, Rows x2r, int64_t rows2, void* prepared2, int d,
+                          const int* perm, hipStream_t st, PrepZero zero) {
+    const size_t nz = zero.na + zero.nb;
+    PrepPlan plan;
+    static_assert(VFM_ROWS_F32 == 0 && VFM_ROWS_F16 == 1, "Rows::f16 carries the row type as passed");
+    VFM_TRY(resolve_prepare(plan, entry, schedule, d, rows1, x1r.f16, rows2, x2r.f16, nz != 0));
+    const Prepared p1 = carve_prepared(prepared1, rows1, d), p2 = rows2 ? carve_prepared(prepared2, rows2, d) : Prepared{};
+    const float* x1 = static_cast<const float*>(x1r.p);   // (the kernels that read fp32 only: the plan gives them no fp16 rows)
     const float* x2 = static_cast<const float*>(x2r.p);
-    const int h6 = (grid_mode & VFM_PREPARE_MX6_HALF) != 0 ? 1 : 0;   // the fp6 image of the first d / 2 columns only (implies VFM_PREPARE_MX6)
-    if (h6) grid_mode |= VFM_PREPARE_MX6;
-    // VFM_PREPARE_NO_I8: prep_once_kernel<., true, ., true> or nothing -- no other form leaves the int8 image out
-    const bool no_i8 = (grid_mode & VFM_PREPARE_NO_I8) != 0;
-    grid_mode &= ~VFM_PREPARE_NO_I8;
-    if (no_i8 && !(h6 && mx6_width(d) && !any_f16 && x2 && (vfm_cfg().prep_stream == 3 || vfm_cfg().prep_stream == 4)))
-        return vfm_fail(VFM_EINVAL, "prepare: VFM_PREPARE_NO_I8 needs VFM_PREPARE_MX6_HALF, d = 256 / 384, fp32 rows of both operands and the "
-                                    "one-read preparation (prep_form 3 / 4)");
-    const bool want_mx6 = (grid_mode & VFM_PREPARE_MX6) != 0 && mx6_width(d);              // int8 + fp6 image from one kernel
-    const bool want_mx6_wide = (grid_mode & VFM_PREPARE_MX6) != 0 && !want_mx6 && mx6_half_width(d);   // d = 512, 768: kernels of their own
-    grid_mode &= ~(VFM_PREPARE_MX6 | VFM_PREPARE_MX6_HALF);
-    Prepared p1 = carve_prepared(prepared1, rows1, d);
-    Prepared p2 = x2 ? carve_prepared(prepared2, rows2, d) : Prepared{};
-    const int t1 = (int)(rows_padded(rows1) / TILE_ROWS), t2 = x2 ? (int)(rows_padded(rows2) / TILE_ROWS) : 0;
-    if (i8_capable(d)) {  // int8 tiles + group data (+ fp16 tiles)
-        const int g1 = (int)(rows_padded(rows1) / I8_GROUP), g2 = x2 ? (int)(rows_padded(rows2) / I8_GROUP) : 0;
-        static unsigned long long attr_set = 0ull;  // one bit per device
-        if (!attr_done(attr_set)) {
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<true, 2>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 384 * 3));
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 2>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 512));
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 3>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 768));
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 2, true, 8>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * (384 * 3 + 384 / 8 + 16)));
-            attr_mark(attr_set);
-        }
-        const int groups = g1 + g2;
-        int pg = prep_grid(groups, grid_mode);
-        const dim3 grid((unsigned)pg), block(1024);
-        if (want_mx6) {   // int8 + fp6 images from one read of the rows; the fp16 image, if wanted, by its own kernel
-            // Which form (vfm_cfg().prep_stream, "coarse_variant" 40, 41, 43, 44).  Default since round 6: prep_once_kernel (3) -- one read of the
-            // rows, the fp16 copy of a wave's tile in registers, two short workgroups per compute unit; 4 is the same kernel as a persistent
-            // grid with the next group's loads under a group's second pass.  Both take d = 256 / 384 in fp32 rows; everything else -- and
-            // the older forms when asked for -- goes on as before: prep_stream_kernel (1) was built to run BESIDE a
-            // coarse workgroup of round 4 (332 of a SIMD's 512 registers, 90 KiB) and reads every row twice; prep_chunk_kernel (0) holds
-            // a group in the registers of 8 fat waves, one workgroup per compute unit.  Since round 5 nothing runs beside a d = 384 coarse
-            // workgroup (444 registers per SIMD), so a preparation form is judged by its own work: tools/ab_prep_r5.py, ab_prep_r6.py,
-            // DESIGN.md R6.2 and the section on the persistent form.
-            const bool stream_form = vfm_cfg().prep_stream == 1;
-            if ((vfm_cfg().prep_stream == 3 || vfm_cfg().prep_stream == 4) && (d == 384 || d == 256) && !any_f16) {
-                const bool persist = vfm_cfg().prep_stream == 4;
-                const dim3 sg((unsigned)(persist ? prep_persist_grid(groups, st) : groups)), sb(256);
-                const PrepOut po1 = prep_out(p1, nullptr, h6), po2 = prep_out(p2, nullptr, h6);
-#define VFM_PREP_ONCE(D_, H_, P_) hipLaunchKernelGGL((prep_once_kernel<D_, H_, P_>), sg, sb, 0, st, x1, rows1, po1, g1, x2, rows2, po2, groups, zero)
-                if (no_i8) {
-#define VFM_PREP_ONCE_NOI8(D_, P_) hipLaunchKernelGGL((prep_once_kernel<D_, true, P_, true>), sg, sb, 0, st, x1, rows1, po1, g1, x2, rows2, po2, groups, zero)
-                    if (d == 384) { if (persist) VFM_PREP_ONCE_NOI8(384, true); else VFM_PREP_ONCE_NOI8(384, false); }
-                    else          { if (persist) VFM_PREP_ONCE_NOI8(256, true); else VFM_PREP_ONCE_NOI8(256, false); }
-#undef VFM_PREP_ONCE_NOI8
-                } else if (d == 384) {
-                    if (h6) { if (persist) VFM_PREP_ONCE(384, true, true); else VFM_PREP_ONCE(384, true, false); }
-                    else    { if (persist) VFM_PREP_ONCE(384, false, true); else VFM_PREP_ONCE(384, false, false); }
-                } else {
-                    if (h6) { if (persist) VFM_PREP_ONCE(256, true, true); else VFM_PREP_ONCE(256, true, false); }
-                    else    { if (persist) VFM_PREP_ONCE(256, false, true); else VFM_PREP_ONCE(256, false, false); }
-                }
-#undef VFM_PREP_ONCE
-                zero_pending = false;
-            } else
-            if (stream_form && (d == 384 || d == 256) && !any_f16) {   // the form that fits beside a coarse workgroup (prep_stream_kernel)
-                const dim3 sg((unsigned)groups), sb(256);
-                if (d == 384 && h6) hipLaunchKernelGGL((prep_stream_kernel<384, true>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else if (d == 384) hipLaunchKernelGGL((prep_stream_kernel<384, false>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else if (h6) hipLaunchKernelGGL((prep_stream_kernel<256, true>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-                else hipLaunchKernelGGL((prep_stream_kernel<256, false>), sg, sb, 0, st, x1, rows1, prep_out(p1, nullptr, h6), g1, x2, rows2, prep_out(p2, nullptr, h6), groups);
-            } else
-            hipLaunchKernelGGL((prep_chunk_kernel<false, 2, true, 8>), grid, dim3(512), (size_t)I8_GROUP * (d * 3 + d / 8 + 16), st, x1r, rows1, d,
-                               prep_out(p1, nullptr, h6), g1, x2r, rows2, prep_out(p2, nullptr, h6), groups);
-            if (want_f16)
-                hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)(t1 + t2)), dim3(256), (size_t)d * 64, st, x1, rows1, d, p1.inv,
-                                   p1.tiles, t1, x2, rows2, p2.inv, p2.tiles);
-        } else if (want_f16 && d <= 384) {  // both images from one read of the rows (144 KB of LDS at d = 384)
-            hipLaunchKernelGGL((prep_chunk_kernel<true, 2>), grid, block, (size_t)I8_GROUP * d * 3, st, x1r, rows1, d, prep_out(p1), g1, x2r,
-                               rows2, prep_out(p2), groups);
-        } else {
-            if (d <= 512)
-                hipLaunchKernelGGL((prep_chunk_kernel<false, 2>), grid, block, (size_t)I8_GROUP * d, st, x1r, rows1, d, prep_out(p1), g1, x2r,
-                                   rows2, prep_out(p2), groups);
-            else
-                hipLaunchKernelGGL((prep_chunk_kernel<false, 3>), grid, block, (size_t)I8_GROUP * d, st, x1r, rows1, d, prep_out(p1), g1, x2r,
-                                   rows2, prep_out(p2), groups);
-            if (want_f16) {  // wider rows: the fp16 image by its own kernel (both images would not fit the LDS)
-                hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)(t1 + t2)), dim3(256), (size_t)d * 64, st, x1, rows1, d, p1.inv,
-                                   p1.tiles, t1, x2, rows2, p2.inv, p2.tiles);
-            }
-        }
-        VFM_CHECK_LAUNCH("prep_chunk_kernel");
-        if (want_mx6_wide) {
-            const int64_t pad1 = rows_padded(rows1), total = pad1 + (x2 ? rows_padded(rows2) : 0);
-            if (d == 512)
-                hipLaunchKernelGGL((prep_mx6_rows_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(256), (size_t)16 * d * 4, st, x1r, rows1, pad1, d,
-                                   prep_out(p1, nullptr, h6), x2r, rows2, prep_out(p2, nullptr, h6), total);
-            else
-                hipLaunchKernelGGL((prep_mx6_rows_kernel<32>), dim3((unsigned)((total + 7) / 8)), dim3(256), (size_t)8 * d * 4, st, x1r, rows1, pad1, d,
-                                   prep_out(p1, nullptr, h6), x2r, rows2, prep_out(p2, nullptr, h6), total);
-            hipLaunchKernelGGL(prep_mx6_group_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, prep_out(p1, nullptr, h6), g1,
-                               prep_out(p2, nullptr, h6), groups);
-            VFM_CHECK_LAUNCH("prep_mx6_rows_kernel");
-        }
-        return zero_behind();
-    }
-    hipLaunchKernelGGL(prep_rows_kernel, dim3((unsigned)(t1 + t2)), dim3(256), (size_t)d * 64, st, x1, rows1, d, p1.inv, p1.tiles,
-                       t1, x2, rows2, p2.inv, p2.tiles);
-    VFM_CHECK_LAUNCH("prep_rows_kernel");
-    return zero_behind();
-}
-
-int do_prepare(const float* x, int64_t rows, int d, void* prepared, hipStream_t st) {
-    return do_prepare2(x, rows, prepared, nullptr, 0, nullptr, d, st);
-}
-
-int do_prepare_perm(const float* x, int64_t rows, const int* perm, int d, void* prepared, hipStream_t st) {
-    if (!i8_capable(d)) return vfm_fail(VFM_EINVAL, "prepare(perm): no int8 image for d = %d", d);
-    Prepared p1 = carve_prepared(prepared, rows, d);
-    const int g1 = (int)(rows_padded(rows) / I8_GROUP);
+    const int64_t pad1 = rows_padded(rows1), total = pad1 + (rows2 ? rows_padded(rows2) : 0);
+    const int t1 = (int)(pad1 / TILE_ROWS), g1 = (int)(pad1 / I8_GROUP), groups = (int)(total / I8_GROUP);
     static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
+    if (i8_capable(d) && !attr_done(attr_set)) {
+        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<true, 2>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 384 * 3));
         VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 2>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 512));
         VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 3>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * 768));
+        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep_chunk_kernel<false, 2, true, 8>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, I8_GROUP * (384 * 3 + 384 / 8 + 16)));
         attr_mark(attr_set);
     }
-    const dim3 grid((unsigned)prep_grid(g1, VFM_PREPARE_DEFAULT)), block(1024);
-    if (d <= 512)
-        hipLaunchKernelGGL((prep_chunk_kernel<false, 2>), grid, block, (size_t)I8_GROUP * d, st, x, rows, d, prep_out(p1, perm), g1,
-                           (const float*)nullptr, (int64_t)0, prep_out(Prepared{}), g1);
-    else
-        hipLaunchKernelGGL((prep_chunk_kernel<false, 3>), grid, block, (size_t)I8_GROUP * d, st, x, rows, d, prep_out(p1, perm), g1,
-                           (const float*)nullptr, (int64_t)0, prep_out(Prepared{}), g1);
-    VFM_CHECK_LAUNCH("prep_chunk_kernel(perm)");
+    for (int i = 0; i < plan.nlaunches; ++i) {
+        const PrepLaunch& l = plan.launches[i];
+        const dim3 grid(prep_grid(l, total, st)), block((unsigned)l.block);
+        const PrepOut o1 = prep_out(p1, perm, l.half6), o2 = prep_out(p2, nullptr, l.half6);
+        auto chunk = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, (size_t)l.lds, st, x1r, rows1, d, o1, g1, x2r, rows2, o2, groups); };
+        auto stream = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, x1, rows1, o1, g1, x2, rows2, o2, groups); };
+        auto once = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, x1, rows1, o1, g1, x2, rows2, o2, groups, zero); };
+        auto mx6_rows = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, (size_t)l.lds, st, x1r, rows1, pad1, d, o1, x2r, rows2, o2, total); };
+        switch (l.inst) {
+            case PREP_ROWS:
+                hipLaunchKernelGGL(prep_rows_kernel, grid, block, (size_t)l.lds, st, x1, rows1, d, p1.inv, p1.tiles, t1, x2, rows2, p2.inv, p2.tiles);
+                break;
+            case PREP_CHUNK_BOTH: chunk(prep_chunk_kernel<true, 2>); break;
+            case PREP_CHUNK_2: chunk(prep_chunk_kernel<false, 2>); break;
+            case PREP_CHUNK_3: chunk(prep_chunk_kernel<false, 3>); break;
+            case PREP_CHUNK_MX6: chunk(prep_chunk_kernel<false, 2, true, 8>); break;
+            case PREP_STREAM + 0: stream(prep_stream_kernel<256, false>); break;
+            case PREP_STREAM + 1: stream(prep_stream_kernel<256, true>); break;
+            case PREP_STREAM + 2: stream(prep_stream_kernel<384, false>); break;
+            case PREP_STREAM + 3: stream(prep_stream_kernel<384, true>); break;
+            case PREP_ONCE + 0: once(prep_once_kernel<256, false, false>); break;
+            case PREP_ONCE + 1: once(prep_once_kernel<256, false, true>); break;
+            case PREP_ONCE + 2: once(prep_once_kernel<256, true, false>); break;
+            case PREP_ONCE + 3: once(prep_once_kernel<256, true, true>); break;
+            case PREP_ONCE + 4: once(prep_once_kernel<384, false, false>); break;
+            case PREP_ONCE + 5: once(prep_once_kernel<384, false, true>); break;
+            case PREP_ONCE + 6: once(prep_once_kernel<384, true, false>); break;
+            case PREP_ONCE + 7: once(prep_once_kernel<384, true, true>); break;
+            case PREP_ONCE_NOI8 + 0: once(prep_once_kernel<256, true, false, true>); break;
+            case PREP_ONCE_NOI8 + 1: once(prep_once_kernel<256, true, true, true>); break;
+            case PREP_ONCE_NOI8 + 2: once(prep_once_kernel<384, true, false, true>); break;
+            case PREP_ONCE_NOI8 + 3: once(prep_once_kernel<384, true, true, true>); break;
+            case PREP_MX6_ROWS_16: mx6_rows(prep_mx6_rows_kernel<16>); break;
+            case PREP_MX6_ROWS_32: mx6_rows(prep_mx6_rows_kernel<32>); break;
+            case PREP_MX6_GROUP: hipLaunchKernelGGL(prep_mx6_group_kernel, grid, block, 0, st, o1, g1, o2, groups); break;
+        }
+        VFM_CHECK_LAUNCH(prep_inst_name(l.inst));
+    }
+    if (plan.zero == PREP_ZERO_BEHIND) {
+        hipLaunchKernelGGL(prep_zero_kernel, dim3((unsigned)((nz + 255) / 256 < 1024 ? (nz + 255) / 256 : 1024)), dim3(256), 0, st, zero);
+        VFM_CHECK_LAUNCH("prep_zero_kernel");
+    }
     return VFM_OK;
+}
+
+int do_prepare2(int entry, int schedule, Rows x1, int64_t rows1, void* prepared1, Rows x2, int64_t rows2, void* prepared2, int d,
+                hipStream_t st, PrepZero zero) {
+    return launch_prepare(entry, schedule, x1, rows1, prepared1, x2, rows2, prepared2, d, nullptr, st, zero);
+}
+
+int do_prepare_perm(const float* x, int64_t rows, const int* perm, int d, void* prepared, hipStream_t st) {
+    return launch_prepare(VFM_PREP_ENTRY_PERM, VFM_PREPARE_DEFAULT, x, rows, prepared, Rows(), 0, nullptr, d, perm, st, PrepZero{});
 }
 
 }  // namespace vfmm

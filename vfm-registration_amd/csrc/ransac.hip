@@ -1342,18 +1342,6 @@ VFM_EXPORT int vfm_ransac_corr_bounded(const double* src, int64_t ns, const doub
                             best_hyp_out, bad_out, ws, ws_bytes, stream);
 }
 namespace {
-// compute units of the device (the grid of ransac_coarse_loop_kernel), asked for once per process: the devices of one job are alike
-int ransac_compute_units() {
-    static std::atomic<int> ncu{0};
-    int cus = ncu.load(std::memory_order_relaxed);
-    if (cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        ncu.store(cus, std::memory_order_relaxed);
-    }
-    return cus;
-}
 int ransac_corr_impl(const double* src, int64_t ns, const double* tgt, int64_t nt, const int32_t* corres, const int64_t* count_dev,
                      int64_t c_max, double max_dist, int32_t n_iter, uint64_t seed, double* T_out, double* fitness_out,
                      double* rmse_out, uint8_t* inlier_mask, int32_t* best_hyp_out, int32_t* bad_out, void* ws, size_t ws_bytes,
@@ -1370,7 +1358,7 @@ int ransac_corr_impl(const double* src, int64_t ns, const double* tgt, int64_t n
     if (vfm_cfg().ransac_fused == 1 && !vfm_cfg().ransac_exact_only && c_max > 0) {
         // chain 1 (round 6, measured and NOT the default: 0.195 ms against 0.187 at 10^4 correspondences -- the stage is its kernels'
         // own dependent chains, not its launch boundaries: tools/time_ransac.py): 5 launches for the 11 below, same winner
-        const int cus = ransac_compute_units();
+        const int cus = vfm_compute_units();
         hipLaunchKernelGGL(ransac_prepare_kernel, dim3(1), dim3(1024), 0, st, src, tgt, corres, count_dev, c_max, w.pts, ns, nt, bad_out,
                            w.stats, w.pts32, w.sel);
         hipLaunchKernelGGL(ransac_moment_kernel, dim3(nblocks), dim3(64), 0, st, w.pts, w.stats, count_dev, c_max, max_d2, n_iter, seed,
@@ -1408,7 +1396,7 @@ int ransac_corr_impl(const double* src, int64_t ns, const double* tgt, int64_t n
             // list + one wave per candidate), minus the launches that only hand a flag on: the select state is reset by the centring
             // kernel, R* comes out of the moment pass (F = C is known there), the point-wise pass is a small grid that looks at the flag,
             // final + mask are one workgroup.  8 launches for 11.
-            const int cus = ransac_compute_units();   // (asked once: this call sits among the ~30 the host issues per pipeline cycle)
+            const int cus = vfm_compute_units();   // (cached per device: this call sits among the ~30 the host issues per pipeline cycle)
             hipLaunchKernelGGL(ransac_center_kernel, dim3(1), dim3(1024), 0, st, w.pts, count_dev, c_max, w.stats, w.pts32, w.sel);
             hipLaunchKernelGGL(ransac_moment_kernel, dim3(nblocks), dim3(64), 0, st, w.pts, w.stats, count_dev, c_max, max_d2,
                                n_iter, seed, w.hyps, w.sel, 1);

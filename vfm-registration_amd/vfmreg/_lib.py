@@ -136,6 +136,7 @@ DEBUG_SIGNATURES = {
     "vfm_debug_last_coarse_kernel": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_coarse_kernel_names": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_search_plan": (C.c_int, [C.c_int, C.c_int, c_i64, c_i64, C.c_int, C.c_char_p, C.c_int]),
+    "vfm_debug_prepare_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i64, C.c_int, c_i64, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "vfm_debug_match_stats": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "vfm_debug_i8_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_mx6_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp]),
@@ -304,6 +305,18 @@ def search_plan(records: int, d: int, n: int, m: int, gated: bool = True) -> dic
     out = {k: bool(int(v)) for k, v in plan.items() if k not in ("pass", "kind", "finish")}
     out.update({"pass": plan["pass"], "kind": int(plan["kind"]), "finish": plan["finish"].split(",")})
     return out
+
+
+def prepare_plan(entry: int, schedule: int, d: int, rows1: int, rows2: int = 0, dtype1: int = 0, dtype2: int = 0, zero: bool = False) -> dict:
+    """What a preparation would do under the calling thread's Config (include/vfmreg_debug.h, vfm_debug_prepare_plan; entry: a
+    VFM_PREP_ENTRY_* value): {"images": [...], "kernels": [launch order], "grid": str, "zero": "none" | "inside" | "behind"}.
+    Raises RuntimeError with the library's message where the entry itself would refuse.  Touches no device."""
+    buf = C.create_string_buffer(1024)
+    check(load().vfm_debug_prepare_plan(entry, schedule, d, rows1, dtype1, rows2, dtype2, int(zero), buf, len(buf)), "prepare_plan")
+    plan = dict(item.split("=", 1) for item in buf.value.decode().split(" "))
+    # (template arguments hold commas: a new kernel starts where "prep_" does)
+    return {"images": plan["images"].split(","), "kernels": plan["kernels"].replace(",prep_", " prep_").split(" "), "grid": plan["grid"],
+            "zero": plan["zero"]}
 
 
 def check(rc: int, what: str = "") -> None:

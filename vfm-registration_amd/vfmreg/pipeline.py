@@ -260,6 +260,12 @@ class RegistrationPipeline:
         except RuntimeError:
             return False
 
+    def _prepares_without_i8(self, records: int, probe: bool, f16_rows: bool) -> bool:
+        """Does this registration's preparation get VFM_PREPARE_NO_I8?  (The library's authority on what that flag needs is resolve_prepare,
+        csrc/match_internal.h; the rule is repeated here to spare a read-back per registration, and tests/test_prepare_plan.py holds the two together.)"""
+        return (records == 8 and self._noi8_shape and self._ws_clean and not probe and not f16_rows
+                and _lib.policy("half_noi8") == 1 and _lib.policy("prep_form") in (3, 4))
+
     def prepare_map(self, b_desc: torch.Tensor) -> None:
         """IndexFlatIP.add: normalise + convert the map once (it is immutable per scene); every buffer
         set gets its own copy so that ``register(..., reuse_map=True)`` never re-prepares."""
@@ -478,8 +484,7 @@ class RegistrationPipeline:
                     # VFM_PREPARE_MX6_HALF: the half-width pass reads the first d / 2 columns of the fp6 image -- only those are
                     # converted, and no int8 half-width image is written (the probe that needs it runs outside this mode)
                     schedule |= 8 | 16
-                if (records == 8 and self._noi8_shape and self._ws_clean and not probe and not (f16q or f16b)
-                        and _lib.policy("half_noi8") == 1 and _lib.policy("prep_form") in (3, 4)):
+                if self._prepares_without_i8(records, probe, f16q or f16b):
                     # nothing behind a kind-8 coarse pass needs the int8 image (the rescan runs on the fp6 half image): it is not written.
                     # When the search's guard goes up, `auto` leaves kind 8 on that search's feedback and the next pair gets the image again.
                     schedule |= 32   # VFM_PREPARE_NO_I8
