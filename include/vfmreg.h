@@ -580,6 +580,43 @@ int vfm_icp_step_nearest_desc(const double *src, int64_t n, const double *T_host
 int vfm_icp_build_system(const double *src, const double *tgt, const uint8_t *valid, int64_t n,
                          double kernel, double *out43, vfm_stream_t stream);
 
+/* ------------------------------------------------------------------ LiDAR odometry (KISS-ICP front end) */
+
+/* Preprocess (src/kiss-icp/cpp/kiss_icp/core/Preprocessing.cpp:139-197): idx_out (int64[n]) receives the ascending indices i of the rows
+ * with min_range < norm_i < max_range, both bounds strict, norm_i = sqrt((x x + y y) + z z) in fp64 without contraction; *count_out
+ * (int64, device memory) their number.  pts: n rows of `stride` fp64, xyz first (as vfm_voxel_first takes them).  One enqueue, no host
+ * synchronisation.  n == 0 is valid (pts and idx_out may be NULL): the count is 0. */
+int vfm_range_crop(const double *pts, int64_t n, int64_t stride, double min_range, double max_range, int64_t *idx_out,
+                   int64_t *count_out, vfm_stream_t stream);
+
+/* DeSkewScan (src/kiss-icp/cpp/kiss_icp/core/Deskew.cpp:40-68): out[i] = exp((timestamps[i] - 0.5) delta) pts[i].xyz, with Sophus'
+ * SE3::exp (two branches, the first-order one below theta = 1e-10).  delta_host: the twist [upsilon, omega] = log(start^-1 finish),
+ * 6 fp64 in HOST memory, read at the call.  pts: n rows of `stride` fp64; timestamps: n fp64; out: n x 3 fp64 (the other columns of a
+ * row are the caller's to carry). */
+int vfm_deskew_scan(const double *pts, int64_t n, int64_t stride, const double *timestamps, const double *delta_host, double *out,
+                    vfm_stream_t stream);
+
+/* VoxelHashMap::Update for the 3-D map (src/kiss-icp/cpp/kiss_icp/core/VoxelHashMap.cpp:693-699, 733-744, 772-779) on the grid that
+ * vfm_icp_nearest reads, without sorting the map again.  Old grid: keys[nv], start[nv + 1], pts[nk][3] (nk = start[nv]).  New points:
+ * xyz_new, m x 3 fp64 in insertion order, moved by T_host first (16 fp64 in HOST memory, row-major, read at the call; NULL: taken as
+ * they are) with the arithmetic of vfm_transform_xyz_f64.  A new point enters voxel trunc(p / voxel_size) iff that voxel holds fewer
+ * than max_points_per_voxel points (0: no cap), old points counting first, then new points in input order; inside a voxel the old
+ * points keep their order and the new ones follow in input order.  Then, if origin_host (3 fp64 in HOST memory) is given, every voxel
+ * whose FIRST point p has ((dx dx + dy dy) + dz dz) > max_distance^2, d = p - origin, is dropped whole -- a voxel this call created
+ * included; NULL: nothing is removed (plain AddPoints).  EVERY far voxel goes: the reference's container erases while it iterates and
+ * keeps some until the next call.
+ * Output: a new grid in caller-owned buffers that do not alias the old ones, sized for nv + m keys, nv + m + 1 starts and nk + m
+ * points; written are keys_out[0, n_voxels), start_out[0, n_voxels] and pts_out[0, n_kept)[3], and info_out (int32[6], device
+ * memory) = {n_voxels, n_kept, status, points_added, voxels_removed, points_removed}; status as in vfm_icp_grid_build (a new point
+ * with |v| >= 2^20 - 1).  nv == 0, m == 0 and "every voxel removed" are valid; an empty grid has start_out[0] = 0.  One enqueue, no
+ * host synchronisation.  vfm_icp_grid_update_workspace_bytes sizes the scratch (0 for sizes the entry refuses: nk + m <= 2^30);
+ * nothing outside ws[0, ws_bytes) and the stated output ranges is written. */
+size_t vfm_icp_grid_update_workspace_bytes(int32_t nv, int64_t nk, int64_t m);
+int vfm_icp_grid_update(const int64_t *keys, const int32_t *start, const double *pts, int32_t nv, int64_t nk, const double *xyz_new,
+                        int64_t m, const double *T_host, double voxel_size, int32_t max_points_per_voxel, const double *origin_host,
+                        double max_distance, int64_t *keys_out, int32_t *start_out, double *pts_out, int32_t *info_out, void *ws,
+                        size_t ws_bytes, vfm_stream_t stream);
+
 /* ------------------------------------------------------------------ FPFH descriptors (Open3D 0.18 baseline) */
 
 /* The CPU work of extract_fpfh_features (src/vfm-reg/src/vfm_reg/descriptors.py:19-44), which the reference runs in Open3D 0.18.

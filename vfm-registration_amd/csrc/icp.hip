@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "grid3.h"
+#include "icp_voxels.h"
 
 namespace {
 
@@ -237,26 +238,7 @@ __global__ __launch_bounds__(256) void icp_system_kernel(const double* __restric
 // ---- The grid itself, built on the device (vfm_icp_grid_build): key of every point -> stable radix sort of (key, input index) -> run
 // starts and "among the first `cap` of its run" flags -> two prefix sums -> one compaction.  A point's place in the output is a pure
 // function of the sorted sequence (no atomic decides an order); the one atomic raises the out-of-range flag.
-constexpr int64_t ICP_GRID_MAX_POINTS = (int64_t)1 << 30;   // int32 positions and prefix sums
-
-// v = trunc(xyz / voxel_size), a true division; an axis with |v| >= 2^20 - 1 (or a NaN) is out of range: v = 0 and the status flag
-struct IcpVoxels {   // the quantiser of grid3::keys_kernel
-    static constexpr const char* kernel_name = "grid3::keys_kernel<IcpVoxels>";
-    double voxel_size;
-    __device__ long long operator()(double x, double y, double z, bool& bad) const {
-        const double lim = (double)((1 << 20) - 1);
-        const double p[3] = {x, y, z};
-        int v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double t = trunc(p[c] / voxel_size);
-            const bool ok = fabs(t) < lim;   // (false for NaN too)
-            bad = bad || !ok;
-            v[c] = ok ? (int)t : 0;
-        }
-        return grid3::key(v[0], v[1], v[2]);
-    }
-};
+// (the quantiser IcpVoxels and ICP_GRID_MAX_POINTS: icp_voxels.h, shared with the update of odometry.hip)
 
 // head[i]: sorted position i opens a run of equal keys; keep[i]: it is among the first `cap` positions of its run (cap 0: all) --
 // position i - cap carries another key, or does not exist

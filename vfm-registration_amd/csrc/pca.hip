@@ -19,6 +19,7 @@
 //   vfm_pca_colours   (y - min) / (max - min), fp32 values or truncated uint8 colours
 //   vfm_colour_gate   per colour the rows within the radius, ascending (one workgroup per colour, ordered as vfm_threshold_compact)
 #include "common.h"
+#include "ordered_compact.h"
 
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -331,8 +332,7 @@ __global__ __launch_bounds__(256) void pca_colours_kernel(const double* __restri
 __global__ __launch_bounds__(1024) void colour_gate_kernel(const unsigned char* __restrict__ colours, int64_t n,
                                                            const double* __restrict__ gate, double r2, int64_t* __restrict__ idx,
                                                            int64_t* __restrict__ counts) {
-    __shared__ int wsum[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ OrderedCompactLds lds;
     const double cr = gate[3 * blockIdx.x], cg = gate[3 * blockIdx.x + 1], cb = gate[3 * blockIdx.x + 2];
     int64_t* out = idx + (size_t)blockIdx.x * n;
     int64_t base = 0;
@@ -344,17 +344,9 @@ __global__ __launch_bounds__(1024) void colour_gate_kernel(const unsigned char* 
             const double dr = (double)colours[3 * i] - cr, dg = (double)colours[3 * i + 1] - cg, db = (double)colours[3 * i + 2] - cb;
             hit = (dr * dr + dg * dg) + db * db < r2;
         }
-        const unsigned long long bal = __ballot(hit);
-        if (lane == 0) wsum[buf][wave] = __popcll(bal);
-        __syncthreads();   // (two buffers: a wave that runs ahead writes the other one, and is held at the next barrier)
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const int c = wsum[buf][w];
-            if (w < wave) before += c;
-            total += c;
-        }
-        if (hit) out[base + before + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+        int total;
+        const int place = ordered_compact_pass(lds, buf, hit, total);   // (ordered_compact.h)
+        if (hit) out[base + place] = i;
         base += total;
     }
     if (threadIdx.x == 0) counts[blockIdx.x] = base;

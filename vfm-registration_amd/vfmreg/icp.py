@@ -41,6 +41,64 @@ def se3_exp(dx: np.ndarray) -> np.ndarray:
     return T
 
 
+SOPHUS_EPSILON = 1e-10  # Sophus::Constants<double>::epsilon()
+OUT_OF_RANGE_MESSAGE = ("voxel coordinate outside +-2^20 voxels: shift the clouds towards the origin "
+                        "(the ICP grid key holds 21 bits per axis)")
+
+
+def quaternion_of(R: np.ndarray):
+    """Eigen's rotation matrix -> quaternion (w, vec): the trace branch, else the branch of the largest diagonal element
+    (what Sophus::SO3d and Eigen::AngleAxisd make of a matrix)."""
+    R = np.asarray(R, dtype=np.float64)
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    q = np.zeros(3)
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        w = 0.5 * t
+        t = 0.5 / t
+        q[0] = (R[2, 1] - R[1, 2]) * t
+        q[1] = (R[0, 2] - R[2, 0]) * t
+        q[2] = (R[1, 0] - R[0, 1]) * t
+    else:
+        i = 0
+        if R[1, 1] > R[0, 0]:
+            i = 1
+        if R[2, 2] > R[i, i]:
+            i = 2
+        j = (i + 1) % 3
+        k = (j + 1) % 3
+        t = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+        q[i] = 0.5 * t
+        t = 0.5 / t
+        w = (R[k, j] - R[j, k]) * t
+        q[j] = (R[j, i] + R[i, j]) * t
+        q[k] = (R[k, i] + R[i, k]) * t
+    return float(w), q
+
+
+def se3_log(T: np.ndarray) -> np.ndarray:
+    """Sophus::SE3d::log of a 4x4 matrix -> tangent [upsilon, omega]: the rotation vector through the quaternion (SO3::logAndTheta),
+    upsilon = V^-1 t with the small-angle branch of V^-1.  The inverse of ``se3_exp``."""
+    T = np.asarray(T, dtype=np.float64)
+    w, q = quaternion_of(T[:3, :3])
+    squared_n = float(q @ q)
+    if squared_n < SOPHUS_EPSILON * SOPHUS_EPSILON:
+        two_atan_nbyw_by_n = 2.0 / w - (2.0 / 3.0) * squared_n / (w * w * w)
+    else:
+        n = np.sqrt(squared_n)
+        atan_nbyw = np.arctan2(-n, -w) if w < 0 else np.arctan2(n, w)
+        two_atan_nbyw_by_n = 2.0 * atan_nbyw / n
+    om = two_atan_nbyw_by_n * q
+    theta = float(np.sqrt(om @ om))
+    Om = np.array([[0, -om[2], om[1]], [om[2], 0, -om[0]], [-om[1], om[0], 0]])
+    if abs(theta) < SOPHUS_EPSILON:
+        V_inv = np.eye(3) - 0.5 * Om + (1.0 / 12.0) * (Om @ Om)
+    else:
+        half = 0.5 * theta
+        V_inv = np.eye(3) - 0.5 * Om + (1.0 - theta * np.cos(half) / (2.0 * np.sin(half))) / (theta * theta) * (Om @ Om)
+    return np.r_[V_inv @ T[:3, 3], om]
+
+
 class VoxelGridDevice:
     """Sorted-key CSR copy of a VoxelHashMap's 3-D points on the GPU (what GetCorrespondences reads)."""
 

@@ -12,6 +12,9 @@ kept points, so it is recomputed from that sequence when points were added.  The
 runs on the GPU through the C ABI; besides the reference's (source, target) coordinate pair the
 indices are available (``get_vfm_correspondence_indices``), which makes the KD-tree index recovery
 of registration_node.py:288-317 unnecessary.
+
+``update`` and ``remove_far_away_points`` (mapping.py:59-75, 89-90; 3-column points) turn the 3-D map into the odometry's local map:
+from then on it lives as the sorted-key grid ICP searches, updated in place on the device (csrc/odometry.hip ``vfm_icp_grid_update``).
 """
 from __future__ import annotations
 
@@ -154,6 +157,63 @@ class VoxelHashMap:
         self._prep = None
         self._xyz = None
         self._drop_icp_grids()
+
+    # ------------------------------------------------------------------ the local map of the odometry
+    # VoxelHashMap::Update (VoxelHashMap.cpp:693-699: AddPoints of the posed points, then RemovePointsFarFromLocation of the pose's
+    # translation) for the 3-D map.  Both calls run through vfm_icp_grid_update on the sorted-key grid that ICP searches; from the first
+    # of them on the map KEEPS that grid on the device (icp._grid_of finds it and does not rebuild), and its stored points are the
+    # grid's, in (voxel key, insertion) order -- which is what point_cloud() then returns: the reference's set of points, not its
+    # robin-map order after erasures.  Every far voxel goes, where the reference's erase-while-iterating keeps some until
+    # the next call.  A map on which neither was called is untouched by any of this.
+    def update(self, points, pose: np.ndarray = np.eye(4)):
+        """mapping.py:59-75 for 3-column points (numpy, or fp64 [n, 3] on the device)"""
+        if not isinstance(points, torch.Tensor):
+            points = np.asarray(points)
+        if points.ndim != 2 or points.shape[1] < 3:
+            raise ValueError("Invalid shape")  # mapping.py:73
+        if points.shape[1] != 3:
+            raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {points.shape[1]} (only 3-column "
+                                      "points are kept in a device-resident local map)")
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        if pose.shape != (4, 4):
+            raise ValueError("expected a 4 x 4 pose")
+        xyz = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).cuda()
+        return self._grid_update(xyz.contiguous(), pose, pose[:3, 3])
+
+    def remove_far_away_points(self, origin):
+        """mapping.py:89-90: drop every voxel whose first point is farther than max_distance from ``origin``"""
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        if origin.shape != (3,):
+            raise ValueError("expected an origin of 3 values")
+        return self._grid_update(None, None, origin)
+
+    def _grid_update(self, xyz, pose, origin):
+        from .icp import OUT_OF_RANGE_MESSAGE, VoxelGridDevice, _grid_of
+        g = _grid_of(self) if not self.empty() else None
+        if xyz is not None and xyz.shape[0] == 0:
+            xyz = None
+        out = ops.icp_grid_update(None if g is None else g.keys, None if g is None else g.start, None if g is None else g.pts, xyz, pose,
+                                  self.voxel_size, self.max_points_per_voxel, origin, self.max_distance)
+        info_h = getattr(ops._tls, "icp_update_info", None)   # page-locked: the update's one read-back
+        if info_h is None:
+            info_h = ops._tls.icp_update_info = torch.zeros(6, dtype=torch.int32).pin_memory()
+        info_h.copy_(out["info"], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        n_voxels, n_kept, status, added, voxels_removed, points_removed = info_h.tolist()
+        if status:
+            raise ValueError(OUT_OF_RANGE_MESSAGE)   # (the map is left as it was)
+        grid = VoxelGridDevice.__new__(VoxelGridDevice)
+        grid.voxel_size = self.voxel_size
+        grid.n_voxels, grid.n_kept = n_voxels, n_kept
+        grid.keys, grid.start, grid.pts = out["keys"][:n_voxels], out["start"][:n_voxels + 1], out["pts"][:n_kept]
+        self._chunks["3"] = [(grid.pts, grid.pts)] if n_kept else []
+        if n_kept:
+            self._ordered["3"] = (grid.pts, grid.pts)
+        else:
+            self._ordered.pop("3", None)
+        self.__dict__.pop("_icp_grid", None)
+        self._icp_grid = (n_kept, grid)
+        self.last_update = dict(points_added=added, voxels_removed=voxels_removed, points_removed=points_removed)
 
     def _cloud(self, kind: str):
         """(rows, xyz64) of one of the maps as the reference walks it (VoxelHashMap.cpp:628-676), on the device."""

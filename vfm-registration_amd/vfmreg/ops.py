@@ -10,6 +10,7 @@ import math
 import threading
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -786,3 +787,82 @@ def colour_gate(colours: torch.Tensor, gate_colours: torch.Tensor, radius: float
     _lib.check(_lib.load().vfm_colour_gate(colours.data_ptr(), n, gate_colours.data_ptr(), m, float(radius), idx.data_ptr(), counts.data_ptr(),
                                            _stream()), "colour_gate")
     return idx, counts
+
+
+# ------------------------------------------------------------------------------------- odometry (csrc/odometry.hip)
+def _rows_f64(rows: torch.Tensor, name: str) -> torch.Tensor:
+    _chk(rows, torch.float64, name)
+    if rows.dim() != 2 or rows.shape[1] < 3:
+        raise ValueError("Invalid shape")
+    return rows
+
+
+def range_crop(rows: torch.Tensor, min_range: float, max_range: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vfm_range_crop (Preprocess, Preprocessing.cpp:139-197): (idx int64[n], count int64[1]) -- the rows of ``rows`` (fp64 [n, w >= 3],
+    xyz first) with min_range < |xyz| < max_range, ascending, in the first ``count`` entries of ``idx``.  No read-back."""
+    _rows_f64(rows, "rows")
+    n, stride = rows.shape
+    idx = torch.empty(max(n, 1), dtype=torch.int64, device=rows.device)
+    count = torch.empty(1, dtype=torch.int64, device=rows.device)
+    _lib.check(_lib.load().vfm_range_crop(rows.data_ptr() if n else None, n, stride, float(min_range), float(max_range), idx.data_ptr(),
+                                          count.data_ptr(), _stream()), "range_crop")
+    return idx, count
+
+
+def deskew_scan(rows: torch.Tensor, timestamps: torch.Tensor, delta) -> torch.Tensor:
+    """vfm_deskew_scan (DeSkewScan, Deskew.cpp:40-68): exp((t_i - 0.5) delta) applied to the coordinates of ``rows`` (fp64 [n, w >= 3]);
+    ``delta``: the twist [upsilon, omega] on the host.  Returns fp64 [n, 3]."""
+    _rows_f64(rows, "rows")
+    _chk(timestamps, torch.float64, "timestamps")
+    n, stride = rows.shape
+    if timestamps.dim() != 1 or timestamps.shape[0] != n:
+        raise ValueError("expected one timestamp per row")
+    d = np.ascontiguousarray(delta, dtype=np.float64)
+    if d.shape != (6,):
+        raise ValueError("expected a twist of 6 values")
+    out = torch.empty((n, 3), dtype=torch.float64, device=rows.device)
+    _lib.check(_lib.load().vfm_deskew_scan(rows.data_ptr() if n else None, n, stride, timestamps.data_ptr() if n else None, d.ctypes.data,
+                                           out.data_ptr() if n else None, _stream()), "deskew_scan")
+    return out
+
+
+def icp_grid_update(keys: Optional[torch.Tensor], start: Optional[torch.Tensor], pts: Optional[torch.Tensor], xyz_new: Optional[torch.Tensor],
+                    T, voxel_size: float, max_points_per_voxel: int, origin, max_distance: float, ws: Optional[torch.Tensor] = None):
+    """vfm_icp_grid_update: VoxelHashMap::Update on the sorted-key grid (keys int64[nv], start int32[nv + 1], pts fp64[nk, 3]; all None:
+    an empty grid).  ``xyz_new``: fp64 [m, 3] on the device or None; ``T``: a 4 x 4 on the host or None (points as they are); ``origin``:
+    3 values on the host or None (nothing is removed).  Returns ``dict(keys, start, pts, info)`` of device tensors sized nv + m, nv + m + 1,
+    nk + m and 6 -- info = {n_voxels, n_kept, status, points_added, voxels_removed, points_removed}.  No read-back."""
+    lib = _lib.load()
+    nv = 0 if keys is None else int(keys.shape[0])
+    nk = 0 if pts is None else int(pts.shape[0])
+    m = 0 if xyz_new is None else int(xyz_new.shape[0])
+    if nv:
+        _chk(keys, torch.int64, "keys")
+        _chk(start, torch.int32, "start")
+        _chk(pts, torch.float64, "pts")
+        if start.shape[0] != nv + 1 or pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("expected start [nv + 1] and pts [nk, 3]")
+    if m:
+        _chk(xyz_new, torch.float64, "xyz_new")
+        if xyz_new.dim() != 2 or xyz_new.shape[1] != 3:
+            raise ValueError("Invalid shape")
+    dev = xyz_new.device if m else (keys.device if nv else torch.device("cuda"))
+    Th = None if T is None else np.ascontiguousarray(T, dtype=np.float64)
+    if Th is not None and Th.shape != (4, 4):
+        raise ValueError("expected a 4 x 4 pose")
+    oh = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64)
+    if oh is not None and oh.shape != (3,):
+        raise ValueError("expected an origin of 3 values")
+    keys_out = torch.empty(max(nv + m, 1), dtype=torch.int64, device=dev)
+    start_out = torch.empty(nv + m + 1, dtype=torch.int32, device=dev)
+    pts_out = torch.empty((max(nk + m, 1), 3), dtype=torch.float64, device=dev)
+    info = torch.empty(6, dtype=torch.int32, device=dev)
+    need = lib.vfm_icp_grid_update_workspace_bytes(nv, nk, m)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    _lib.check(lib.vfm_icp_grid_update(keys.data_ptr() if nv else None, start.data_ptr() if nv else None, pts.data_ptr() if nv else None, nv, nk,
+                                       xyz_new.data_ptr() if m else None, m, None if Th is None else Th.ctypes.data, float(voxel_size),
+                                       int(max_points_per_voxel), None if oh is None else oh.ctypes.data, float(max_distance),
+                                       keys_out.data_ptr(), start_out.data_ptr(), pts_out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream()), "icp_grid_update")
+    return dict(keys=keys_out, start=start_out, pts=pts_out, info=info)
