@@ -74,14 +74,6 @@ const char *vfm_build_info(void);
  *   "voxel_small"        a code: 0 / 1 = VoxelDownsample-shaped calls by the general multi-launch path / the one-launch kernel (default);
  *                        2 / 3 = round 4's / round 5's (default) per-cluster replay; 10 + k = k points per thread of the one-launch kernel
  *                        (10 = by size); 100 / 101 = its phase stamps off / on (vfm_debug_voxel_trace)
- *   "vit_gemm"           value = (narrow << 32) | (uint32) wide: narrow > 0: ViT GEMM wave tile / prefetch depth NT * 100 + PF for N <= 512
- *                        (narrow) and N > 512 (wide); narrow = -3 / -4 XCD-consistent tile mapping on (default) / off; -5 the LDS-tiled GEMM
- *                        from `wide` workgroups on (default 256, 0 never); -6 its stage shape, k-steps x 10 + stages (23); -7 attention with
- *                        K / V^T through the LDS from `wide` images on (1; 0 never); -8 waves per workgroup of the direct kernel; -9 the
- *                        token-stationary QKV / fc1 kernel from `wide` groups of 128 rows on (0 default rule, -1 never); -10 its waves per
- *                        workgroup; -11 / -12 low / high half of a device pointer to its placement trace (tools); -14 preprocessing by one
- *                        workgroup per patch (1, default) / round 1's kernel (0); -15 two (default) / one channel tile per wave; -16 timing
- *                        experiment, WRONG RESULTS; -17 residual GEMMs of the LDS-tiled path as 128 x 384 tiles (1) / 128 x 128 (0, default)
  *   "vit_fused_qkv"      QKV product + attention of an (image, head) in one workgroup (vit_qkv_attention_kernel: q, K, V^T never leave the
  *                        compute unit; the same bits as the two kernels): 0 (default) vfm_vit_forward's policy -- ViT-S width, from 24 images per
  *                        call on, unless a second round of workgroups would be less than a quarter full --, n > 0 from n images on, -1 never
@@ -90,7 +82,7 @@ const char *vfm_build_info(void);
  *                        fifths full: a single round runs in lockstep and ends level with the two kernels --, n > 0
  *                        from n images per call on, -1 never
  *   and the single fields behind the codes: "coarse_qsets", "seed_units", "select_variant", "mx6_t4", "mx6_ns3", "prep_form" (0, 1, 3, 4),
- *   "finish_short", "rescan_rows", "rescore_block" (64 / 256: queries per workgroup of the fp64 decision, the same bits; anything else is refused; an untouched config reads 0: 256 behind the half-width record kinds, 64 elsewhere), "vit_*", "voxel_replay2", "voxel_one_launch", "voxel_trace", "voxel_grid_ppt" (vfm_config_get reads these;
+ *   "finish_short", "rescan_rows", "rescore_block" (64 / 256: queries per workgroup of the fp64 decision, the same bits; anything else is refused; an untouched config reads 0: 256 behind the half-width record kinds, 64 elsewhere), the other "vit_*" keys (A/B switches of the ViT's kernels: include/vfmreg_debug.h), "voxel_replay2", "voxel_one_launch", "voxel_trace", "voxel_grid_ppt" (vfm_config_get reads these;
  *   cfg == NULL there: what the calling thread's entry points would read now). */
 typedef struct vfm_config vfm_config_t;
 int vfm_config_create(vfm_config_t **out);

@@ -11,7 +11,7 @@
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
- *   - vfm_debug_search_plan / vfm_debug_prepare_plan  read the calling thread's vfm_config and nothing else; host memory only.
+ *   - vfm_debug_search_plan / vfm_debug_prepare_plan / vfm_debug_vit_plan  read the calling thread's vfm_config and nothing else; host memory only.
  *   - vfm_debug_l2_narrow_slices  host arithmetic only; vfm_debug_l2_narrow_evals  reads a workspace's counters and synchronises the device.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
@@ -125,6 +125,34 @@ int vfm_debug_ransac_state(const void *ws, int64_t c_max, int32_t n_iter, int32_
  * by the forward's own carving routine.  After a forward the buffers hold what the LAST block left: q / k / vt are not written under
  * "vit_fused_qkv", h is not written under "vit_fused_mlp".  Does not touch the device. */
 int vfm_debug_vit_workspace_layout(const vfm_vit_config *cfg, int B, int64_t *offsets_host, int64_t *bytes_host);
+
+/* tests / tools: what vfm_vit_forward(cfg, ..., B images W pixels wide ...) would launch under the calling thread's vfm_config, resolved by
+ * the function the forward itself calls once (csrc/vit_plan.h, resolve_vit).  compute_units: of the device asked about, 0: the current
+ * device's.  One line of text to buf_host[cap]:
+ *     pre=.. patch=.. qkv=.. att=.. proj=.. fc1=.. fc2=..   each stage's launch as <kernel>@<workgroups>x<threads>+<bytes of dynamic LDS>, the
+ *              kernel an instantiation spelled from its template arguments (vit_gemm_lds_kernel<RESID,2,3>, vit_attention_lds_kernel<11>, ...);
+ *              a block's launches are those of every layer; "-": the stage is inside the kernel before it (att in vit_qkv_attention_kernel,
+ *              fc2 in vit_mlp_kernel)
+ *     launches=<kernel launches of the whole forward> trace=<the one stage whose launch gets "vit_trace_buffer" | none>
+ * A model or batch the forward refuses fails here with the same error.  Host memory only.
+ * The "vit_*" keys of vfm_config_set beside "vit_fused_qkv" / "vit_fused_mlp" (include/vfmreg.h); the same results under every value but "vit_hot_a":
+ *   "vit_preprocess_patch"  1 (default): preprocessing by one workgroup per patch; 0: a thread per fragment unit
+ *   "vit_xcd"               1 (default) / 0: a token tile's work on the workgroups of one XCD in every kernel, or not
+ *   "vit_cfg_narrow", "vit_cfg_wide"  the direct GEMM kernel's wave tile and prefetch depth for N <= 512 / N > 512: 108 (default), 116, 208
+ *   "vit_wpw"               waves per workgroup of the direct kernel: n > 0; 0 (default): one
+ *   "vit_lds_min_wg"        the LDS-tiled GEMM from this many workgroups on: n > 0 (default 256); 0: never
+ *   "vit_lds_shape"         its k-steps per stage x 10 + stages: 23 (default), 24, 25, 26, 42, 43
+ *   "vit_wide_tile"         1: its residual GEMMs of 384 channels as one 128 x 384 tile per workgroup; 0 (default): 128 x 128
+ *   "vit_hot_a"             timing experiment of the LDS-tiled kernel, WRONG RESULTS: bits 0 .. 3; 0 (default)
+ *   "vit_att_lds_min"       attention with K / V^T through the LDS from this many images on: n > 0 (default 1); 0: never
+ *   "vit_astat_min"         the token-stationary QKV / fc1 kernel from this many groups of 128 rows on: n > 0; 0 (default): where its rounds of
+ *                           one workgroup per compute unit are full; -1: never
+ *   "vit_astat_nw"          its waves per workgroup: 6, 8, 12, 16 where they divide the channel tiles, 112 = 12 with non-temporal stores; 0 (default): 12
+ *   "vit_astat_two"         1 (default) / 0: two channel tiles per wave (eight waves) / one
+ *   "vit_trace_fused"       which launch of a block gets the trace buffer: 0 (default) the token-stationary fc1, or else the LDS-tiled fc2;
+ *                           1 vit_qkv_attention_kernel; 2 the LDS-tiled proj; 3 vit_mlp_kernel
+ *   "vit_trace_buffer"      a device pointer (all 64 bits of the value) to the buffer that launch writes its per-workgroup stamps to; 0 (default): none */
+int vfm_debug_vit_plan(const vfm_vit_config *cfg, int B, int W, int compute_units, char *buf_host, int cap);
 
 /* VFM_MATCH_NARROW (csrc/match_l2_narrow.hip).  vfm_debug_l2_narrow_slices: the number of map slices the host rule gives a search of n
  * queries among m map rows (the grid is ceil(n / 256) query blocks x slices); 0 for n or m <= 0.  Host only, no device is touched.

@@ -124,26 +124,20 @@ def test_vit_lds_tiled_gemms_equal_the_direct_kernels_bit_for_bit():
     GEMMs as 128 x 128 tiles and as one 128 x 384 tile per workgroup; and the forced LDS path passes the oracle tolerance."""
     from vfmreg import _lib
     from vfmreg import vit as V
-    lib = _lib.load()
-    try:
-        for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (768, 1, 3072, 3, 560, 700), (384, 12, 1536, 6, 1200, 1600)):
-            w = V.random_weights(seed=11, dim=dim, depth=depth, mlp=mlp)
-            imgs = torch.from_numpy(_smooth_images(np.random.default_rng(3), B, H, W)).cuda()
-            model = V.ViTS14(w, H, W, device="cuda")
-            lib.vfm_debug_set_vit_gemm(-5, 0)        # never the LDS kernel
+    for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (768, 1, 3072, 3, 560, 700), (384, 12, 1536, 6, 1200, 1600)):
+        w = V.random_weights(seed=11, dim=dim, depth=depth, mlp=mlp)
+        imgs = torch.from_numpy(_smooth_images(np.random.default_rng(3), B, H, W)).cuda()
+        model = V.ViTS14(w, H, W, device="cuda")
+        with _lib.using(_lib.Config().set("vit_lds_min_wg", 0)):        # never the LDS kernel
             direct = model.forward(imgs).clone()
-            lib.vfm_debug_set_vit_gemm(-5, 1)        # always (every GEMM whose N is a multiple of 128)
-            for wide in (0, 1):                      # the residual GEMMs (N = 384) as 128 x 128 tiles / as one 128 x 384 tile per workgroup (round 5)
-                lib.vfm_debug_set_vit_gemm(-17, wide)
+        for wide in (0, 1):                      # the residual GEMMs (N = 384) as 128 x 128 tiles / as one 128 x 384 tile per workgroup (round 5)
+            with _lib.using(_lib.Config().set("vit_lds_min_wg", 1).set("vit_wide_tile", wide)):   # always (every GEMM whose N is a multiple of 128)
                 tiled = model.forward(imgs).clone()
-                torch.cuda.synchronize()
-                assert torch.equal(direct, tiled), (dim, B, wide, float((direct - tiled).abs().max()))
-        lib.vfm_debug_set_vit_gemm(-5, 1)
+            torch.cuda.synchronize()
+            assert torch.equal(direct, tiled), (dim, B, wide, float((direct - tiled).abs().max()))
+    with _lib.using(_lib.Config().set("vit_lds_min_wg", 1).set("vit_wide_tile", 1)):
         w = V.random_weights(seed=5, dim=128, depth=2, mlp=256)
         _check(w, _smooth_images(np.random.default_rng(0), 9, 300, 400), atol=1e-2, cos_min=0.99999)
-    finally:
-        lib.vfm_debug_set_vit_gemm(-5, 256)
-        lib.vfm_debug_set_vit_gemm(-17, 0)
 
 
 def test_vit_token_stationary_gemms_equal_the_other_kernels_bit_for_bit():
@@ -153,24 +147,18 @@ def test_vit_token_stationary_gemms_equal_the_other_kernels_bit_for_bit():
     and at a ViT-B-like width, whose rows (192 KiB) do not fit the LDS: the launcher then keeps the other kernels."""
     from vfmreg import _lib
     from vfmreg import vit as V
-    lib = _lib.load()
-    try:
-        for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (384, 1, 1536, 7, 1200, 1600), (768, 1, 3072, 3, 560, 700),
-                                           (384, 12, 1536, 6, 1200, 1600)):
-            w = V.random_weights(seed=17, dim=dim, depth=depth, mlp=mlp)
-            imgs = torch.from_numpy(_smooth_images(np.random.default_rng(5), B, H, W)).cuda()
-            model = V.ViTS14(w, H, W, device="cuda")
-            lib.vfm_debug_set_vit_gemm(-9, -1)       # never
+    for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (384, 1, 1536, 7, 1200, 1600), (768, 1, 3072, 3, 560, 700),
+                                       (384, 12, 1536, 6, 1200, 1600)):
+        w = V.random_weights(seed=17, dim=dim, depth=depth, mlp=mlp)
+        imgs = torch.from_numpy(_smooth_images(np.random.default_rng(5), B, H, W)).cuda()
+        model = V.ViTS14(w, H, W, device="cuda")
+        with _lib.using(_lib.Config().set("vit_astat_min", -1)):       # never
             ref = model.forward(imgs).clone()
-            lib.vfm_debug_set_vit_gemm(-9, 1)        # always (QKV and fc1, wherever 128 rows of A fit the LDS)
-            for two in (0, 1):                       # round 4's form (one channel tile per wave) and round 5's (two: half the LDS reads per MFMA)
-                lib.vfm_debug_set_vit_gemm(-15, two)
+        for two in (0, 1):                       # round 4's form (one channel tile per wave) and round 5's (two: half the LDS reads per MFMA)
+            with _lib.using(_lib.Config().set("vit_astat_min", 1).set("vit_astat_two", two)):   # always (QKV and fc1, wherever 128 rows of A fit the LDS)
                 got = model.forward(imgs).clone()
-                torch.cuda.synchronize()
-                assert torch.equal(ref, got), (dim, B, two, float((ref - got).abs().max()))
-    finally:
-        lib.vfm_debug_set_vit_gemm(-15, 1)
-        lib.vfm_debug_set_vit_gemm(-9, 0)            # the default policy: where its rounds of one workgroup per compute unit are full
+            torch.cuda.synchronize()
+            assert torch.equal(ref, got), (dim, B, two, float((ref - got).abs().max()))
 
 
 def test_vit_attention_with_keys_and_values_in_the_lds_equals_the_per_tile_kernel_bit_for_bit():
@@ -179,21 +167,17 @@ def test_vit_attention_with_keys_and_values_in_the_lds_equals_the_per_tile_kerne
     has one, two or three query tiles (9, 10, 11 tiles), one image and several."""
     from vfmreg import _lib
     from vfmreg import vit as V
-    lib = _lib.load()
-    try:
-        for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (384, 1, 1536, 1, 1200, 1600), (768, 1, 3072, 2, 560, 600),
-                                           (384, 12, 1536, 6, 1200, 1600)):
-            w = V.random_weights(seed=13, dim=dim, depth=depth, mlp=mlp)
-            imgs = torch.from_numpy(_smooth_images(np.random.default_rng(4), B, H, W)).cuda()
-            model = V.ViTS14(w, H, W, device="cuda")
-            lib.vfm_debug_set_vit_gemm(-7, 0)        # never
+    for (dim, depth, mlp, B, H, W) in ((384, 2, 1536, 5, 560, 700), (384, 1, 1536, 1, 1200, 1600), (768, 1, 3072, 2, 560, 600),
+                                       (384, 12, 1536, 6, 1200, 1600)):
+        w = V.random_weights(seed=13, dim=dim, depth=depth, mlp=mlp)
+        imgs = torch.from_numpy(_smooth_images(np.random.default_rng(4), B, H, W)).cuda()
+        model = V.ViTS14(w, H, W, device="cuda")
+        with _lib.using(_lib.Config().set("vit_att_lds_min", 0)):      # never
             per_tile = model.forward(imgs).clone()
-            lib.vfm_debug_set_vit_gemm(-7, 1)        # always
+        with _lib.using(_lib.Config().set("vit_att_lds_min", 1)):      # always
             shared = model.forward(imgs).clone()
-            torch.cuda.synchronize()
-            assert torch.equal(per_tile, shared), (dim, B, H, W, float((per_tile - shared).abs().max()))
-    finally:
-        lib.vfm_debug_set_vit_gemm(-7, 1)
+        torch.cuda.synchronize()
+        assert torch.equal(per_tile, shared), (dim, B, H, W, float((per_tile - shared).abs().max()))
 
 
 def test_vit_qkv_and_attention_in_one_workgroup_equal_the_two_kernels_bit_for_bit():
@@ -248,20 +232,16 @@ def test_vit_preprocessing_one_workgroup_per_patch_equals_the_per_unit_kernel_bi
     C3's resolution, NCLT's (padding tokens), an up-sampling resize (source smaller than 224 rows: taps at the right / bottom border)."""
     from vfmreg import _lib
     from vfmreg import vit as V
-    lib = _lib.load()
-    try:
-        for (B, H, W) in ((6, 1200, 1600), (2, 700, 820), (3, 150, 210)):
-            w = V.random_weights(seed=19, dim=384, depth=1, mlp=1536)
-            imgs = torch.from_numpy(_smooth_images(np.random.default_rng(6), B, max(H, 80), max(W, 80))[:, :H, :W].copy()).cuda()
-            model = V.ViTS14(w, H, W, device="cuda")
-            lib.vfm_debug_set_vit_gemm(-14, 0)
+    for (B, H, W) in ((6, 1200, 1600), (2, 700, 820), (3, 150, 210)):
+        w = V.random_weights(seed=19, dim=384, depth=1, mlp=1536)
+        imgs = torch.from_numpy(_smooth_images(np.random.default_rng(6), B, max(H, 80), max(W, 80))[:, :H, :W].copy()).cuda()
+        model = V.ViTS14(w, H, W, device="cuda")
+        with _lib.using(_lib.Config().set("vit_preprocess_patch", 0)):
             old = model.forward(imgs).clone()
-            lib.vfm_debug_set_vit_gemm(-14, 1)
+        with _lib.using(_lib.Config().set("vit_preprocess_patch", 1)):
             new = model.forward(imgs).clone()
-            torch.cuda.synchronize()
-            assert torch.equal(old, new), (B, H, W, float((old - new).abs().max()))
-    finally:
-        lib.vfm_debug_set_vit_gemm(-14, 1)
+        torch.cuda.synchronize()
+        assert torch.equal(old, new), (B, H, W, float((old - new).abs().max()))
 
 
 def test_vit_batch_as_two_half_batches_on_two_streams_equals_one_forward_bit_for_bit():

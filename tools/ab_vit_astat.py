@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""A/B of the token-stationary GEMM kernel for the QKV / fc1 products (vit_gemm_astat_kernel, vfm_debug_set_vit_gemm(-9, n)) against
+"""A/B of the token-stationary GEMM kernel for the QKV / fc1 products (vit_gemm_astat_kernel, "vit_astat_min") against
 the 128 x 128 LDS-tiled kernel: ViT-S/14 forward per batch size, identical bits required.  Output: profiles/r04_ab_vit_astat.txt."""
 import sys
 from pathlib import Path
@@ -12,11 +12,9 @@ sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
 from vfmreg import _lib  # noqa: E402
 from vfmreg import vit as V  # noqa: E402
 
-lib = _lib.load()
 rng = np.random.default_rng(0)
 NMAX = int(sys.argv[1]) if len(sys.argv) > 1 else 192
-if len(sys.argv) > 2:
-    lib.vfm_debug_set_vit_gemm(-10, int(sys.argv[2]))   # waves per workgroup of the token-stationary kernel
+NW = int(sys.argv[2]) if len(sys.argv) > 2 else 0   # waves per workgroup of the token-stationary kernel (0: the library's rule)
 all_imgs = torch.from_numpy(rng.integers(1, 255, (NMAX, 1200, 1600, 3), dtype=np.uint8)).cuda()
 tok = 337
 
@@ -43,8 +41,8 @@ for nimg in [n for n in [int(x) for x in os.environ.get("VFM_AB_IMAGES", "48,88,
     row = []
     ref = None
     for astat in (0, 1, 0, 1):
-        lib.vfm_debug_set_vit_gemm(-9, 1 if astat else -1)
-        out, ms = run(model, imgs)
+        with _lib.using(_lib.Config().set("vit_astat_nw", NW).set("vit_astat_min", 1 if astat else -1)):
+            out, ms = run(model, imgs)
         if ref is None:
             ref = out
         else:
@@ -53,4 +51,3 @@ for nimg in [n for n in [int(x) for x in os.environ.get("VFM_AB_IMAGES", "48,88,
     tp = (16 * model.patch_w + 1 + 31) // 32 * 32      # padded tokens per image
     print(f"{nimg:3d} images ({(nimg * tp // 32 + 3) // 4} groups of 128 token rows): " + " | ".join(row), flush=True)
     del model
-lib.vfm_debug_set_vit_gemm(-9, 0)   # back to the default policy

@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Where and when the workgroups of the token-stationary GEMM kernel run (its per-workgroup trace: start / end in 100 MHz ticks, XCC and
 HW_ID): the last such launch of a one-block ViT forward (fc1), per number of images."""
-import ctypes as C
 import sys
 from collections import Counter
 from pathlib import Path
@@ -14,20 +13,18 @@ sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
 from vfmreg import _lib  # noqa: E402
 from vfmreg import vit as V  # noqa: E402
 
-lib = _lib.load()
 rng = np.random.default_rng(0)
 all_imgs = torch.from_numpy(rng.integers(1, 255, (112, 1200, 1600, 3), dtype=np.uint8)).cuda()
 buf = torch.zeros((1024, 4), dtype=torch.int64, device="cuda")
-ptr = buf.data_ptr()
-lib.vfm_debug_set_vit_gemm(-11, C.c_int32(ptr & 0xffffffff).value)
-lib.vfm_debug_set_vit_gemm(-12, C.c_int32((ptr >> 32) & 0xffffffff).value)
-lib.vfm_debug_set_vit_gemm(-9, 1)
+# (one channel tile per wave: the two-tile kernel keeps no trace)
+cfg = _lib.Config().set("vit_trace_buffer", buf.data_ptr()).set("vit_astat_min", 1).set("vit_astat_two", 0)
 for nimg in [int(x) for x in (sys.argv[1:] or ["88", "93", "94", "96", "112"])]:
     model = V.ViTS14(V.random_weights(0, depth=int(__import__("os").environ.get("VFM_DEPTH", "1"))), 1200, 1600)
     imgs = all_imgs[:nimg]
-    for _ in range(3):
-        buf.zero_()
-        model.forward(imgs)
+    with _lib.using(cfg):
+        for _ in range(3):
+            buf.zero_()
+            model.forward(imgs)
     torch.cuda.synchronize()
     groups = (nimg * ((16 * model.patch_w + 1 + 31) // 32 * 32) // 32 + 3) // 4
     t = buf[:groups].cpu().numpy()

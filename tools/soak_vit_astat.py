@@ -15,7 +15,6 @@ from vfmreg import vit as V  # noqa: E402
 
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-lib = _lib.load()
 bad = 0
 for t in range(trials):
     dim = int(rng.choice([128, 256, 384, 384, 384, 512]))
@@ -28,14 +27,11 @@ for t in range(trials):
     model = V.ViTS14(w, H, W, device="cuda")
     outs = []
     for astat, lds in ((-1, 0), (-1, 1), (1, 1), (1, 0)):
-        lib.vfm_debug_set_vit_gemm(-9, astat)
-        lib.vfm_debug_set_vit_gemm(-5, lds)
-        outs.append(model.forward(imgs).clone())
+        with _lib.using(_lib.Config().set("vit_astat_min", astat).set("vit_lds_min_wg", lds)):
+            outs.append(model.forward(imgs).clone())
     torch.cuda.synchronize()
     ok = all(torch.equal(outs[0], o) for o in outs[1:]) and bool(torch.isfinite(outs[0]).all())
     bad += 0 if ok else 1
     print(f"trial {t}: dim {dim} depth {depth} {B} x {H}x{W} ({model.patch_w} patch columns) -> {'ok' if ok else 'MISMATCH'}", flush=True)
     del model, imgs, outs
-lib.vfm_debug_set_vit_gemm(-9, 0)
-lib.vfm_debug_set_vit_gemm(-5, 256)
 print(f"{trials} trials, {bad} mismatches")

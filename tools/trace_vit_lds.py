@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Inside the LDS-tiled residual GEMMs (proj, fc2) of a ViT forward at N images: per workgroup the time in the k loop and in the epilogue
 (residual read-modify-write, fp16 copy, LayerNorm statistics), from the kernel's own trace (start / end of loop / end, 100 MHz)."""
-import ctypes as C
 import os
 import sys
 from pathlib import Path
@@ -14,22 +13,20 @@ sys.path.insert(0, str(ROOT / "vfm-registration_amd"))
 from vfmreg import _lib  # noqa: E402
 from vfmreg import vit as V  # noqa: E402
 
-lib = _lib.load()
 rng = np.random.default_rng(0)
 nimg = int(sys.argv[1]) if len(sys.argv) > 1 else 90
 imgs = torch.from_numpy(rng.integers(1, 255, (nimg, 1200, 1600, 3), dtype=np.uint8)).cuda()
 buf = torch.zeros((2, 4096, 4), dtype=torch.int64, device="cuda")
-ptr = buf.data_ptr()
-lib.vfm_debug_set_vit_gemm(-11, C.c_int32(ptr & 0xffffffff).value)
-lib.vfm_debug_set_vit_gemm(-12, C.c_int32((ptr >> 32) & 0xffffffff).value)
+cfg = _lib.Config().set("vit_trace_buffer", buf.data_ptr())
 # depth 1: the LAST residual GEMM of the forward is the block's fc2; with VFM_ONLY_PROJ=1 the MLP is skipped by reading after a
 # forward whose weights make fc2 the traced launch anyway -- the two are told apart by the k-steps the kernel records
 if os.environ.get("VFM_ONLY_PROJ") == "1":   # the proj launch instead of fc2 (both are the LDS-tiled residual kernel)
-    _lib.thread_config().set("vit_trace_fused", 2)
+    cfg.set("vit_trace_fused", 2)
 model = V.ViTS14(V.random_weights(0, depth=1), 1200, 1600)
-for _ in range(3):
-    buf.zero_()
-    model.forward(imgs)
+with _lib.using(cfg):
+    for _ in range(3):
+        buf.zero_()
+        model.forward(imgs)
 torch.cuda.synchronize()
 both = buf.cpu().numpy()
 live = both[0][:, 0] > 0

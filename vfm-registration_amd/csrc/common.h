@@ -40,17 +40,41 @@ int vfm_fail(int code, const char *fmt, ...);
         if (rc__ != VFM_OK) return rc__; \
     } while (0)
 
-// compute units of the current device, asked for once per device (256 where the runtime cannot say)
-static inline int vfm_compute_units() {
+// compute units of device `dev` / of the current device, asked for once per device (256 where the runtime cannot say)
+static inline int vfm_compute_units_of(int dev) {
     static std::atomic<int> cus[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     int n = cus[dev & 63].load(std::memory_order_relaxed);
     if (n == 0) {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         cus[dev & 63].store(n, std::memory_order_relaxed);
     }
     return n;
+}
+static inline int vfm_compute_units() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return vfm_compute_units_of(dev);
+}
+
+// hipFuncSetAttribute is per device: remember which devices have been configured (one bit each)
+inline bool attr_done(unsigned long long mask) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return (mask >> (dev & 63)) & 1ull;
+}
+inline void attr_mark(unsigned long long& mask) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    mask |= 1ull << (dev & 63);
+}
+// ... and the whole of it for a kernel that may be launched from several host threads at once: `bytes` of dynamic LDS allowed to `kernel`
+// on device `dev` (the current one), once per device on the kernel's own atomic mask
+static inline int vfm_allow_dynamic_lds(const void* kernel, int bytes, int dev, std::atomic<unsigned long long>& done) {
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_relaxed) & bit) return VFM_OK;
+    VFM_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_relaxed);
+    return VFM_OK;
 }
 
 static inline size_t vfm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -43,7 +43,9 @@ const Field k_fields[] = {
     {"voxel_trace", &VfmConfig::voxel_trace},        {"voxel_grid_ppt", &VfmConfig::voxel_grid_ppt},
 };
 
-// the code tables of round 1 - 5's vfm_debug_set_coarse_variant / _vit_gemm / _voxel_small, on a config
+const char* const k_trace_buffer = "vit_trace_buffer";   // the one key whose value is a device pointer: all 64 bits
+
+// the code tables of round 1 - 5's vfm_debug_set_coarse_variant / _voxel_small, on a config
 void set_coarse_variant(VfmConfig& c, int v) {
     if (v == 60 || v == 61) { c.rescan_rows = v == 61 ? 1 : 0; return; }
     if (v == 50 || v == 51) { c.finish_short = v == 51 ? 1 : 0; return; }
@@ -55,30 +57,6 @@ void set_coarse_variant(VfmConfig& c, int v) {
     c.select_variant = v == 20 ? 1 : (v == 21 ? 2 : 0);
     if (v == 20 || v == 21) v = 0;
     c.coarse_qsets = v;
-}
-void set_vit_gemm(VfmConfig& c, int narrow, int wide) {
-    switch (narrow) {
-        case -3: case -4: c.vit_xcd = narrow == -3 ? 1 : 0; return;
-        case -5: c.vit_lds_min_wg = wide; return;
-        case -6: c.vit_lds_shape = wide; return;
-        case -7: c.vit_att_lds_min = wide; return;
-        case -8: c.vit_wpw = wide; return;
-        case -9: c.vit_astat_min = wide; return;
-        case -10: c.vit_astat_nw = wide; return;
-        case -11: case -12: {
-            unsigned long long v = (unsigned long long)(uintptr_t)c.vit_astat_dbg;
-            v = narrow == -11 ? ((v & 0xffffffff00000000ull) | (unsigned)wide) : ((v & 0xffffffffull) | ((unsigned long long)(unsigned)wide << 32));
-            c.vit_astat_dbg = reinterpret_cast<unsigned long long*>((uintptr_t)v);
-            return;
-        }
-        case -14: c.vit_preprocess_patch = wide; return;
-        case -15: c.vit_astat_two = wide; return;
-        case -16: c.vit_hot_a = wide; return;
-        case -17: c.vit_wide_tile = wide; return;
-        default:
-            c.vit_cfg_narrow = narrow ? narrow : 108;
-            c.vit_cfg_wide = wide ? wide : 108;
-    }
 }
 void set_voxel_small(VfmConfig& c, int on) {
     if (on == 2 || on == 3) c.voxel_replay2 = on == 3;
@@ -112,7 +90,7 @@ VFM_EXPORT int vfm_config_set(vfm_config_t* cfg, const char* key, int64_t value)
         return vfm_fail(VFM_EINVAL, "config_set: rescore_block %lld (a workgroup of match_rescore_kernel owns 64 or 256 queries)", (long long)value);
     if (!strcmp(key, "coarse_variant")) { set_coarse_variant(cfg->c, (int)value); return VFM_OK; }
     if (!strcmp(key, "voxel_small")) { set_voxel_small(cfg->c, (int)value); return VFM_OK; }
-    if (!strcmp(key, "vit_gemm")) { set_vit_gemm(cfg->c, (int)(value >> 32), (int)(int32_t)(uint32_t)(value & 0xffffffffll)); return VFM_OK; }
+    if (!strcmp(key, k_trace_buffer)) { cfg->c.vit_astat_dbg = reinterpret_cast<unsigned long long*>((uintptr_t)value); return VFM_OK; }
     for (const Field& f : k_fields)
         if (!strcmp(key, f.name)) {
             cfg->c.*(f.p) = (int)value;
@@ -123,6 +101,7 @@ VFM_EXPORT int vfm_config_set(vfm_config_t* cfg, const char* key, int64_t value)
 VFM_EXPORT int vfm_config_get(const vfm_config_t* cfg, const char* key, int64_t* value) {
     VFM_CHECK_ARG(key && value, "config_get: null pointer");
     const VfmConfig& c = cfg ? cfg->c : vfm_cfg();   // NULL: what the calling thread's entry points would read now
+    if (!strcmp(key, k_trace_buffer)) { *value = (int64_t)(uintptr_t)c.vit_astat_dbg; return VFM_OK; }
     for (const Field& f : k_fields)
         if (!strcmp(key, f.name)) {
             *value = c.*(f.p);

@@ -31,13 +31,14 @@ struct VfmConfig {
     // ---- RANSAC (ransac.hip)
     int ransac_exact_only = 0;   // 1 = every hypothesis scored in fp64 (no bounds)
     int ransac_fused = 2;        // 2 (default since round 6) = 8 launches, 1 = the 5-launch chain (slower: its one-workgroup gather), 0 = round 5's 11
-    // ---- ViT (vit.hip): "vit_gemm" (narrow, wide) codes, see include/vfmreg.h
+    // ---- ViT (vit_plan.h resolves them, once per forward): one key per field, see include/vfmreg_debug.h
     int vit_preprocess_patch = 1, vit_xcd = 1, vit_cfg_narrow = 108, vit_cfg_wide = 108, vit_wpw = 0, vit_hot_a = 0, vit_wide_tile = 0,
         vit_lds_shape = 23, vit_att_lds_min = 1, vit_lds_min_wg = 256, vit_astat_min = 0, vit_astat_two = 1, vit_astat_nw = 0,
-        vit_trace_fused = 0,   // (tools) whose trace buffer it is: 0 the GEMM kernels', 1 vit_qkv_attention_kernel's, 2 the proj launches' of the LDS-tiled kernel
+        vit_trace_fused = 0,   // (tools) the ONE launch of a block that gets the trace buffer: 0 the token-stationary fc1, or else the LDS-tiled fc2;
+                               // 1 vit_qkv_attention_kernel; 2 the LDS-tiled proj; 3 vit_mlp_kernel
         vit_fused_mlp = 0,     // fc1 -> GELU -> fc2 of 128 tokens in one workgroup: n > 0 from n images on, -1 never, 0 vfm_vit_forward's policy
         vit_fused_qkv = 0;   // QKV + attention of an (image, head) in one workgroup: n > 0 from n images on, -1 never, 0 vfm_vit_forward's policy
-    unsigned long long* vit_astat_dbg = nullptr;   // (tools) device buffer of the token-stationary kernel's placement trace
+    unsigned long long* vit_astat_dbg = nullptr;   // "vit_trace_buffer" (tools): device buffer of the traced launch's per-workgroup stamps
     // ---- voxel containers (voxel.hip): "voxel_small" codes
     int voxel_replay2 = 1, voxel_small = 1, voxel_trace = 0, voxel_grid_ppt = 0;
 };

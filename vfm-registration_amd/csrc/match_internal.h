@@ -535,18 +535,6 @@ inline size_t search_zero_bytes(int64_t n, int64_t m) {
            (size_t)npad * BIN_CNT_STRIDE * sizeof(unsigned) + (size_t)npad * sizeof(unsigned long long);
 }
 
-// hipFuncSetAttribute is per device: remember which devices have been configured (one bit each)
-inline bool attr_done(unsigned long long mask) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return (mask >> (dev & 63)) & 1ull;
-}
-inline void attr_mark(unsigned long long& mask) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    mask |= 1ull << (dev & 63);
-}
-
 // Descriptor rows as the caller stores them (round 5, BASELINE.json configs[4] "fp16 descriptor storage"): fp32 -- the reference's layout
 // behind VoxelHashMap.cpp:469-482 -- or fp16 (VFM_ROWS_F16: half the bytes of a resident map and of the preparation's read), every
 // element widened to fp32 as it is loaded; from there on the arithmetic is the fp32 path's, operation for operation -- the oracle of an

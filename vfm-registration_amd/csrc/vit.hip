@@ -24,7 +24,9 @@
 // Floating point => tolerance parity (tests state it); weights are seeded-random in tests/bench.
 #include <atomic>
 #include "common.h"
+#include "vit_plan.h"
 
+#include <string.h>
 #include <type_traits>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -398,7 +400,7 @@ __device__ __forceinline__ void ln_stats_load(const GemmArgs& g, int m, float& l
     ln_a = __builtin_amdgcn_rsqf(var + 1e-6f);   // (the argument is >= 1e-6: no denormal guard)
     ln_nb = -(ln_a * mean);
 }
-// NT: the fp16 outputs leave with non-temporal stores (vfm_debug_set_vit_gemm(-13, 1), token-stationary kernel only: A/B)
+// NT: the fp16 outputs leave with non-temporal stores ("vit_astat_nw" 112, token-stationary kernel only: A/B)
 __device__ __forceinline__ void store_half4(void* p, half4 v, bool nt) {
     if (nt) {
         const uint2 u = *reinterpret_cast<const uint2*>(&v);
@@ -519,7 +521,9 @@ __device__ __forceinline__ unsigned pack_f16x2(float a, float b) {
 #define VFM_VIT_PART 0
 #endif
 }  // namespace
-extern "C" __attribute__((visibility("hidden"))) int vfm_vit_launch_mlp_(const void* fc1_args, const void* fc2_args, void* stream);
+// (part 0 -> part 1) vit_mlp_kernel on `grid` workgroups with the two GEMMs' GemmArgs; dev: the current device
+extern "C" __attribute__((visibility("hidden"))) int vfm_vit_launch_mlp_(const void* fc1_args, const void* fc2_args, int grid, int lds_bytes, int dev,
+                                                                        void* stream);
 namespace {
 #if VFM_VIT_PART == 0
 
@@ -1727,158 +1731,78 @@ inline VitWs carve_vit(void* p, const Dims& d) {
 }
 
 
-template <int EPI, int NT, int PF>
-int launch_gemm_cfg(const GemmArgs& g, hipStream_t st) {
-    const int waves = (g.M / 32) * (g.N / (32 * NT));
-    // waves per workgroup: one -- the waves share nothing, and single waves are spread over more compute units (one scan, N = 384: 648 waves
-    // were 168 workgroups); tools/ab_vit_wpw.py: 6 / 12 / 24 images 0.62 / 0.865 / 1.444 ms with four waves per workgroup, 0.62 / 0.845 / 1.425 with one
-    const int wpw = vfm_cfg().vit_wpw > 0 ? vfm_cfg().vit_wpw : 1;
-    // xcd_map: every XCD gets ceil(tiles / 8) token tiles' worth of workgroups
-    const int grid = g.xcd_map ? 8 * ceil_div(ceil_div(g.M / 32, 8) * (g.N / (32 * NT)), wpw) : ceil_div(waves, wpw);
-    hipLaunchKernelGGL((vit_gemm_kernel<EPI, NT, PF>), dim3(grid), dim3(64 * wpw), 0, st, g);
-    VFM_CHECK_LAUNCH("vit_gemm_kernel");
-    return VFM_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// The launch table: one row per kernel instantiation a forward can launch, indexed by VitInst (vit_plan.h).  WHICH row a stage takes, with
+// what grid, is resolve_vit's business; here a row is launched.  A kernel that needs more dynamic LDS than the runtime grants by default
+// is allowed it once per device, on the row's own mask (atomic: vfm_vit_forward may run on two host threads at once -- ViTS14.SPLIT_FROM).
+// ---------------------------------------------------------------------------------------------
+using namespace vitplan;
+static_assert((int)EPI_PATCH == VIT_EPI_PATCH && (int)EPI_QKV == VIT_EPI_QKV && (int)EPI_RESID == VIT_EPI_RESID && (int)EPI_GELU == VIT_EPI_GELU,
+              "vit_plan.h counts the epilogues as enum Epi does");
 
-// Wave tile (NT x 32 channels) and prefetch depth (PF k-steps).  Round 2 measurements on 6 x 1200 x 1600 (tools/ab_vit.py,
-// profiles/r02_pmc_vit.json): a wave lives ~2.5 us inside kernels that take 10-17 us -- the forward is bound by the
-// ~5 us floor of each of its 87 launches, not by L2 latency or bandwidth: PF = 8 / 16 / 24 make no difference, 32-channel
-// tiles everywhere (twice the waves) give 0.76 instead of 0.82 ms, 64 x 64 wave tiles and row-complete workgroups with the
-// LayerNorm fused into the epilogue (63 launches, but 66 workgroups per GEMM) gave 1.04 ms and were removed again.
-template <int EPI>
-int launch_gemm(const GemmArgs& g, hipStream_t st) {
-    if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {
-        const int groups = ceil_div(g.M / 32, 4);
-        const int nw = vfm_cfg().vit_astat_nw == 112 ? 112 : (vfm_cfg().vit_astat_nw > 0 && (g.N / 32) % vfm_cfg().vit_astat_nw == 0 ? vfm_cfg().vit_astat_nw : 12);
-        // One workgroup per compute unit: the kernel pays when its rounds are full.  vfm_cfg().vit_astat_min > 0: from that many groups on whatever
-        // the fill (tools); 0 (default): when the last round of `ncu` workgroups is at least three quarters full and there is at least one
-        // such round -- 69 ... 93 images of 1200 x 1600 at a time on 256 compute units (tools/ab_vit_astat.py: 48 images 2.19 -> 2.30 ms,
-        // 84: 3.35 -> 3.22, 93: 3.60 -> 3.49, 96 = 264 groups, eight of them alone in a second round: 3.95 -> 4.58)
-        static std::atomic<int> ncu{0};   // (atomics: vfm_vit_forward may run on two host threads at once -- ViTS14.SPLIT_FROM)
-        if (ncu == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            (void)hipGetDevice(&dev);
-            ncu = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
-        const int last_round = groups % ncu;
-        const bool full_rounds = groups >= (3 * ncu) / 4 && (last_round == 0 || 4 * last_round >= 3 * ncu);
-        const bool want = vfm_cfg().vit_astat_min > 0 ? groups >= vfm_cfg().vit_astat_min : (vfm_cfg().vit_astat_min == 0 && full_rounds);
-        if (want && 4 * g.KS * 1024 <= 128 * 1024 && (nw == 112 || (g.N / 32) % nw == 0)) {
-#define VIT_ASTAT(NW)                                                                                                                \
-    do {                                                                                                                             \
-        static std::atomic<unsigned long long> attr_set{0ull};                                                                                   \
-        int dev = 0;                                                                                                                 \
-        (void)hipGetDevice(&dev);                                                                                                    \
-        if (!((attr_set >> (dev & 63)) & 1ull)) {                                                                                    \
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_astat_kernel<EPI, NW, 6>),                     \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));                              \
-            attr_set |= 1ull << (dev & 63);                                                                                          \
-        }                                                                                                                            \
-        GemmArgs ga = g;                                                                                                             \
-        ga.dbg = vfm_cfg().vit_trace_fused ? nullptr : vfm_cfg().vit_astat_dbg;                                                                                                    \
-        hipLaunchKernelGGL((vit_gemm_astat_kernel<EPI, NW, 6>), dim3(groups), dim3(64 * NW), 4 * g.KS * 1024, st, ga);               \
-    } while (0)
-            if (vfm_cfg().vit_astat_two && (g.N / 64) >= 8 && g.N % 64 == 0 && g.KS % 4 == 0) {   // two channel tiles per wave, eight waves (round 5)
-                static std::atomic<unsigned long long> attr2{0ull};
-                int dev2 = 0;
-                (void)hipGetDevice(&dev2);
-                if (!((attr2 >> (dev2 & 63)) & 1ull)) {
-                    VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_astat2_kernel<EPI, 8, 4>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    attr2 |= 1ull << (dev2 & 63);
-                }
-                hipLaunchKernelGGL((vit_gemm_astat2_kernel<EPI, 8, 4>), dim3(groups), dim3(512), 4 * g.KS * 1024, st, g);
-                VFM_CHECK_LAUNCH("vit_gemm_astat2_kernel");
-                return VFM_OK;
-            }
-            switch (nw) {
-                case 6: VIT_ASTAT(6); break;
-                case 112: {   // (A/B) twelve waves, non-temporal output stores
-                    static std::atomic<unsigned long long> attr_set2{0ull};
-                    int dev = 0;
-                    (void)hipGetDevice(&dev);
-                    if (!((attr_set2 >> (dev & 63)) & 1ull)) {
-                        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_astat_kernel<EPI, 12, 6, true>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                        attr_set2 |= 1ull << (dev & 63);
-                    }
-                    GemmArgs ga = g;
-                    ga.dbg = vfm_cfg().vit_trace_fused ? nullptr : vfm_cfg().vit_astat_dbg;
-                    hipLaunchKernelGGL((vit_gemm_astat_kernel<EPI, 12, 6, true>), dim3(groups), dim3(768), 4 * g.KS * 1024, st, ga);
-                } break;
-                case 8: VIT_ASTAT(8); break;
-                case 16: VIT_ASTAT(16); break;
-                default: VIT_ASTAT(12); break;
-            }
-#undef VIT_ASTAT
-            VFM_CHECK_LAUNCH("vit_gemm_astat_kernel");
-            return VFM_OK;
+struct VitKernel {
+    const void* fn = nullptr;   // every GEMM kernel takes one GemmArgs
+    int max_lds = 0;            // the dynamic LDS to allow it (0: it asks for none)
+    std::string name;           // spelled from the template arguments (vit_inst_name)
+    std::atomic<unsigned long long> lds_allowed{0ull};
+};
+struct VitTable {
+    VitKernel k[VIT_INST_COUNT];
+
+    template <typename K>
+    void set(int inst, K* kernel, int max_lds = 0) {
+        k[inst].fn = reinterpret_cast<const void*>(kernel);
+        k[inst].max_lds = max_lds;
+    }
+    template <int EPI, int KB, int NS>
+    void lds_shape(int index) {   // ... and its twin that keeps a trace
+        set(VIT_GEMM + 4 * (VIT_LDS + 2 * index) + EPI, &vit_gemm_lds_kernel<EPI, KB, NS>, NS * 8 * KB * 1024);
+        set(VIT_GEMM + 4 * (VIT_LDS + 2 * index + 1) + EPI, &vit_gemm_lds_kernel<EPI, KB, NS, 1, 4, true>, NS * 8 * KB * 1024);
+    }
+    template <int EPI>
+    void gemms() {
+        set(VIT_GEMM + 4 * VIT_DIRECT_1_8 + EPI, &vit_gemm_kernel<EPI, 1, 8>);
+        set(VIT_GEMM + 4 * VIT_DIRECT_1_16 + EPI, &vit_gemm_kernel<EPI, 1, 16>);
+        set(VIT_GEMM + 4 * VIT_DIRECT_2_8 + EPI, &vit_gemm_kernel<EPI, 2, 8>);
+        lds_shape<EPI, 2, 3>(0); lds_shape<EPI, 2, 4>(1); lds_shape<EPI, 2, 5>(2);
+        lds_shape<EPI, 2, 6>(3); lds_shape<EPI, 4, 2>(4); lds_shape<EPI, 4, 3>(5);
+        set(VIT_GEMM + 4 * VIT_LDS_WIDE + EPI, &vit_gemm_lds_kernel<EPI, 2, 4, 3, 8>, 4 * 16 * 2 * 1024);
+        set(VIT_GEMM + 4 * (VIT_LDS_WIDE + 1) + EPI, &vit_gemm_lds_kernel<EPI, 2, 4, 3, 8, true>, 4 * 16 * 2 * 1024);
+        if constexpr (EPI == EPI_QKV || EPI == EPI_GELU) {   // 128 token rows of up to 512 channels in the LDS
+            set(VIT_GEMM + 4 * VIT_ASTAT_6 + EPI, &vit_gemm_astat_kernel<EPI, 6, 6>, 128 * 1024);
+            set(VIT_GEMM + 4 * VIT_ASTAT_8 + EPI, &vit_gemm_astat_kernel<EPI, 8, 6>, 128 * 1024);
+            set(VIT_GEMM + 4 * VIT_ASTAT_12 + EPI, &vit_gemm_astat_kernel<EPI, 12, 6>, 128 * 1024);
+            set(VIT_GEMM + 4 * VIT_ASTAT_16 + EPI, &vit_gemm_astat_kernel<EPI, 16, 6>, 128 * 1024);
+            set(VIT_GEMM + 4 * VIT_ASTAT_12_NT + EPI, &vit_gemm_astat_kernel<EPI, 12, 6, true>, 128 * 1024);
+            set(VIT_GEMM + 4 * VIT_ASTAT2 + EPI, &vit_gemm_astat2_kernel<EPI, 8, 4>, 128 * 1024);
         }
     }
-    if (g.N % 128 == 0 && vfm_cfg().vit_lds_min_wg > 0 && g.KS % (vfm_cfg().vit_lds_shape / 10 == 4 ? 4 : 2) == 0) {   // (whole stages of 2 or 4 k-steps)
-        const int wgs = ceil_div(g.M / 32, 4) * (g.N / 128);
-        if (wgs >= vfm_cfg().vit_lds_min_wg) {
-            GemmArgs gl = g;
-            gl.hot_a = vfm_cfg().vit_hot_a;
-            gl.dbg = EPI == EPI_RESID && (vfm_cfg().vit_trace_fused == 0 || (vfm_cfg().vit_trace_fused == 2 && g.KS * 16 == g.D)) ? vfm_cfg().vit_astat_dbg : nullptr;   // (2: the proj launches only)   // (the trace buffer serves whichever kernel a tool looks at)
-            if (EPI == EPI_RESID && g.N == 384 && vfm_cfg().vit_wide_tile && g.KS % 2 == 0) {   // one workgroup per 128 tokens x all 384 channels (NG = 3)
-                const int gridw = 8 * ceil_div(ceil_div(g.M / 32, 4), 8);
-                constexpr int ldsw = 4 * 16 * 2 * 1024;   // NS = 4 stages of (4 + 12) x KB = 2 KiB: 128 KiB
-                static std::atomic<unsigned long long> attr_w{0ull};
-                int devw = 0;
-                (void)hipGetDevice(&devw);
-                if (!((attr_w >> (devw & 63)) & 1ull)) {
-                    VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_lds_kernel<EPI, 2, 4, 3, 8>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, ldsw));
-                    attr_w |= 1ull << (devw & 63);
-                }
-                if (gl.dbg) {
-                    VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_lds_kernel<EPI, 2, 4, 3, 8, true>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, ldsw));
-                    hipLaunchKernelGGL((vit_gemm_lds_kernel<EPI, 2, 4, 3, 8, true>), dim3(gridw), dim3(512), ldsw, st, gl);
-                } else
-                hipLaunchKernelGGL((vit_gemm_lds_kernel<EPI, 2, 4, 3, 8>), dim3(gridw), dim3(512), ldsw, st, gl);
-                VFM_CHECK_LAUNCH("vit_gemm_lds_kernel (128 x 384)");
-                return VFM_OK;
-            }
-            const int grid = 8 * ceil_div(ceil_div(g.M / 32, 4), 8) * (g.N / 128);   // every XCD: ceil(groups / 8) token groups x channel groups
-#define VIT_LDS(KB, NS)                                                                                                              \
-    do {                                                                                                                             \
-        static std::atomic<unsigned long long> attr_set{0ull};                                                                                   \
-        int dev = 0;                                                                                                                 \
-        (void)hipGetDevice(&dev);                                                                                                    \
-        if (!((attr_set >> (dev & 63)) & 1ull)) {                                                                                    \
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_lds_kernel<EPI, KB, NS>),                      \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, NS * 8 * KB * 1024));                      \
-            attr_set |= 1ull << (dev & 63);                                                                                          \
-        }                                                                                                                            \
-        if (gl.dbg) {                                                                                                                \
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_gemm_lds_kernel<EPI, KB, NS, 1, 4, true>),          \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, NS * 8 * KB * 1024));                      \
-            hipLaunchKernelGGL((vit_gemm_lds_kernel<EPI, KB, NS, 1, 4, true>), dim3(grid), dim3(256), NS * 8 * KB * 1024, st, gl);   \
-        } else                                                                                                                       \
-        hipLaunchKernelGGL((vit_gemm_lds_kernel<EPI, KB, NS>), dim3(grid), dim3(256), NS * 8 * KB * 1024, st, gl);                    \
-    } while (0)
-            switch (vfm_cfg().vit_lds_shape) {
-                case 42: VIT_LDS(4, 2); break;
-                case 43: VIT_LDS(4, 3); break;
-                case 24: VIT_LDS(2, 4); break;
-                case 25: VIT_LDS(2, 5); break;
-                case 26: VIT_LDS(2, 6); break;
-                default: VIT_LDS(2, 3); break;
-            }
-#undef VIT_LDS
-            VFM_CHECK_LAUNCH("vit_gemm_lds_kernel");
-            return VFM_OK;
-        }
+    template <int NKT>
+    void token_tiles() {   // the three families instantiated per token-tile count: NKT ... 16
+        set(VIT_ATT + NKT - 1, &vit_attention_kernel<NKT>);
+        set(VIT_ATT_LDS + NKT - 1, &vit_attention_lds_kernel<NKT>, NKT * 4096 + 16384);
+        if constexpr (NKT <= 12) set(VIT_FQA + NKT - 1, &vit_qkv_attention_kernel<NKT>, 48 * 1024 + 2 * NKT * 4096 + NKT * 32 * 8);
+        if constexpr (NKT < 16) token_tiles<NKT + 1>();
     }
-    const int cfg = g.N <= 512 ? vfm_cfg().vit_cfg_narrow : vfm_cfg().vit_cfg_wide;
-    switch (cfg) {
-        case 116: return launch_gemm_cfg<EPI, 1, 16>(g, st);
-        case 208: return launch_gemm_cfg<EPI, 2, 8>(g, st);
-        default: return launch_gemm_cfg<EPI, 1, 8>(g, st);
+    VitTable() {
+        set(VIT_PRE_UNIT, &vit_preprocess_kernel);
+        set(VIT_PRE_PATCH, &vit_preprocess_patch_kernel);
+        gemms<EPI_PATCH>(); gemms<EPI_QKV>(); gemms<EPI_RESID>(); gemms<EPI_GELU>();
+        token_tiles<1>();
+        // (VIT_MLP: vit_mlp_kernel is in the file's other compile part, behind vfm_vit_launch_mlp_)
+        for (int i = 0; i < VIT_INST_COUNT; ++i) k[i].name = vit_inst_name(i);
     }
+};
+
+// args: the addresses of the kernel's arguments, in order
+int launch_vit(const VitLaunch& l, void** args, int dev, hipStream_t st) {
+    static VitTable table;
+    VitKernel& k = table.k[l.inst];
+    if (!k.fn) return vfm_fail(VFM_EINVAL, "vit: no kernel %s", k.name.c_str());
+    if (k.max_lds) VFM_TRY(vfm_allow_dynamic_lds(k.fn, k.max_lds, dev, k.lds_allowed));
+    (void)hipLaunchKernel(k.fn, dim3((unsigned)l.grid), dim3((unsigned)l.block), args, (size_t)l.lds_bytes, st);
+    VFM_CHECK_LAUNCH(k.name.c_str());
+    return VFM_OK;
 }
 
 }  // namespace
@@ -1919,18 +1843,27 @@ VFM_EXPORT int vfm_debug_vit_workspace_layout(const vfm_vit_config* cfg, int B, 
     return VFM_OK;
 }
 
+// (include/vfmreg_debug.h) what vfm_vit_forward would launch for B images W pixels wide under the calling thread's policy: resolve_vit's
+// plan as one line of text
+VFM_EXPORT int vfm_debug_vit_plan(const vfm_vit_config* cfg, int B, int W, int compute_units, char* buf_host, int cap) {
+    VFM_CHECK_ARG(cfg && buf_host && cap > 0 && compute_units >= 0, "vit_plan: bad argument");
+    VitPlan plan;
+    VFM_TRY(resolve_vit(*cfg, B, W, vfm_cfg(), compute_units ? compute_units : vfm_compute_units(), plan));
+    const std::string line = vit_plan_line(plan);
+    if ((size_t)cap <= line.size()) return vfm_fail(VFM_EINVAL, "vit_plan: the buffer holds %d bytes, the answer needs %zu", cap, line.size() + 1);
+    memcpy(buf_host, line.c_str(), line.size() + 1);
+    return VFM_OK;
+}
+
 VFM_EXPORT int vfm_vit_forward(const vfm_vit_config* cfg, const void* weights, const uint8_t* img, int B, int H, int W,
                                float* tokens_out, void* ws, size_t ws_bytes, vfm_stream_t stream) {
     VFM_CHECK_ARG(cfg && weights && img && tokens_out && ws, "vit: null pointer");
-    VFM_CHECK_ARG(cfg->dim % 64 == 0 && cfg->dim == cfg->heads * 64 && cfg->dim <= 1024, "vit: dim must be heads*64 and <= 1024");
-    VFM_CHECK_ARG(cfg->mlp_dim % 64 == 0 && cfg->depth >= 1 && cfg->depth <= 64, "vit: bad mlp_dim / depth");
-    VFM_CHECK_ARG(cfg->patch == 14 && cfg->patch_h >= 1 && cfg->patch_w >= 1 && B >= 1, "vit: bad patch grid");
-    const Dims d = make_dims(cfg, B, H, W);
-    VFM_CHECK_ARG(d.Tp / 32 <= 16, "vit: at most 512 tokens per image supported (got %d)", d.T);
-    // (the GEMM epilogues address every activation buffer with 32-bit byte offsets and find a token tile's image by a 20-bit reciprocal)
-    VFM_CHECK_ARG((uint64_t)d.M * (uint64_t)(d.mlp > 3 * d.D ? d.mlp : 3 * d.D) * 4u < (1ull << 32) && d.M / 32 < 65536 &&
-                  (uint64_t)(d.M / 32) * ((1u << 20) / (unsigned)(d.Tp / 32) + 1u) < (1ull << 32),   // (the reciprocal's product is 32-bit in the kernels)
-                  "vit: batch of %d images too large for one call", B);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const VfmConfig& policy = vfm_cfg();
+    VitPlan plan;
+    VFM_TRY(resolve_vit(*cfg, B, W, policy, vfm_compute_units_of(dev), plan));
+    Dims d = make_dims(cfg, B, H, W);
     if (ws_bytes < carve_vit(nullptr, d).bytes) return vfm_fail(VFM_EWORKSPACE, "vit: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const Layout L = make_layout(cfg);
@@ -1938,136 +1871,66 @@ VFM_EXPORT int vfm_vit_forward(const vfm_vit_config* cfg, const void* weights, c
     auto f32 = [&](int seg) { return reinterpret_cast<const float*>(wb + L.off[seg]); };
     auto f16 = [&](int seg) { return reinterpret_cast<const uint4*>(wb + L.off[seg]); };
     VitWs w = carve_vit(ws, d);
+    // a GEMM stage: the launch gets its OWN arguments -- the trace buffer if the plan gives it to this launch, null otherwise
+    const auto traced = [&](const VitLaunch& l, GemmArgs ga) {
+        ga.dbg = l.trace ? policy.vit_astat_dbg : nullptr;
+        ga.hot_a = l.hot_a;
+        return ga;
+    };
+    const auto gemm = [&](int stage, const GemmArgs& g) {
+        GemmArgs ga = traced(plan.st[stage], g);
+        void* args[] = {&ga};
+        return launch_vit(plan.st[stage], args, dev, st);
+    };
 
-    // padded token rows stay exactly zero in the residual stream
     {
-        const int64_t total = (int64_t)d.M * (d.KP / 16) * 2;
-        if (vfm_cfg().vit_preprocess_patch && d.KP <= 640 && d.W >= 2)
-            hipLaunchKernelGGL(vit_preprocess_patch_kernel, dim3((unsigned)d.M), dim3(256), 0, st, img, d, w.a);
-        else
-            hipLaunchKernelGGL(vit_preprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, img, d, w.a);
-        VFM_CHECK_LAUNCH("vit_preprocess_kernel");
+        void* args[] = {&img, &d, &w.a};
+        VFM_TRY(launch_vit(plan.st[VIT_ST_PRE], args, dev, st));
     }
     GemmArgs g{};
     g.T = d.T; g.Tp = d.Tp; g.D = d.D; g.heads = d.heads; g.M = d.M;
     g.x = w.x; g.q = w.q; g.k = w.k; g.vt = w.vt;
     g.xh = w.xh; g.stats = w.stats; g.invD = 1.0f / (float)d.D; g.qt_magic = (1u << 20) / (unsigned)(d.Tp / 32) + 1u;
-    g.xcd_map = vfm_cfg().vit_xcd;
-    const int att_grid = vfm_cfg().vit_xcd ? 8 * ceil_div(ceil_div(d.M / 32, 8) * d.heads, 4) : ceil_div(d.B * d.heads * (d.Tp / 32), 4);
+    g.xcd_map = plan.xcd_map;
     // patch embedding (+ cls token + position embedding)
     g.A = reinterpret_cast<const uint4*>(w.a); g.W = f16(SEG_PATCH_W); g.bias = f32(SEG_PATCH_B);
     g.N = d.D; g.KS = d.KP / 16; g.clspos = f32(SEG_CLS_POS);
-    int rc = launch_gemm<EPI_PATCH>(g, st);
-    if (rc) return rc;
-    const int att_work = d.B * d.heads * (d.Tp / 32);
-    // K / V^T of an (image, head) shared by four query tiles through the LDS from vfm_cfg().vit_att_lds_min images on (0: never): at one scan the
-    // one-wave-per-tile kernel's 396 waves spread over the chip win, at batches the shared form reads a quarter of the L2 bytes
-    const bool att_lds = vfm_cfg().vit_att_lds_min > 0 && d.B >= vfm_cfg().vit_att_lds_min && d.Tp / 32 <= 16;
-    // QKV + attention per (image, head) in one workgroup (vit_qkv_attention_kernel).  vfm_cfg().vit_fused_qkv: n > 0 from n images on, -1 never,
-    // 0 (default) the policy: one workgroup per compute unit, B x heads of them, an eighth per XCD in rounds of 32 -- from 24 images on
-    // (below, the two kernels' many small workgroups fill the chip better) unless a second round would be less than a quarter full
-    // (profiles/r06_ab_vit_fused_qkv_sweep.txt: 42 images -12.6 %, 44: +1.7 %, 48: +0.2 %, 54: -2.1 %, 84: -11 %, 86: -3.7 %; three
-    // rounds and more: -4 ... -9 % wherever the last one ends)
-    bool fused_qkv = false;
-    if (d.D == 384 && d.Tp / 32 <= 12) {
-        const int per_xcd = ceil_div(d.B * d.heads, 8), rounds = ceil_div(per_xcd, 32), last = per_xcd - 32 * (rounds - 1);
-        const int k = vfm_cfg().vit_fused_qkv;
-        fused_qkv = k > 0 ? d.B >= k : (k == 0 && d.B >= 24 && (rounds >= 3 || rounds == 1 || 4 * last >= 32));
-    }
-    // fc1 -> GELU -> fc2 in one workgroup per 128 tokens (vit_mlp_kernel).  vfm_cfg().vit_fused_mlp: n > 0 from n images on, -1 never, 0 (default)
-    // the policy: one workgroup per compute unit whose loop moves nothing through HBM and whose epilogue moves everything -- a single round runs
-    // in lockstep and ends level with the two kernels; from two rounds on the workgroups drift apart and it wins, IF the last round is full
-    // (profiles/r06_ab_vit_fused_mlp_sweep.txt: 84 images 0 %, 144: +1.5 %, 156: -1.9 %, 168: -5.3 %, 180: -6.8 %, 192: +5.4 %, 252: -8.9 %)
-    bool fused_mlp = false;
-    if (d.D == 384 && d.mlp == 1536) {
-        static std::atomic<int> ncu_m{0};
-        if (ncu_m == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            (void)hipGetDevice(&dev);
-            ncu_m = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        }
-        const int groups = ceil_div(d.M / 32, 4), rounds = ceil_div(groups, ncu_m), k = vfm_cfg().vit_fused_mlp;
-        fused_mlp = k > 0 ? d.B >= k : (k == 0 && rounds >= 2 && 5 * groups >= 4 * rounds * ncu_m);
-    }
+    VFM_TRY(gemm(VIT_ST_PATCH, g));
+    const uint4 *q = reinterpret_cast<const uint4*>(w.q), *k = reinterpret_cast<const uint4*>(w.k), *vt = reinterpret_cast<const uint4*>(w.vt);
+    int att_work = d.B * d.heads * (d.Tp / 32);
     for (int l = 0; l < d.depth; ++l) {
         const int s0 = SEG_LAYER0 + l * SEGS_PER_LAYER;
         // LayerNorm 1 is inside this GEMM: raw residual stream x folded weight, statistics applied in the epilogue
         g.A = reinterpret_cast<const uint4*>(w.xh); g.W = f16(s0 + L_QKV_W); g.bias = f32(s0 + L_QKV_B); g.csum = f32(s0 + L_QKV_C);
         g.N = 3 * d.D; g.KS = d.D / 16;
-        if (fused_qkv) {
-#define VIT_FQA(NKT)                                                                                                      \
-    do {                                                                                                                  \
-        constexpr int lds_ = 48 * 1024 + 2 * NKT * 4096 + NKT * 32 * 8;                                                       \
-        static std::atomic<unsigned long long> attr_set{0ull};                                                            \
-        int dev_ = 0;                                                                                                     \
-        (void)hipGetDevice(&dev_);                                                                                        \
-        if (!((attr_set >> (dev_ & 63)) & 1ull)) {                                                                        \
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_qkv_attention_kernel<NKT>),             \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_));                         \
-            attr_set |= 1ull << (dev_ & 63);                                                                              \
-        }                                                                                                                 \
-        GemmArgs gf = g;                                                                                                  \
-        gf.dbg = vfm_cfg().vit_trace_fused == 1 ? vfm_cfg().vit_astat_dbg : nullptr;                                                                             \
-        hipLaunchKernelGGL(vit_qkv_attention_kernel<NKT>, dim3(8 * ceil_div(d.B * d.heads, 8)), dim3(256), lds_, st, gf, d.B, w.a);       \
-    } while (0)
-            switch (d.Tp / 32) {
-                case 1: VIT_FQA(1); break;   case 2: VIT_FQA(2); break;   case 3: VIT_FQA(3); break;
-                case 4: VIT_FQA(4); break;   case 5: VIT_FQA(5); break;   case 6: VIT_FQA(6); break;
-                case 7: VIT_FQA(7); break;   case 8: VIT_FQA(8); break;   case 9: VIT_FQA(9); break;
-                case 10: VIT_FQA(10); break; case 11: VIT_FQA(11); break;
-                default: VIT_FQA(12); break;
-            }
-#undef VIT_FQA
-            VFM_CHECK_LAUNCH("vit_qkv_attention_kernel");
+        if (plan.st[VIT_ST_ATT].inst == VIT_NONE) {   // QKV + attention of an (image, head) in one workgroup
+            GemmArgs gf = traced(plan.st[VIT_ST_QKV], g);
+            void* args[] = {&gf, &d.B, &w.a};
+            VFM_TRY(launch_vit(plan.st[VIT_ST_QKV], args, dev, st));
         } else {
-        if ((rc = launch_gemm<EPI_QKV>(g, st))) return rc;
-#define VIT_ATT(NKT)                                                                                                      \
-    if (att_lds) {                                                                                                        \
-        static std::atomic<unsigned long long> attr_set{0ull};                                                                        \
-        int dev_ = 0;                                                                                                     \
-        (void)hipGetDevice(&dev_);                                                                                        \
-        if (!((attr_set >> (dev_ & 63)) & 1ull)) {                                                                        \
-            VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_attention_lds_kernel<NKT>),             \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, NKT * 4096 + 16384));           \
-            attr_set |= 1ull << (dev_ & 63);                                                                              \
-        }                                                                                                                 \
-        hipLaunchKernelGGL(vit_attention_lds_kernel<NKT>, dim3(d.B * d.heads * ((d.Tp / 32 + 3) / 4)), dim3(256), NKT * 4096 + 16384, st, \
-                           reinterpret_cast<const uint4*>(w.q), reinterpret_cast<const uint4*>(w.k),                      \
-                           reinterpret_cast<const uint4*>(w.vt), d.T, d.Tp, d.heads, d.D, w.a);                           \
-    } else                                                                                                                \
-    hipLaunchKernelGGL(vit_attention_kernel<NKT>, dim3(att_grid), dim3(256), 0, st,                                       \
-                       reinterpret_cast<const uint4*>(w.q), reinterpret_cast<const uint4*>(w.k),                          \
-                       reinterpret_cast<const uint4*>(w.vt), d.T, d.Tp, d.heads, d.D, att_work, w.a, vfm_cfg().vit_xcd)
-        switch (d.Tp / 32) {
-            case 1: VIT_ATT(1); break;   case 2: VIT_ATT(2); break;   case 3: VIT_ATT(3); break;
-            case 4: VIT_ATT(4); break;   case 5: VIT_ATT(5); break;   case 6: VIT_ATT(6); break;
-            case 7: VIT_ATT(7); break;   case 8: VIT_ATT(8); break;   case 9: VIT_ATT(9); break;
-            case 10: VIT_ATT(10); break; case 11: VIT_ATT(11); break; case 12: VIT_ATT(12); break;
-            case 13: VIT_ATT(13); break; case 14: VIT_ATT(14); break; case 15: VIT_ATT(15); break;
-            default: VIT_ATT(16); break;
-        }
-#undef VIT_ATT
-        VFM_CHECK_LAUNCH("vit_attention_kernel");
+            VFM_TRY(gemm(VIT_ST_QKV, g));
+            void* shared[] = {&q, &k, &vt, &d.T, &d.Tp, &d.heads, &d.D, &w.a};                                 // vit_attention_lds_kernel
+            void* per_tile[] = {&q, &k, &vt, &d.T, &d.Tp, &d.heads, &d.D, &att_work, &w.a, &plan.xcd_map};    // vit_attention_kernel
+            VFM_TRY(launch_vit(plan.st[VIT_ST_ATT], plan.st[VIT_ST_ATT].inst >= VIT_ATT_LDS ? shared : per_tile, dev, st));
         }
         g.A = reinterpret_cast<const uint4*>(w.a); g.W = f16(s0 + L_PROJ_W); g.bias = f32(s0 + L_PROJ_B);
         g.gamma = f32(s0 + L_LS1); g.N = d.D; g.KS = d.D / 16;
-        if ((rc = launch_gemm<EPI_RESID>(g, st))) return rc;
+        VFM_TRY(gemm(VIT_ST_PROJ, g));
         // LayerNorm 2 likewise
         g.A = reinterpret_cast<const uint4*>(w.xh); g.W = f16(s0 + L_FC1_W); g.bias = f32(s0 + L_FC1_B); g.csum = f32(s0 + L_FC1_C);
         g.N = d.mlp; g.KS = d.D / 16; g.out = w.h;
-        if (fused_mlp) {   // fc1 -> GELU -> fc2 of 128 tokens in one workgroup (vit_mlp_kernel, the file's second compile part)
-            GemmArgs g2 = g;
-            g.dbg = vfm_cfg().vit_trace_fused == 3 ? vfm_cfg().vit_astat_dbg : nullptr;   // (tools: 3 = the trace buffer is vit_mlp_kernel's)
-            g2.A = reinterpret_cast<const uint4*>(w.h); g2.W = f16(s0 + L_FC2_W); g2.bias = f32(s0 + L_FC2_B);
-            g2.gamma = f32(s0 + L_LS2); g2.N = d.D; g2.KS = d.mlp / 16;
-            if ((rc = vfm_vit_launch_mlp_(&g, &g2, st))) return rc;
+        GemmArgs g2 = g;
+        g2.A = reinterpret_cast<const uint4*>(w.h); g2.W = f16(s0 + L_FC2_W); g2.bias = f32(s0 + L_FC2_B);
+        g2.gamma = f32(s0 + L_LS2); g2.N = d.D; g2.KS = d.mlp / 16;
+        if (plan.st[VIT_ST_FC2].inst == VIT_NONE) {   // fc1 -> GELU -> fc2 of 128 tokens in one workgroup (vit_mlp_kernel, the file's second compile part)
+            const VitLaunch& m = plan.st[VIT_ST_FC1];
+            const GemmArgs g1 = traced(m, g);
+            VFM_TRY(vfm_vit_launch_mlp_(&g1, &g2, m.grid, m.lds_bytes, dev, st));
             continue;
         }
-        if ((rc = launch_gemm<EPI_GELU>(g, st))) return rc;
-        g.A = reinterpret_cast<const uint4*>(w.h); g.W = f16(s0 + L_FC2_W); g.bias = f32(s0 + L_FC2_B);
-        g.gamma = f32(s0 + L_LS2); g.N = d.D; g.KS = d.mlp / 16;
-        if ((rc = launch_gemm<EPI_RESID>(g, st))) return rc;
+        VFM_TRY(gemm(VIT_ST_FC1, g));
+        g = g2;
+        VFM_TRY(gemm(VIT_ST_FC2, g));
     }
     const int tail = SEG_LAYER0 + d.depth * SEGS_PER_LAYER;
     hipLaunchKernelGGL(vit_final_kernel, dim3(ceil_div(d.B * d.Np, 4)), dim3(256), 0, st, w.x, f32(tail + 0), f32(tail + 1),
@@ -2345,18 +2208,13 @@ __global__ __launch_bounds__(256, 1) void vit_mlp_kernel(GemmArgs g1, GemmArgs g
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int vfm_vit_launch_mlp_(const void* fc1_args, const void* fc2_args, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int vfm_vit_launch_mlp_(const void* fc1_args, const void* fc2_args, int grid, int lds_bytes, int dev,
+                                                                        void* stream) {
     const GemmArgs& g1 = *static_cast<const GemmArgs*>(fc1_args);
     const GemmArgs& g2 = *static_cast<const GemmArgs*>(fc2_args);
-    constexpr int lds_ = 144 * 1024 + 2 * 1536 * 4;
-    static std::atomic<unsigned long long> attr_set{0ull};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((attr_set >> (dev & 63)) & 1ull)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&vit_mlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_));
-        attr_set |= 1ull << (dev & 63);
-    }
-    hipLaunchKernelGGL(vit_mlp_kernel, dim3(ceil_div(g1.M / 32, 4)), dim3(256), lds_, (hipStream_t)stream, g1, g2);
+    static std::atomic<unsigned long long> lds_allowed{0ull};
+    VFM_TRY(vfm_allow_dynamic_lds(reinterpret_cast<const void*>(&vit_mlp_kernel), vitplan::VIT_MLP_LDS, dev, lds_allowed));
+    hipLaunchKernelGGL(vit_mlp_kernel, dim3((unsigned)grid), dim3(256), (size_t)lds_bytes, (hipStream_t)stream, g1, g2);
     VFM_CHECK_LAUNCH("vit_mlp_kernel");
     return VFM_OK;
 }

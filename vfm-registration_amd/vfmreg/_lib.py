@@ -150,6 +150,7 @@ DEBUG_SIGNATURES = {
     "vfm_debug_ransac_counts": (C.c_int, [c_vp, c_i64, C.c_int, c_vp]),
     "vfm_debug_ransac_state": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vfm_debug_vit_workspace_layout": (C.c_int, [C.POINTER(VitConfig), C.c_int, C.POINTER(c_i64), C.POINTER(c_i64)]),
+    "vfm_debug_vit_plan": (C.c_int, [C.POINTER(VitConfig), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "vfm_debug_l2_narrow_slices": (C.c_int, [c_i64, c_i64]),
     "vfm_debug_l2_narrow_evals": (C.c_int, [c_vp, C.POINTER(c_i64)]),
 }
@@ -197,9 +198,6 @@ class Config:
     def set(self, key: str, value: int) -> "Config":
         check(load().vfm_config_set(self._h, key.encode(), int(value)), f"config_set({key})")
         return self
-
-    def set_vit_gemm(self, narrow: int, wide: int) -> "Config":
-        return self.set("vit_gemm", (int(narrow) << 32) | (int(wide) & 0xFFFFFFFF))
 
     def get(self, key: str) -> int:
         v = c_i64()
@@ -266,7 +264,8 @@ def thread_config() -> Config:
 def _install_tool_names(lib) -> None:
     """Rounds 1 - 5 exported process-global setters (vfm_debug_set_*); ~140 scripts under tools/ and the A/B tests call them as
     ``lib.vfm_debug_set_coarse_variant(43)``.  The library no longer has them: these PYTHON functions of the same names set the calling
-    thread's Config (``thread_config()``) -- same effect for a single-threaded script, no effect on any other thread."""
+    thread's Config (``thread_config()``) -- same effect for a single-threaded script, no effect on any other thread.  (The ViT's code
+    table ``vfm_debug_set_vit_gemm`` is gone with its key: the ViT tools set the named ``vit_*`` keys under ``using(Config().set(...))``.)"""
     def setter(key):
         def f(value):
             thread_config().set(key, value)
@@ -279,11 +278,6 @@ def _install_tool_names(lib) -> None:
     lib.vfm_debug_set_prep_grid = setter("prep_grid")
     lib.vfm_debug_set_voxel_small = setter("voxel_small")
     lib.vfm_debug_set_ransac_exact_only = setter("ransac_exact_only")
-
-    def vit_gemm(narrow, wide):
-        thread_config().set_vit_gemm(narrow, wide)
-        return 0
-    lib.vfm_debug_set_vit_gemm = vit_gemm
 
 
 def last_coarse_kernel() -> str:
@@ -322,6 +316,22 @@ def prepare_plan(entry: int, schedule: int, d: int, rows1: int, rows2: int = 0, 
     # (template arguments hold commas: a new kernel starts where "prep_" does)
     return {"images": plan["images"].split(","), "kernels": plan["kernels"].replace(",prep_", " prep_").split(" "), "grid": plan["grid"],
             "zero": plan["zero"]}
+
+
+VIT_STAGES = ("pre", "patch", "qkv", "att", "proj", "fc1", "fc2")
+
+
+def vit_plan(cfg, B: int, W: int = 1600, compute_units: int = 0) -> dict:
+    """What vfm_vit_forward(cfg, B images W pixels wide) would launch under the calling thread's Config (include/vfmreg_debug.h,
+    vfm_debug_vit_plan; cfg: a VitConfig; compute_units 0: the current device's): {stage: "<kernel>@<grid>x<block>+<lds bytes>", or None
+    where the stage is inside the kernel before it, for each of VIT_STAGES; "launches": int; "trace": the stage whose launch gets
+    "vit_trace_buffer", or None}.  Raises RuntimeError with the library's message where the forward itself would refuse.  Touches no device."""
+    buf = C.create_string_buffer(1024)
+    check(load().vfm_debug_vit_plan(C.byref(cfg), B, W, compute_units, buf, len(buf)), "vit_plan")
+    plan = dict(item.split("=", 1) for item in buf.value.decode().split(" "))
+    out = {s: (None if plan[s] == "-" else plan[s]) for s in VIT_STAGES}
+    out.update({"launches": int(plan["launches"]), "trace": None if plan["trace"] == "none" else plan["trace"]})
+    return out
 
 
 def check(rc: int, what: str = "") -> None:
