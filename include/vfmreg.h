@@ -36,6 +36,7 @@ extern "C" {
 #define VFM_EINVAL (-1)    /* bad argument (shape, alignment, unsupported size) */
 #define VFM_EWORKSPACE (-2) /* workspace too small */
 #define VFM_EHIP (-3)      /* HIP runtime error at launch */
+#define VFM_ELIMIT (-4)    /* a caller-set work limit ran out before the exact answer was found (nothing is written) */
 
 typedef void *vfm_stream_t; /* hipStream_t */
 
@@ -706,6 +707,54 @@ int vfm_mreach_mst(const int64_t *keys, const int32_t *order, const double *sort
  * (int32[n]): clusters 0.. in ascending condensed-tree node, noise -1.  min_cluster_size >= 2. */
 int vfm_hdbscan_labels_host(const int32_t *lo, const int32_t *hi, const double *w2, int64_t n, int min_cluster_size,
                             int32_t *labels_out);
+
+/* ------------------------------------------------------------------ TEASER++ registration (RN:91-159), csrc/teaser.hip, DESIGN 7.8 */
+
+/* teaser.RobustRegistrationSolver.solve(src, dst) as src/vfm-reg/src/registration_node.py:91-159 sets it up (cbar2 = 1, noise_bound =
+ * 0.2, no scale estimation, PMC_EXACT, CHAIN, GNC_TLS with factor 1.4, 10000 iterations, cost threshold 1e-16), restated with every tie
+ * and every order of summation decided (DESIGN 7.8 is the specification; teaserpp_python itself is not a dependency).  src / tgt:
+ * n x 3 fp64, row i is correspondence i, 1 <= n <= 32768.  Everything is fp64 and unfused, d2 = (dx*dx + dy*dy) + dz*dz.
+ *
+ * vfm_teaser_graph -- TEASER's inlier graph (the translation-invariant-measurement consistency test, RN:112-119): adj_out is an
+ * n x ceil(n / 64) matrix of uint64 words, bit j of row i set iff i != j and abs(sqrt(d2_src(i, j)) - sqrt(d2_tgt(i, j))) <= beta,
+ * beta = 2 * noise_bound * sqrt(cbar2) (inclusive; a NaN gives no edge); diagonal and padding bits clear.  degree_out: int32[n].
+ * No workspace. */
+int vfm_teaser_graph(const double *src, const double *tgt, int64_t n, double noise_bound, double cbar2, uint64_t *adj_out,
+                     int32_t *degree_out, vfm_stream_t stream);
+/* vfm_teaser_reduce -- in front of PMC_EXACT's search (RN:116-117): a lower bound h of the clique number from greedy cliques grown from
+ * the first `seeds` (1..16) vertices in (degree descending, index ascending) order, then the fixpoint of "keep v iff
+ * popcount(adj[v] & kept) >= h - 1" -- every clique of h members or more survives, ties with the heuristic included.  kept_out
+ * (int32[n]): the kept vertices ascending, info_out (int32[2]): {h, the number kept}.  An optimisation only: the maximum clique of
+ * the kept graph is that of the whole graph for every h the heuristic may find. */
+size_t vfm_teaser_reduce_workspace_bytes(int64_t n);
+int vfm_teaser_reduce(const uint64_t *adj, const int32_t *degree, int64_t n, int32_t seeds, int32_t *kept_out, int32_t *info_out,
+                      void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* vfm_teaser_submatrix -- the rows and columns kept[0..k) (ascending, each in 0..n-1) of adj as a k x ceil(k / 64) matrix of the
+ * same form (what vfm_teaser_max_clique_host searches, RN:116-117).  No workspace. */
+int vfm_teaser_submatrix(const uint64_t *adj, int64_t n, const int32_t *kept, int64_t k, uint64_t *sub_out, vfm_stream_t stream);
+/* vfm_teaser_max_clique_host -- PMC_EXACT's answer (RN:116-117), on the HOST (no HIP call, host pointers): THE maximum clique of the
+ * k-vertex graph `sub` (k x ceil(k / 64) words, symmetric, diagonal and padding clear), i.e. the one whose ascending index list is
+ * lexicographically smallest; clique_out (int32[k]) receives kept[] of its members ascending, size_out its size.  kept: int32[k],
+ * strictly ascending.  known: the size of a clique known to exist (0: none) -- it only prunes, the answer does not depend on it; a
+ * value above the clique number is VFM_EINVAL.  node_limit: when the search has visited that many nodes it stops with VFM_ELIMIT and
+ * writes nothing.  A graph that is itself one clique is recognised without a search. */
+int vfm_teaser_max_clique_host(const uint64_t *sub, const int32_t *kept, int64_t k, int64_t known, int64_t node_limit,
+                               int32_t *clique_out, int64_t *size_out);
+/* vfm_teaser_gnc -- the rotation by GNC-TLS on the CHAIN measurements of the clique (RN:118-124): x_i = src[c_i+1] - src[c_i],
+ * y_i likewise, i < k - 1; 2 <= k <= n, clique: int32[k] device, ascending indices into src / tgt.  The whole loop runs in one
+ * launch.  Every sum over the chain is taken in this order (part of the contract): 256 partials p_l over i = l, l + 256, ...
+ * ascending from +0.0, then p_l = p_l + p_(l+s) for l < s, s = 128, 64, ..., 1.  R_out: fp64[9] row-major, weights_out: fp64[k - 1],
+ * iterations_out: int32[1], the weight updates made (0: the loop stopped at its first iteration; -1: an index of clique outside
+ * 0..n-1, nothing else written); v_out: fp64[k x 3], tgt[c_i] - R src[c_i], the input of the translation. */
+size_t vfm_teaser_gnc_workspace_bytes(int64_t k);
+int vfm_teaser_gnc(const double *src, const double *tgt, int64_t n, const int32_t *clique, int64_t k, double noise_bound,
+                   double gnc_factor, int32_t max_iterations, double cost_threshold, double *R_out, double *weights_out,
+                   int32_t *iterations_out, double *v_out, void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* vfm_teaser_tls_translation_host -- the translation by TEASER's scalar TLS estimator per axis (the solver's last stage, RN:127-131),
+ * on the HOST: v is k x 3 fp64 (finite), range = noise_bound * sqrt(cbar2) > 0.  Per axis the 2k endpoints (v_i - range, +(i + 1)),
+ * (v_i + range, -(i + 1)) are sorted as pairs and swept; the estimate is the weighted mean of the consensus set of smallest cost,
+ * the first on ties.  t_out: fp64[3]; inliers_out: uint8[k], abs(v_i - t) <= range on all three axes. */
+int vfm_teaser_tls_translation_host(const double *v, int64_t k, double range, double *t_out, uint8_t *inliers_out);
 
 /* ------------------------------------------------------------------ descriptor PCA and the colour gate (IF:162-192, RN:696-702)
  * csrc/pca.hip, DESIGN 7.6.  Rows x (n x d, row-major) are fp32 or fp16 (VFM_ROWS_F32 / VFM_ROWS_F16); both widen exactly to fp64, and

@@ -118,6 +118,15 @@ SIGNATURES = {
     "vfm_mreach_mst_workspace_bytes": (C.c_size_t, [c_i64]),
     "vfm_mreach_mst": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_hdbscan_labels_host": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp]),
+    "vfm_teaser_graph": (C.c_int, [c_vp, c_vp, c_i64, C.c_double, C.c_double, c_vp, c_vp, c_vp]),
+    "vfm_teaser_reduce_workspace_bytes": (C.c_size_t, [c_i64]),
+    "vfm_teaser_reduce": (C.c_int, [c_vp, c_vp, c_i64, C.c_int32, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_teaser_submatrix": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "vfm_teaser_max_clique_host": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.POINTER(c_i64)]),
+    "vfm_teaser_gnc_workspace_bytes": (C.c_size_t, [c_i64]),
+    "vfm_teaser_gnc": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, C.c_double, C.c_double, C.c_int32, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 C.c_size_t, c_vp]),
+    "vfm_teaser_tls_translation_host": (C.c_int, [c_vp, c_i64, C.c_double, c_vp, c_vp]),
     "vfm_pca_moments_workspace_bytes": (C.c_size_t, [C.c_int]),
     "vfm_pca_moments": (C.c_int, [c_vp, C.c_int, c_i64, C.c_int, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_pca_project_workspace_bytes": (C.c_size_t, []),

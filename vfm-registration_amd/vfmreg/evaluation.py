@@ -168,7 +168,7 @@ class Evaluation:
 def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = None,
                    evaluation: Optional[Evaluation] = None, run_icp: bool = True, icp_ground_truth: bool = False,
                    icp_baseline: bool = False, baselines=(), cluster_removal_prob: float = 0.0, remove_classes=None,
-                   pca=None) -> Evaluation:
+                   pca=None, teaser: bool = False) -> Evaluation:
     """The VFM + RANSAC (+ ICP) branch of make_step for one scene (RN:587-589, 593, 860-882, 943-951):
     every scan is registered against the accumulated map with the identity as initial guess and
     compared with its ground-truth pose.  ``icp_ground_truth``: that pose is the stored one refined by ICP against the map, as the
@@ -183,7 +183,10 @@ def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = No
     this chance and one ``np.random.RandomState(42)`` per scene shared by its scans (RN:584); the scan is registered against the
     filtered map, the map's baseline features are dropped at every scan (RN:876-877) and ``points_in_map`` records the filtered size
     (RN:792).  ``pca``: what has ``run_pca`` (an ``ImageFeatureGenerator`` or a ``pca.DescriptorPCA``, e.g. one whose ``fit_pca[3]`` holds
-    the reference's fit); default a fresh ``pca.DescriptorPCA``, fitted on the first scan's map."""
+    the reference's fit); default a fresh ``pca.DescriptorPCA``, fitted on the first scan's map.
+
+    ``teaser`` (default False: the result set is unchanged): the TEASER rows of RN:895-904 behind the RANSAC rows -- ``fpfh_teaser`` /
+    ``fpfh_teaser_icp`` if ``"fpfh"`` is among ``baselines``, ``vfm_teaser`` / ``vfm_teaser_icp`` always (``*_icp`` with ``run_icp``)."""
     node = node or RegistrationNode(cache_map=True, baseline_methods=tuple(baselines))   # local_map below is built here and never edited: one map per scene (RN:556-589)
     ev = evaluation or Evaluation()
     n_desc = scene["map_point_clouds"][0].shape[1] - 3
@@ -212,6 +215,9 @@ def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = No
         for method in baselines:                                                     # RN:867-883, in the reference's order
             results[f"{method}_ransac"], results[f"{method}_ransac_icp"] = node.ransac_registration(local_map, point_cloud, method, run_icp)
         results["vfm_ransac"], results["vfm_ransac_icp"] = node.ransac_registration(local_map, point_cloud, "vfm", run_icp)
+        if teaser:                                                                   # RN:895-904
+            for method in (("fpfh",) if "fpfh" in baselines else ()) + ("vfm",):
+                results[f"{method}_teaser"], results[f"{method}_teaser_icp"] = node.teaser_registration(local_map, point_cloud, method, run_icp)
         if icp_baseline:
             results["icp"] = node.icp_registration(icp_map, point_cloud[:, :3], dist=7)          # RN:929
         for k, v in results.items():

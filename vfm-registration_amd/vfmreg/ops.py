@@ -702,6 +702,105 @@ def hdbscan_labels_host(lo, hi, w2, min_cluster_size: int):
     return labels
 
 
+# ------------------------------------------------------------------------------------- TEASER++ registration (csrc/teaser.hip, teaser_host.cpp)
+TEASER_MAX_N = 32768
+TEASER_MAX_SEEDS = 16
+TEASER_NODE_LIMIT = 50_000_000     # nodes of the host's exact clique search before it gives up (VFM_ELIMIT), the default of the wrappers
+
+
+def _teaser_rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    _chk(t, torch.float64, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected n x 3 rows")
+    return t
+
+
+def teaser_graph(src: torch.Tensor, tgt: torch.Tensor, noise_bound: float, cbar2: float = 1.0):
+    """vfm_teaser_graph: (adj uint64-as-int64 [n, ceil(n / 64)], degree int32[n]) of the consistency graph of n correspondences
+    (``src`` / ``tgt``: n x 3 fp64, 1 <= n <= 32768).  No read-back."""
+    _teaser_rows(src, "src"), _teaser_rows(tgt, "tgt")
+    n = src.shape[0]
+    if tgt.shape[0] != n:
+        raise ValueError("src and tgt must have one row per correspondence each")
+    adj = torch.empty((n, (n + 63) // 64), dtype=torch.int64, device=src.device)
+    deg = torch.empty(n, dtype=torch.int32, device=src.device)
+    _lib.check(_lib.load().vfm_teaser_graph(src.data_ptr(), tgt.data_ptr(), n, float(noise_bound), float(cbar2), adj.data_ptr(), deg.data_ptr(),
+                                            _stream()), "teaser_graph")
+    return adj, deg
+
+
+def teaser_reduce(adj: torch.Tensor, deg: torch.Tensor, seeds: int = TEASER_MAX_SEEDS, ws: Optional[torch.Tensor] = None):
+    """vfm_teaser_reduce: (kept int32[n], info int32[2] = {h, number kept}) on the device -- the first info[1] entries of kept are the
+    vertices that can belong to a clique of h members or more, ascending.  No read-back."""
+    _chk(adj, torch.int64, "adj"), _chk(deg, torch.int32, "degree")
+    n = deg.shape[0]
+    if tuple(adj.shape) != (n, (n + 63) // 64):
+        raise ValueError("adj: expected n x ceil(n / 64) words")
+    lib = _lib.load()
+    kept = torch.empty(n, dtype=torch.int32, device=adj.device)
+    info = torch.empty(2, dtype=torch.int32, device=adj.device)
+    need = lib.vfm_teaser_reduce_workspace_bytes(n)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, adj.device)
+    _lib.check(lib.vfm_teaser_reduce(adj.data_ptr(), deg.data_ptr(), n, int(seeds), kept.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _stream()), "teaser_reduce")
+    return kept, info
+
+
+def teaser_submatrix(adj: torch.Tensor, kept: torch.Tensor) -> torch.Tensor:
+    """vfm_teaser_submatrix: the rows and columns ``kept`` (int32[k], ascending) of adj as [k, ceil(k / 64)] words.  No read-back."""
+    _chk(adj, torch.int64, "adj"), _chk(kept, torch.int32, "kept")
+    n, k = adj.shape[0], kept.shape[0]
+    sub = torch.empty((k, (k + 63) // 64), dtype=torch.int64, device=adj.device)
+    _lib.check(_lib.load().vfm_teaser_submatrix(adj.data_ptr(), n, kept.data_ptr(), k, sub.data_ptr(), _stream()), "teaser_submatrix")
+    return sub
+
+
+def teaser_max_clique_host(sub, kept, known: int = 0, node_limit: int = TEASER_NODE_LIMIT) -> np.ndarray:
+    """vfm_teaser_max_clique_host: THE maximum clique (int32, the entries of ``kept`` of its members, ascending) of the graph ``sub``
+    (numpy, [k, ceil(k / 64)] uint64 or int64 words).  Raises RuntimeError when ``node_limit`` runs out.  No device is touched."""
+    import ctypes as C
+    kept = np.ascontiguousarray(kept, dtype=np.int32)
+    k = len(kept)
+    sub = np.ascontiguousarray(sub).view(np.uint64).reshape(k, (k + 63) // 64)
+    clique = np.full(max(k, 1), -1, dtype=np.int32)
+    size = C.c_int64(-1)
+    _lib.check(_lib.load().vfm_teaser_max_clique_host(sub.ctypes.data, kept.ctypes.data, k, int(known), int(node_limit), clique.ctypes.data,
+                                                      C.byref(size)), "teaser_max_clique_host")
+    return clique[:size.value].copy()
+
+
+def teaser_gnc(src: torch.Tensor, tgt: torch.Tensor, clique: torch.Tensor, noise_bound: float, gnc_factor: float = 1.4,
+               max_iterations: int = 10000, cost_threshold: float = 1e-16, ws: Optional[torch.Tensor] = None):
+    """vfm_teaser_gnc: (R fp64[3, 3], weights fp64[k - 1], iterations int32[1], v fp64[k, 3]) on the device for the clique (int32[k],
+    k >= 2, ascending rows of src / tgt).  No read-back."""
+    _teaser_rows(src, "src"), _teaser_rows(tgt, "tgt"), _chk(clique, torch.int32, "clique")
+    n, k = src.shape[0], clique.shape[0]
+    lib = _lib.load()
+    dev = src.device
+    R = torch.empty((3, 3), dtype=torch.float64, device=dev)
+    w = torch.empty(max(k - 1, 0), dtype=torch.float64, device=dev)
+    it = torch.empty(1, dtype=torch.int32, device=dev)
+    v = torch.empty((k, 3), dtype=torch.float64, device=dev)
+    need = lib.vfm_teaser_gnc_workspace_bytes(k)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    _lib.check(lib.vfm_teaser_gnc(src.data_ptr(), tgt.data_ptr(), n, clique.data_ptr(), k, float(noise_bound), float(gnc_factor),
+                                  int(max_iterations), float(cost_threshold), R.data_ptr(), w.data_ptr(), it.data_ptr(), v.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), _stream()), "teaser_gnc")
+    return R, w, it, v
+
+
+def teaser_tls_translation_host(v, rng: float):
+    """vfm_teaser_tls_translation_host: (t fp64[3], inliers bool[k]) from the rows ``v`` (numpy, k x 3).  No device is touched."""
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3)
+    t = np.empty(3, dtype=np.float64)
+    inl = np.empty(len(v), dtype=np.uint8)
+    _lib.check(_lib.load().vfm_teaser_tls_translation_host(v.ctypes.data, len(v), float(rng), t.ctypes.data, inl.ctypes.data),
+               "teaser_tls_translation_host")
+    return t, inl.astype(bool)
+
+
 # ------------------------------------------------------------------------------------- descriptor PCA and the colour gate (csrc/pca.hip)
 PCA_MAX_D = 768
 PCA_MAX_K = 8

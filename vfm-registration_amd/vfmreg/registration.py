@@ -6,9 +6,11 @@
   rotation re-orthogonalisation RN:331-336     icp_registration            RN:359-394
   ransac_registration('fpfh')  RN:282-357 (opt-in: ``baseline_methods``; the row recovery of RN:295-310 is vfmreg.neighbors)
 
+  teaser_registration('vfm' | 'fpfh')  RN:91-159 (vfmreg/teaser.py stands in for teaserpp_python; 'fpfh' opt-in like the RANSAC row)
+
 Same names, argument meaning and return values; numpy in / numpy out.  The ROS node, the learned baseline
-descriptors, TEASER and PointDSC are out of scope.  ``run_icp=True`` runs the point-to-point ICP
-refinement of registration_node.py:338-344 (row F2, vfmreg/icp.py).
+descriptors and PointDSC are out of scope.  ``run_icp=True`` runs the point-to-point ICP
+refinement of registration_node.py:338-344 / 133-157 (row F2, vfmreg/icp.py).
 """
 from __future__ import annotations
 
@@ -348,6 +350,57 @@ class RegistrationNode:
                                   max_correspondance_distance=3 * sigma, kernel=sigma / 3)   # RN:340-344
             return ransac_pose, pose
         return ransac_pose, None
+
+    def teaser_registration(self, voxel_map, raw_scan, method: str, run_icp: bool = False):
+        """RN:91-159: TEASER++ on the correspondences of ``compute_vfm_correspondences`` (``'vfm'``) or of
+        ``compute_correspondences(..., 'fpfh', mutual_filter=True)`` (``'fpfh'``: only on a node created with ``baseline_methods``
+        that lists it, as ``ransac_registration('fpfh')``); every other name raises ValueError.  Returns (teaser_pose, pose after ICP or
+        None).  An invalid solution (fewer than two consistent correspondences) is the identity, as the reference's ``np.eye(4)`` filled
+        from an aborted solve.  ``voxel_map`` may be a ``MapHandle`` for ``'vfm'``."""
+        from . import teaser
+        if method == "vfm":
+            c = self._correspond(voxel_map, raw_scan, np.eye(4))                                   # RN:104
+            src, tgt = c["src_xyz"], c["map_xyz"][c["tgt_rows"]]
+        elif method == "fpfh" and method in self.baseline_methods:
+            vm, scan = np.asarray(voxel_map), np.asarray(raw_scan)
+            if vm.ndim != 2 or vm.shape[1] < 3 or scan.ndim != 2 or scan.shape[1] < 3:
+                raise ValueError("Invalid shape")
+            map_xyz = np.ascontiguousarray(vm[:, :3])
+            raw_xyz = torch.from_numpy(np.ascontiguousarray(scan[:, :3], dtype=np.float64)).cuda()
+            src, tgt = self._baseline_correspondences_device(map_xyz, raw_xyz, method, True)       # RN:98-101
+        else:
+            raise ValueError(f"Invalid method: {method}")
+        solver_params = teaser.RobustRegistrationSolver.Params()                                   # RN:112-124
+        solver_params.cbar2 = 1.0
+        solver_params.noise_bound = 0.2
+        solver_params.estimate_scaling = False
+        solver_params.inlier_selection_mode = teaser.RobustRegistrationSolver.INLIER_SELECTION_MODE.PMC_EXACT
+        solver_params.rotation_tim_graph = teaser.RobustRegistrationSolver.INLIER_GRAPH_FORMULATION.CHAIN
+        solver_params.rotation_estimation_algorithm = teaser.RobustRegistrationSolver.ROTATION_ESTIMATION_ALGORITHM.GNC_TLS
+        solver_params.rotation_gnc_factor = 1.4
+        solver_params.rotation_max_iterations = 10000
+        solver_params.rotation_cost_threshold = 1e-16
+        solver = teaser.RobustRegistrationSolver(solver_params)                                    # RN:125
+        solution = solver.solve_rows(src.to(torch.float64).contiguous(), tgt.to(torch.float64).contiguous())   # RN:127-128
+        teaser_pose = np.eye(4)                                                                    # RN:129-131
+        teaser_pose[:3, :3] = solution.rotation
+        teaser_pose[:3, 3] = solution.translation
+        if not run_icp:
+            return teaser_pose, None
+        teaser_pose = orthogonalize_rotation(teaser_pose)                                          # RN:145-148
+        sigma = self.config.adaptive_threshold.initial_threshold                                   # RN:150
+        if method == "vfm":
+            vhm = c["voxel_hash_map"]                                                              # RN:135-136: the same kept points
+            voxel_scan = c["voxel_scan_xyz"].cpu().numpy()                                         # RN:139-141
+            pose = register_frame(points=voxel_scan, voxel_map=vhm if not vhm.empty() else vhm.xyz_map(), initial_guess=teaser_pose,
+                                  max_correspondance_distance=3 * sigma, kernel=sigma / 3)         # RN:151-155
+        else:
+            from .icp import _grid_of, register_frame_on_grid
+            voxel_hash_map = get_voxel_hash_map(self.config)                                       # RN:135-136
+            voxel_hash_map.add_points(map_xyz)
+            voxel_scan = self._voxel_scan(raw_xyz, self.config.mapping.voxel_size)                 # RN:139-141
+            pose = register_frame_on_grid(voxel_scan, _grid_of(voxel_hash_map), teaser_pose, 3 * sigma, sigma / 3)   # RN:151-155
+        return teaser_pose, pose
 
     def baseline_row_pairs(self, voxel_map, raw_scan, method: str = "fpfh") -> dict:
         """RN:282-310 on the device: the baseline's correspondences, the scan's two voxel levels, the 3-D hash map of
