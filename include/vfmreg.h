@@ -120,6 +120,29 @@ int vfm_match_ip_top1_gated(const float *q, int64_t n, const float *b, int64_t m
                             float gate, int64_t *idx_out, float *sim_out, void *ws, size_t ws_bytes,
                             vfm_stream_t stream);
 
+/* faiss::IndexFlatIP(d).search(n, xq, k, D, I) with k as a parameter -- the loop of VHM:491-511, 587-600 is written for k candidates
+ * per point (I[i * k + j], D[i * k + j]) and run with k = 1.  Raw rows go in and are normalised as vfm_match_ip_top1 normalises them.
+ * idx_out (int64[n k]) / sim_out (fp32[n k]): row i holds the k best map rows of query i, sorted by the fp64 score of the
+ * fp32-normalised rows (ascending column order) DESCENDING, equal scores to the LOWER map index; sim = (float)score.  Column 0 is,
+ * bit for bit, vfm_match_ip_top1's answer.  m < k: the last k - m columns are (-1, -FLT_MAX), as faiss pads an inner-product heap
+ * (m == 0: all of them; not an error).  A zero query row scores 0.0 against every row: rows 0 .. k-1 with sim 0; a zero map row
+ * scores 0.0 and takes part like any other.  1 <= k <= VFM_MATCH_TOPK_MAX, d >= 1 (VFM_EINVAL otherwise, before anything is
+ * launched, as for null outputs); n == 0 succeeds and writes nothing; a workspace smaller than _workspace_bytes is VFM_EWORKSPACE.
+ * No gate: the caller applies !(sim < thr) to the result, as the reference does (VHM:503).
+ * VFM_MATCH_EXACT (d <= 8192): all pairs in fp64 on the vector ALUs.
+ * VFM_MATCH_FAST, d = 128 / 256 / 384 and at most 2^24 map rows: an fp16 MFMA coarse pass that keeps, per query, a lower bound of
+ * the k-th best coarse score and records every row within the proven window of it, then the fp64 decision among the records
+ * (csrc/match_topk.hip); a query with more than 1024 records is decided by the all-pairs kernel inside the same
+ * call.  Same answers as EXACT.  Any other shape given FAST runs EXACT (the d = 512 and d = 640 / 768 kernel shapes of the top-1
+ * search have no k-best form).
+ * info_out (nullable, DEVICE int32[4]): the largest record count of a query, the number of queries decided by the all-pairs
+ * kernel, the largest number of map slices of a coarse launch, 0.  A call that ran EXACT reports (0, n, 0, 0). */
+#define VFM_MATCH_TOPK_MAX 8
+size_t vfm_match_ip_topk_workspace_bytes(int64_t n, int64_t m, int d, int k, int prec_mode);
+int vfm_match_ip_topk(const float *q, int64_t n, const float *b, int64_t m, int d, int k, int prec_mode,
+                      int64_t *idx_out, float *sim_out, int32_t *info_out /* may be NULL */,
+                      void *ws, size_t ws_bytes, vfm_stream_t stream);
+
 /* Split form for a map that is searched many times (IndexFlatIP.add once, VHM:487): the
  * prepared operand holds 1/|row| and the fp16 MFMA-fragment image of the normalised rows. */
 size_t vfm_match_prepared_bytes(int64_t rows, int d);

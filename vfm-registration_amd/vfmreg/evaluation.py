@@ -168,7 +168,7 @@ class Evaluation:
 def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = None,
                    evaluation: Optional[Evaluation] = None, run_icp: bool = True, icp_ground_truth: bool = False,
                    icp_baseline: bool = False, baselines=(), cluster_removal_prob: float = 0.0, remove_classes=None,
-                   pca=None, teaser: bool = False) -> Evaluation:
+                   pca=None, teaser: bool = False, vfm_candidates: int = 1) -> Evaluation:
     """The VFM + RANSAC (+ ICP) branch of make_step for one scene (RN:587-589, 593, 860-882, 943-951):
     every scan is registered against the accumulated map with the identity as initial guess and
     compared with its ground-truth pose.  ``icp_ground_truth``: that pose is the stored one refined by ICP against the map, as the
@@ -186,8 +186,12 @@ def evaluate_scene(scene: Dict[str, list], node: Optional[RegistrationNode] = No
     the reference's fit); default a fresh ``pca.DescriptorPCA``, fitted on the first scan's map.
 
     ``teaser`` (default False: the result set is unchanged): the TEASER rows of RN:895-904 behind the RANSAC rows -- ``fpfh_teaser`` /
-    ``fpfh_teaser_icp`` if ``"fpfh"`` is among ``baselines``, ``vfm_teaser`` / ``vfm_teaser_icp`` always (``*_icp`` with ``run_icp``)."""
-    node = node or RegistrationNode(cache_map=True, baseline_methods=tuple(baselines))   # local_map below is built here and never edited: one map per scene (RN:556-589)
+    ``fpfh_teaser_icp`` if ``"fpfh"`` is among ``baselines``, ``vfm_teaser`` / ``vfm_teaser_icp`` always (``*_icp`` with ``run_icp``).
+
+    ``vfm_candidates`` (default 1: the rows are unchanged): map candidates per scan point of the VFM rows, passed to the node this
+    function creates (``RegistrationNode(vfm_candidates=...)``; a ``node`` that is handed in keeps its own)."""
+    node = node or RegistrationNode(cache_map=True, baseline_methods=tuple(baselines),   # local_map below is built here and never edited: one map per scene (RN:556-589)
+                                    vfm_candidates=vfm_candidates)
     ev = evaluation or Evaluation()
     n_desc = scene["map_point_clouds"][0].shape[1] - 3
     local_map = build_local_map(scene["map_poses"], scene["map_point_clouds"], n_descriptors=n_desc)

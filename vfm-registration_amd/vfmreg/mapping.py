@@ -323,6 +323,37 @@ class VoxelHashMap:
         corres = r["corres"][:k]
         return corres[:, 0].long(), corres[:, 1].long(), sim
 
+    def search_device_topk(self, q_rows: Optional[torch.Tensor], min_cosine_similarity: float, k: int,
+                           q_desc: Optional[torch.Tensor] = None):
+        """The search with k candidates per point, as VoxelHashMap.cpp:491-511, 587-600 is written (``I[i * k + j]``; the reference sets
+        k = 1): (query_idx int64[K], map_idx int64[K], rank int64[K], sim fp32[N, k]) as device tensors.  ``sim`` is faiss' D array --
+        every query's k best cosines, descending, equal ones to the lower map row, (-1, lowest float32) behind the last map row --;
+        an entry is a correspondence iff ``!(sim < min_cosine_similarity)`` (VoxelHashMap.cpp:503), and the pairs come query-major,
+        rank-minor (VoxelHashMap.cpp:590-600).  No query is left unresolved: the gate is applied to the result."""
+        b_desc, _ = self._device_map()
+        if q_desc is not None:
+            if q_desc.dim() != 2 or q_desc.shape[1] != b_desc.shape[1] or q_desc.dtype != torch.float32:
+                raise RuntimeError("Unable to cast Python instance to C++ type: expected %d float32 descriptor columns" % b_desc.shape[1])
+            q_desc = q_desc.contiguous()
+        else:
+            if q_rows.dim() != 2 or q_rows.shape[1] != b_desc.shape[1] + 3:
+                raise RuntimeError("Unable to cast Python instance to C++ type: expected %d columns" % (b_desc.shape[1] + 3))
+            q_desc = q_rows[:, 3:].float().contiguous()            # VoxelHashMap.cpp:478-481
+        prec = ops.FAST if q_desc.shape[1] in (128, 256, 384) else ops.EXACT
+        idx, sim = ops.match_ip_topk(q_desc, b_desc, k, prec)
+        valid = ~(sim.double() < float(min_cosine_similarity)) & (idx >= 0)   # (the padding never passes a gate a cosine can reach)
+        at = torch.nonzero(valid)                                  # row-major: query-major, rank-minor
+        return at[:, 0], idx[valid], at[:, 1], sim
+
+    def get_vfm_correspondence_indices_topk(self, points: np.ndarray, min_cosine_similarity: float, k: int):
+        """(query_idx[K], map_idx[K], rank[K], sim[N, k]) -- ``get_vfm_correspondence_indices`` with k candidates per point, in the
+        reference's emission order (see ``search_device_topk``)."""
+        points = np.asarray(points)
+        if self._cloud("n") is None or points.ndim != 2:
+            raise RuntimeError("Unable to cast Python instance to C++ type")
+        qi, mi, rank, sim = self.search_device_topk(to_device_rows(points)[0], min_cosine_similarity, k)
+        return qi.cpu().numpy(), mi.cpu().numpy(), rank.cpu().numpy(), sim.cpu().numpy()
+
     def get_vfm_correspondence_indices(self, points: np.ndarray, min_cosine_similarity: float, resolve_all: bool = False):
         """(query_idx[K], map_idx[K], sim[N]) -- the indices behind get_vfm_correspondences.  ``sim[i]`` = -2.0 marks a query
         that provably has no match at the threshold (see ``search_device``); ``resolve_all=True`` returns every best cosine."""

@@ -83,6 +83,39 @@ def match_ip_top1(q: torch.Tensor, b: torch.Tensor, prec: int = FAST,
     return idx, sim
 
 
+MATCH_TOPK_MAX_K = 8            # VFM_MATCH_TOPK_MAX
+MATCH_TOPK_RECORD_CAP = 1024    # records a query can hold in FAST mode before the all-pairs kernel decides it (csrc/match_topk.hip)
+
+
+def match_ip_topk(q: torch.Tensor, b: torch.Tensor, k: int, prec: int = FAST, ws: Optional[torch.Tensor] = None,
+                  return_info: bool = False):
+    """Normalise + IndexFlatIP.search(n, x, k, D, I) (the k-candidate loop of VoxelHashMap.cpp:491-511).  Returns
+    (idx int64[N, k], sim fp32[N, k]): per query the k best map rows by fp64 score, descending, equal scores to the lower index;
+    with fewer than k map rows the last columns are (-1, lowest finite float32).  Column 0 is ``match_ip_top1``'s answer.  No gate:
+    apply ``~(sim < thr)`` to the result.  ``return_info``: also int32[4] on the device -- largest record count of a query, queries
+    decided by the all-pairs kernel, map slices of the coarse pass, 0 (a call that ran EXACT: 0, N, 0, 0)."""
+    _chk(q, torch.float32, "q")
+    _chk(b, torch.float32, "b")
+    if q.dim() != 2 or b.dim() != 2 or q.shape[1] != b.shape[1]:
+        raise ValueError("Invalid shape")
+    k = int(k)
+    if not 1 <= k <= MATCH_TOPK_MAX_K:
+        raise ValueError(f"k must be in 1 .. {MATCH_TOPK_MAX_K}, got {k}")
+    lib = _lib.load()
+    n, d = q.shape
+    m = b.shape[0]
+    need = lib.vfm_match_ip_topk_workspace_bytes(n, m, d, k, prec)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, q.device)
+    idx = torch.empty((n, k), dtype=torch.int64, device=q.device)
+    sim = torch.empty((n, k), dtype=torch.float32, device=q.device)
+    info = torch.zeros(4, dtype=torch.int32, device=q.device) if return_info else None
+    if n > 0:   # (no queries: nothing to write, and an empty tensor has no address to pass)
+        _lib.check(lib.vfm_match_ip_topk(q.data_ptr(), n, b.data_ptr(), m, d, k, prec, idx.data_ptr(), sim.data_ptr(), _ptr(info),
+                                         ws.data_ptr(), ws.numel(), _stream()), "match_ip_topk")
+    return (idx, sim, info) if return_info else (idx, sim)
+
+
 class PreparedRows:
     """IndexFlatIP.add (VoxelHashMap.cpp:486-487): 1/|row| + fp16 fragment tiles of the rows."""
 

@@ -143,7 +143,7 @@ class RegistrationNode:
     builds the scene's map itself and never edits it -- opts in."""
 
     def __init__(self, config=None, ransac_iterations: int = 50000, max_correspondence_distance: float = 10000.0,
-                 min_cosine_similarity: float = 0.8, cache_map: bool = False, baseline_methods=()):
+                 min_cosine_similarity: float = 0.8, cache_map: bool = False, baseline_methods=(), vfm_candidates: int = 1):
         self.config = config or load_config(None, None)  # RN:85
         self.ransac_iterations = ransac_iterations       # RN:326
         self.max_correspondence_distance = max_correspondence_distance  # RN:323
@@ -153,6 +153,12 @@ class RegistrationNode:
         for m in self.baseline_methods:
             if m != "fpfh" and m not in self._LEARNED:
                 raise ValueError(f"Invalid method: {m}")
+        # map candidates per scan point of the VFM correspondences (the k of VoxelHashMap.cpp:491; the reference sets 1).  1: today's
+        # search, the same code path; more: the k-best search -- among alike descriptors the best cosine is often a twin of the
+        # right row -- and RANSAC / TEASER receive up to k pairs per scan point
+        self.vfm_candidates = int(vfm_candidates)
+        if not 1 <= self.vfm_candidates <= ops.MATCH_TOPK_MAX_K:
+            raise ValueError(f"vfm_candidates must be in 1 .. {ops.MATCH_TOPK_MAX_K}, got {vfm_candidates}")
         self._map_cache = None   # (weakref to the array, (shape, dtype, fingerprint), VoxelHashMap)
         self._pose_cache = None  # (bytes of the last initial pose, its device copy): the node passes the identity in every call
         self._chain_host = None  # page-locked landing area of the voxel chain's one read-back
@@ -248,7 +254,10 @@ class RegistrationNode:
                 raw_idx = raw_of_voxel_scan[order].cpu().numpy()
             sub_xyz = pcl_xyz[order]
             q_desc = self._upload_rows(scan, raw_idx)                   # VoxelHashMap.cpp:478-481
-            qi, mi, _ = voxel_hash_map.search_device(None, self.min_cosine_similarity, q_desc=q_desc)       # RN:418
+            if self.vfm_candidates == 1:
+                qi, mi, _ = voxel_hash_map.search_device(None, self.min_cosine_similarity, q_desc=q_desc)       # RN:418
+            else:   # up to k pairs per scan point, query-major (a scan point may appear several times: legal in both solvers)
+                qi, mi, _, _ = voxel_hash_map.search_device_topk(None, self.min_cosine_similarity, self.vfm_candidates, q_desc=q_desc)
             out = dict(src_rows=order[qi], tgt_rows=mi, src_xyz=sub_xyz[qi])
             if len(qi) >= 75:
                 break
