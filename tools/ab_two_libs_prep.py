@@ -5,7 +5,8 @@ A build may be given with a "coarse_variant" code for its preparation form (the 
     python tools/ab_two_libs_prep.py libA.so libB.so:43 libB.so:44 [...]          (files under vfm-registration_amd/vfmreg/lib/)
 --cases (first argument): no timing; every row of tests/prep_plan_cases.py that an exported entry serves, at the table's shape and at C2,
 through each build with the row's policy in the build's own config: torch.equal of both whole prepared buffers and of the search workspace
-(the ranges vfm_match_prepare2_gated_z clears; filled alike before), per row, against the first build."""
+(the ranges vfm_match_prepare2_gated_z clears; filled alike before), per row, against the first build.  Both operands carry planted
+rows (plant(): NaN, Inf, huge, scaled half, zero), so the paths random rows never take are compared as well."""
 import ctypes as C
 import sys
 from pathlib import Path
@@ -37,6 +38,22 @@ for arg in sys.argv[2 if cases_mode else 1:]:
     libs.append((arg, l, cfg))
 
 
+def plant(x):
+    """Rows that plain randn never draws, in place: a NaN below column d / 2, a NaN at or above it, an Inf, a row scaled by 1e30, a row
+    whose first half is scaled by 1e-3 -- one 128-row group each where the operand has that many groups -- and a zero row as the last
+    row, in the partly filled last group (tests/test_gpu_mx6.py plants the same kinds)."""
+    r, d = x.shape
+    groups = (r + 127) // 128
+    at = [min((k * groups // 6) * 128 + 3 + k, r - 6 + k) for k in range(5)]   # distinct, in front of the last row
+    x[at[0], 5] = float("nan")
+    x[at[1], d // 2 + 7] = float("nan")
+    x[at[2], 11] = float("inf")
+    x[at[3]] *= 1e30
+    x[at[4], : d // 2] *= 1e-3
+    x[r - 1] = 0.0
+    return x
+
+
 def run_cases():
     """the case table through every build: same bytes as the first one?"""
     sys.path.insert(0, str(ROOT))
@@ -52,7 +69,7 @@ def run_cases():
             if d not in rows:
                 rows.clear()   # (one width's operands at a time)
                 g = torch.Generator(device="cuda").manual_seed(d)
-                rows[d] = [torch.randn(r, d, device="cuda", generator=g) for r in (r1, r2)]
+                rows[d] = [plant(torch.randn(r, d, device="cuda", generator=g)) for r in (r1, r2)]
                 rows[d] += [x.half() for x in rows[d]]
             x1, x2 = rows[d][2 * t1], rows[d][1 + 2 * t2]
             n2 = 0 if case.entry in ppc.ONE_OPERAND else r2

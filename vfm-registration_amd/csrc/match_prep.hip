@@ -6,6 +6,15 @@
 namespace vfmm {
 namespace {
 
+// 16 bytes of an image to global memory as four non-temporal words (the images are read next by another kernel, from HBM)
+__device__ __forceinline__ void store_nt(uint4* dst, const uint4 t) {
+    unsigned* o = reinterpret_cast<unsigned*>(dst);
+    __builtin_nontemporal_store(t.x, o);
+    __builtin_nontemporal_store(t.y, o + 1);
+    __builtin_nontemporal_store(t.z, o + 2);
+    __builtin_nontemporal_store(t.w, o + 3);
+}
+
 // (a second operand -- x2, rows2, ... -- may ride in the same grid: workgroups >= tiles1 prepare it; the scan and the map
 // of a registration go out as ONE launch instead of two, 25 us less on the stream the coarse pass waits on)
 __global__ __launch_bounds__(256) void prep_rows_kernel(const float* __restrict__ x, int64_t rows, int d,
@@ -58,14 +67,7 @@ __global__ __launch_bounds__(256) void prep_rows_kernel(const float* __restrict_
     const int units = ksteps * 64;
     uint4* dst = tiles + (int64_t)tile * units;
     const uint4* src = reinterpret_cast<const uint4*>(smem);
-    for (int u = threadIdx.x; u < units; u += 256) {
-        const uint4 t = src[u];
-        unsigned* o = reinterpret_cast<unsigned*>(dst + u);
-        __builtin_nontemporal_store(t.x, o);
-        __builtin_nontemporal_store(t.y, o + 1);
-        __builtin_nontemporal_store(t.z, o + 2);
-        __builtin_nontemporal_store(t.w, o + 3);
-    }
+    for (int u = threadIdx.x; u < units; u += 256) store_nt(dst + u, src[u]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -121,6 +123,229 @@ constexpr float MX6_F16_ROUNDING = 4.8929e-4f;   // 2^-11 (1 + 2^-13) + sqrt(768
 typedef _Float16 halfx32 __attribute__((ext_vector_type(32)));
 typedef int intx6 __attribute__((ext_vector_type(6)));
 typedef unsigned short ushortx2 __attribute__((ext_vector_type(2)));
+
+// ---------------------------------------------------------------------------------------------
+// The steps the forms of the preparation share: prep_chunk_kernel, prep_stream_kernel, prep_once_kernel and
+// prep_mx6_rows_kernel call these, so "the same arithmetic on the same values, bit for bit" holds by construction.  The order of
+// the floating-point operations inside each is part of the images' definition (-ffp-contract=off).  Only store_group takes a
+// kernel's `const PrepOut& o` (there it is what keeps prep_chunk_kernel's lines); the others get the pointers they need, or a
+// PrepOut, by value (see group_tail).  Where a call moved a line of a kernel's resource usage, that kernel keeps a copy of the
+// step, marked with the figure that moved (profiles/prep_steps_refactor.md).
+// ---------------------------------------------------------------------------------------------
+// (the maxima of a group -- amax_bits, emax_bits, ... -- are collected in the LDS as bits: uint order == float order for values >= 0
+// and +Inf.  Each kernel declares the five as separate variables: the forms that never touch one do not pay for it.)
+
+// Eight per-row sums per lane -> one per lane: a reduce-scatter over the xor-32 / 16 / 8 levels (the lane keeps half of its rows
+// at every level and adds the partner's partial of those rows), then the xor-4 / 2 / 1 levels on the single value.  Every
+// addition pairs the same two partials as row_sumsq_wave's butterfly (which computes each of them in both lanes), so the sum is
+// bit-identical to the oracle's; 10 shuffles instead of 48.  Afterwards lane l holds row l >> 3.
+__device__ __forceinline__ float scatter8(const float* p, int lane) {
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
+    float q4[4], q2[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q4[j] = (b5 ? p[j + 4] : p[j]) + __shfl_xor(b5 ? p[j] : p[j + 4], 32);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) q2[j] = (b4 ? q4[j + 2] : q4[j]) + __shfl_xor(b4 ? q4[j] : q4[j + 2], 16);
+    float q1 = (b3 ? q2[1] : q2[0]) + __shfl_xor(b3 ? q2[0] : q2[1], 8);
+    q1 = q1 + __shfl_xor(q1, 4);
+    q1 = q1 + __shfl_xor(q1, 2);
+    q1 = q1 + __shfl_xor(q1, 1);
+    return q1;
+}
+
+// a chunk's squares onto a sum in the oracle's order (lane-sequential over its elements, as row_sumsq_wave):
+// ((((p + x^2) + y^2) + z^2) + w^2)
+__device__ __forceinline__ float fold4(float p, const float4& t) {
+    float q;
+    q = t.x * t.x; p = p + q;
+    q = t.y * t.y; p = p + q;
+    q = t.z * t.z; p = p + q;
+    q = t.w * t.w; p = p + q;
+    return p;
+}
+
+// The group's quantisation step from its largest normalised magnitude: s = amax / 127 (no clipping, no tuning constant).  A
+// group without a finite positive maximum (zero rows only, or an Inf / NaN element): step 1 and every code 0 -- the measured
+// residual then says what the image is worth.
+__device__ __forceinline__ void group_step(float amax, float& qstep, float& inv_qstep) {
+    const bool usable = amax > 0.0f && amax < 3.0e38f;
+    qstep = usable ? amax / 127.0f : 1.0f;
+    inv_qstep = usable ? 127.0f / amax : 0.0f;
+}
+
+// Four normalised values to int8 codes (returned packed, the first in the low byte) and their squared residuals onto e2:
+// q = rint(v / s), e = v - s q by one fma -- measured, not assumed.  CLAMP: q to [-127, 127] (a NaN becomes -127: any integer is
+// valid, the residual turns E into Inf); a caller that proves the range leaves the clamp out.
+template <bool CLAMP>
+__device__ __forceinline__ unsigned quant4(const float (&nv)[4], float qstep, float inv_qstep, float& e2) {
+    int qi[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float qf = rintf(nv[e] * inv_qstep);
+        if constexpr (CLAMP) qf = fminf(fmaxf(qf, -127.0f), 127.0f);
+        const float res = __builtin_fmaf(-qstep, qf, nv[e]);
+        e2 = __builtin_fmaf(res, res, e2);
+        qi[e] = (int)qf;
+    }
+    // low bytes of the four integers: two byte permutes and an or
+    return __builtin_amdgcn_perm((unsigned)qi[1], (unsigned)qi[0], 0x0c0c0400u) |
+           __builtin_amdgcn_perm((unsigned)qi[3], (unsigned)qi[2], 0x04000c0cu);
+}
+
+// fp32 -> fp16 of four values as a rounding of its own: the values are hidden from the compiler, which otherwise turns the
+// product that made them and the conversion into one v_fma_mixlo_f16 -- a single rounding -- in SOME instantiations: 1 % of the
+// rows then carry an fp16 value one ulp off the definition, and E differs between the forms of the preparation.
+__device__ __forceinline__ half4 round_half4(const float (&nv)[4]) {
+    float nh[4] = {nv[0], nv[1], nv[2], nv[3]};
+    asm volatile("" : "+v"(nh[0]), "+v"(nh[1]), "+v"(nh[2]), "+v"(nh[3]));
+    half4 h;
+    h[0] = (_Float16)nh[0];
+    h[1] = (_Float16)nh[1];
+    h[2] = (_Float16)nh[2];
+    h[3] = (_Float16)nh[3];
+    return h;
+}
+
+// A norm from its sum of squares, rounded UP, + c: the fp32 sum of d non-negative terms is within (d + 8) 2^-24 of exact and sqrtf
+// within 2^-24, the factor 1 + 2^-12 covers both for every d <= 768.  FROM_F16 (the int8 E of the one-read form, quantised from the
+// fp16 copy): |h - s q|_2 measured + |v - h|_2 bounded by PREP_F16_ROUNDING, the sum rounded up by one more ulp.  NaN (an Inf / NaN
+// element) or `absent` (no such image) -> +Inf: nothing is ever pruned against such a row; a padding row -> 0.
+template <bool FROM_F16 = false>
+__device__ __forceinline__ float norm_up(float sumsq, float c, bool absent, bool padding) {
+    float n = sqrtf(sumsq) * 1.000244140625f;
+    if constexpr (FROM_F16) n = (n + PREP_F16_ROUNDING) * 1.0000002384185791f;
+    n = n + c;
+    if (!(n == n) || absent) n = __builtin_inff();
+    if (padding) n = 0.0f;
+    return n;
+}
+
+// One (row, 32-column block) of the fp6 image from its 32 halves: the scale 2^e with max / 2^e <= 7.75 (the largest code is 7.5;
+// up to 7.75 rounds there with the half-step error of its binade) -- am = (1 + f) 2^x: e = x - 2 when 1 + f <= 1.9375, else x - 1;
+// Inf / NaN blocks: scale 1 (the residual turns E into Inf); normalised finite rows: e <= -2 --, the conversion (round to nearest
+// even, saturating), and the squared residual against the halves, MEASURED: the codes converted back at scale 1 are exact in fp16.
+// Returns the codes; ex = the scale's exponent (the E8M0 byte is ex + 127), e6 = the squared residual.
+union Block6 {
+    uint4 u[4];
+    halfx32 h;
+    unsigned w[16];
+};
+__device__ __forceinline__ intx6 convert_block6(const Block6& v, int& ex, float& e6) {
+    ushortx2 m2 = {0, 0};   // packed maximum of the magnitudes (as 15-bit integers: the order of non-negative halves)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const unsigned a2 = v.w[i] & 0x7fff7fffu;
+        m2 = __builtin_elementwise_max(m2, *reinterpret_cast<const ushortx2*>(&a2));
+    }
+    const unsigned am = max((unsigned)m2[0], (unsigned)m2[1]);
+    ex = (int)(am >> 10) - 15 - ((am & 0x3ffu) <= 0x3c0u ? 2 : 1);
+    ex = ex > 0 ? 0 : ex;
+    const float sc6 = __uint_as_float((unsigned)(ex + 127) << 23);
+    const intx6 codes = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v.h, sc6);
+    const halfx32 back = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(codes, 1.0f);
+    e6 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const float res = __builtin_fmaf(-(float)back[i], sc6, (float)v.h[i]);
+        e6 = __builtin_fmaf(res, res, e6);
+    }
+    return codes;
+}
+
+// a block's 24 code bytes to MFMA lane l6 of k-step s6 of a tile: 16 to the first code plane, 8 to the second.  NT: the tile is in
+// global memory and is written once, as six non-temporal words; otherwise (the LDS, or the rows kernel's global tile) plain stores
+template <bool NT>
+__device__ __forceinline__ void store_codes(unsigned char* tile, int s6, int l6, const intx6& codes) {
+    if constexpr (NT) {
+        unsigned* pa = reinterpret_cast<unsigned*>(tile + mx6_code_a(s6, l6));
+        __builtin_nontemporal_store((unsigned)codes[0], pa);
+        __builtin_nontemporal_store((unsigned)codes[1], pa + 1);
+        __builtin_nontemporal_store((unsigned)codes[2], pa + 2);
+        __builtin_nontemporal_store((unsigned)codes[3], pa + 3);
+        unsigned* pb = reinterpret_cast<unsigned*>(tile + mx6_code_b(s6, l6));
+        __builtin_nontemporal_store((unsigned)codes[4], pb);
+        __builtin_nontemporal_store((unsigned)codes[5], pb + 1);
+    } else {
+        *reinterpret_cast<uint4*>(tile + mx6_code_a(s6, l6)) = make_uint4((unsigned)codes[0], (unsigned)codes[1], (unsigned)codes[2], (unsigned)codes[3]);
+        *reinterpret_cast<uint2*>(tile + mx6_code_b(s6, l6)) = make_uint2((unsigned)codes[4], (unsigned)codes[5]);
+    }
+}
+
+// the d / 64 scales of MFMA lane (hh, r & 31) of row r's tile: its 8 bytes of the scale plane, from the group's block scales
+// sc[128 rows][16] (byte s6 = the scale of block 2 s6 + hh)
+__device__ __forceinline__ void store_scales(unsigned char* tile, int ks, const unsigned char* sc, int r, int hh, int nconv) {
+    unsigned lo = 0u, hi = 0u;
+    for (int s6 = 0; s6 < (nconv >> 1); ++s6) {
+        const unsigned b = sc[r * 16 + 2 * s6 + hh];
+        if (s6 < 4) lo |= b << (8 * s6);
+        else hi |= b << (8 * (s6 - 4));
+    }
+    *reinterpret_cast<uint2*>(tile + mx6_scale_at(ks, 0, hh * 32 + (r & 31))) = make_uint2(lo, hi);
+}
+
+// (E of the fp6 image per row -- the blocks' squared residuals summed in order, rounded up like norm_up, HALF -> +Inf, padding -> 0,
+// two atomicMax -- is NOT shared: as a function, with any signature, it moved a line of prep_chunk_kernel<false, 2, true, 8> (255 ->
+// 254 VGPRs) or of prep_once_kernel<256, true, true, true> (61 -> 62 SGPRs).  Its four copies -- prep_chunk_kernel,
+// prep_stream_kernel, group_tail, prep_mx6_rows_kernel -- are marked "E6 per row: one of four copies".)
+
+// A group's data, by one thread behind the barrier that follows the last atomicMax.  I8: there is an int8 image (step, largest E);
+// MX6: there is an fp6 image -- without one its E says so: a search that asks for an fp6 record kind on such an operand bounds
+// nothing and ends in the exact all-pairs decision (correct, slow) instead of trusting stale bytes.
+template <bool I8, bool MX6>
+__device__ __forceinline__ void store_group(const PrepOut& o, int grp, float qstep, const unsigned& emax_bits, const unsigned& rmax_bits,
+                                            const unsigned& e6max_bits, const unsigned& e6hmax_bits) {
+    if constexpr (I8) {
+        o.gstep[grp] = qstep;
+        o.gerr[grp] = __uint_as_float(emax_bits);
+    }
+    o.grest[grp] = __uint_as_float(rmax_bits);
+    if constexpr (MX6) {
+        o.gerr6[grp] = __uint_as_float(e6max_bits);
+        o.gerr6h[grp] = __uint_as_float(e6hmax_bits);
+        o.gstep6[grp] = MX6_FIX_STEP;
+    } else if (o.gerr6) {
+        o.gerr6[grp] = o.gerr6h[grp] = __builtin_inff();
+        o.gstep6[grp] = 0.0f;
+    }
+}
+
+// The group's tail of prep_once_kernel (every instantiation), behind the last batch: the scale planes of its four fp6 tiles from the
+// block scales l_sc[128][16], E of the fp6 image per row from l_e6[block][128], the group's data.  tid: the thread's index as the
+// kernel holds it.  (o by VALUE: a reference to the kernel's own `o` handed to a function made the compiler load every field of BOTH
+// operands' PrepOut up front -- 43 -> 86 SGPRs, spills in the persistent forms.  prep_stream_kernel keeps the tail as its own copy:
+// through this function <384, false> was 0.8 % slower, its fields loaded in one block behind the last batch.)
+template <int D, bool HALF, bool NOI8>
+__device__ __forceinline__ void group_tail(const PrepOut o, int grp, int64_t rows, int tid, const unsigned char* l_sc, const float* l_e6,
+                                           float qstep, unsigned& emax_bits, unsigned& rmax_bits, unsigned& e6max_bits, unsigned& e6hmax_bits) {
+    constexpr int NBLK = D >> 5, nconv = HALF ? NBLK >> 1 : NBLK;
+    __syncthreads();
+    {
+        const int r = tid & (I8_GROUP - 1), hh = tid >> 7;
+        unsigned char* t6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + (r >> 5)) * (size_t)mx6_tile_bytes(D >> 6);
+        store_scales(t6, D >> 6, l_sc, r, hh, nconv);
+    }
+    if (tid < I8_GROUP) {   // E6 per row: one of four copies.  Blocks in order; rounded up like the int8 one
+        const int r = tid;
+        float acc = 0.0f, acch = 0.0f;
+        for (int blk = 0; blk < nconv; ++blk) {
+            acc = acc + l_e6[blk * I8_GROUP + r];
+            if (blk + 1 == (NBLK >> 1)) acch = acc;
+        }
+        float e6n = sqrtf(acc) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
+        float e6h = sqrtf(acch) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
+        if (!(e6n == e6n) || HALF) e6n = __builtin_inff();
+        if (!(e6h == e6h)) e6h = __builtin_inff();
+        const int64_t row = (int64_t)grp * I8_GROUP + r;
+        if (row >= rows) e6n = e6h = 0.0f;
+        o.err6[row] = e6n;
+        o.err6h[row] = e6h;
+        if (e6n > 0.0f) atomicMax(&e6max_bits, __float_as_uint(e6n));
+        if (e6h > 0.0f) atomicMax(&e6hmax_bits, __float_as_uint(e6h));
+    }
+    __syncthreads();
+    if (tid == 0) store_group<!NOI8, true>(o, grp, qstep, emax_bits, rmax_bits, e6max_bits, e6hmax_bits);
+}
+
 // WAVES = 8 (the MX6 form): 8 waves x 16 rows -- half the threads, twice the registers each: room for the conversion AND for the
 // next group's rows, which the 16-wave form had to read after it (128 registers: 49 spilled, the loads exposed; 0.21 ms)
 template <bool F16, int NC = 2, bool MX6 = false, int WAVES = 16>
@@ -173,23 +398,6 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
             v[j][i] = t;
         }
     };
-    // Eight per-row sums per lane -> one per lane: a reduce-scatter over the xor-32 / 16 / 8 levels (the lane keeps half of
-    // its rows at every level and adds the partner's partial of those rows), then the xor-4 / 2 / 1 levels on the single
-    // value.  Every addition pairs the same two partials as row_sumsq_wave's butterfly (which computes each of them in both
-    // lanes), so the sum is bit-identical to the oracle's; 10 shuffles instead of 48.  Afterwards lane l holds row l >> 3.
-    auto scatter8 = [&](const float* p) __attribute__((always_inline)) {
-        const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
-        float q4[4], q2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q4[j] = (b5 ? p[j + 4] : p[j]) + __shfl_xor(b5 ? p[j] : p[j + 4], 32);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) q2[j] = (b4 ? q4[j + 2] : q4[j]) + __shfl_xor(b4 ? q4[j] : q4[j + 2], 16);
-        float q1 = (b3 ? q2[1] : q2[0]) + __shfl_xor(b3 ? q2[0] : q2[1], 8);
-        q1 = q1 + __shfl_xor(q1, 4);
-        q1 = q1 + __shfl_xor(q1, 2);
-        q1 = q1 + __shfl_xor(q1, 1);
-        return q1;
-    };
     if ((int)blockIdx.x < groups) {
 #pragma unroll
         for (int j = 0; j < RPW; ++j) load_row(blockIdx.x, j);
@@ -203,24 +411,18 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
         // phase 1: 1/|row| in the oracle's order, the group's largest normalised magnitude
         float part[RPW];
 #pragma unroll
-        for (int j = 0; j < RPW; ++j) {  // lane-sequential over its chunks and elements, as row_sumsq_wave
+        for (int j = 0; j < RPW; ++j) {  // lane-sequential over its chunks
             float p = 0.0f;
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
-                if (lane + 64 * i < nchunks) {
-                    float t;
-                    t = v[j][i].x * v[j][i].x; p = p + t;
-                    t = v[j][i].y * v[j][i].y; p = p + t;
-                    t = v[j][i].z * v[j][i].z; p = p + t;
-                    t = v[j][i].w * v[j][i].w; p = p + t;
-                }
+                if (lane + 64 * i < nchunks) p = fold4(p, v[j][i]);
             }
             part[j] = p;
         }
         float my_inv[RPW / 8];   // of row 8 hb + (lane >> 3): eight rows in one evaluation
 #pragma unroll
         for (int hb = 0; hb < RPW / 8; ++hb) {
-            my_inv[hb] = inv_norm_from_sumsq(scatter8(part + 8 * hb));
+            my_inv[hb] = inv_norm_from_sumsq(scatter8(part + 8 * hb, lane));
             if ((lane & 7) == 0) o.inv[(int64_t)grp * I8_GROUP + wave * RPW + 8 * hb + (lane >> 3)] = my_inv[hb];
         }
         float lmax = 0.0f;
@@ -241,10 +443,8 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
         __syncthreads();  // amax_bits / emax_bits initialised; the previous group's image has left the LDS
         if (lane == 0 && lmax > 0.0f) atomicMax(&amax_bits, __float_as_uint(lmax));  // finite or +Inf: uint order == float order
         __syncthreads();
-        const float amax = __uint_as_float(amax_bits);
-        const bool usable = amax > 0.0f && amax < 3.0e38f;
-        const float qstep = usable ? amax / 127.0f : 1.0f;
-        const float inv_qstep = usable ? 127.0f / amax : 0.0f;
+        float qstep, inv_qstep;
+        group_step(__uint_as_float(amax_bits), qstep, inv_qstep);
         // phase 2: quantise from the registers; each row's registers then take the same row of the next group
         float rpart[RPW];
 #pragma unroll
@@ -262,19 +462,8 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
 #endif
                     const float nv[4] = {v[j][i].x, v[j][i].y, v[j][i].z, v[j][i].w};
                     if (8 * c >= d) r2 = r2 + (nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] + nv[3] * nv[3]);  // columns >= d / 2
-                    int qi[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float qf = rintf(nv[e] * inv_qstep);
-                        qf = fminf(fmaxf(qf, -127.0f), 127.0f);                // (a NaN becomes -127: any integer is valid,
-                        const float res = __builtin_fmaf(-qstep, qf, nv[e]);   //  the residual is measured: it turns E into Inf)
-                        e2 = __builtin_fmaf(res, res, e2);
-                        qi[e] = (int)qf;
-                    }
-                    // low bytes of the four integers: two byte permutes and an or
-                    const unsigned packed = __builtin_amdgcn_perm((unsigned)qi[1], (unsigned)qi[0], 0x0c0c0400u) |
-                                            __builtin_amdgcn_perm((unsigned)qi[3], (unsigned)qi[2], 0x04000c0cu);
-                    *reinterpret_cast<unsigned*>(img8 + (size_t)t * (d * 32) + (((c >> 3) * 2 + ((c >> 2) & 1)) * 32 + p) * 16 + (c & 3) * 4) = packed;
+                    *reinterpret_cast<unsigned*>(img8 + (size_t)t * (d * 32) + (((c >> 3) * 2 + ((c >> 2) & 1)) * 32 + p) * 16 + (c & 3) * 4) =
+                        quant4<true>(nv, qstep, inv_qstep, e2);
                     if constexpr (F16 || MX6) {
                         half4 h;
                         h[0] = (_Float16)nv[0];
@@ -292,27 +481,19 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
         }
 #pragma unroll
         for (int hb = 0; hb < RPW / 8; ++hb) {
-            // |e|_2 of row lane >> 3, rounded up: the fp32 sum of d non-negative terms is within (d + 8) 2^-24 of exact, sqrtf
-            // within 2^-24
-            float en = sqrtf(scatter8(part + 8 * hb)) * 1.000244140625f + 1.0e-30f;
-            if (!(en == en)) en = __builtin_inff();
+            // |e|_2 of row lane >> 3, rounded up
             const int64_t r = (int64_t)grp * I8_GROUP + wave * RPW + 8 * hb + (lane >> 3);
-            if (r >= rows) en = 0.0f;
+            const float en = norm_up(scatter8(part + 8 * hb, lane), 1.0e-30f, false, r >= rows);
             if ((lane & 7) == 0) {
                 o.err[r] = en;
                 if (en > 0.0f) atomicMax(&emax_bits, __float_as_uint(en));
-                // no fp6 image in this form: its E says so -- a search that asks for an fp6 record kind on such an operand bounds
-                // nothing and ends in the exact all-pairs decision (correct, slow) instead of trusting stale bytes
-                if constexpr (!MX6) {
+                if constexpr (!MX6) {   // no fp6 image in this form: its E says so (store_group)
                     if (o.err6) o.err6[r] = o.err6h[r] = __builtin_inff();
                 }
             }
             {   // (the MX6 form keeps these: VFM_RECORDS_MX6_HALF bounds the second half of the columns with them)
-                // |second half of the row|_2, rounded up like E (d / 2 + 8 roundings of 2^-24 on non-negative terms, one sqrtf);
-                // NaN / Inf elements -> Inf: nothing is ever pruned against such a row
-                float rn = sqrtf(scatter8(rpart + 8 * hb)) * 1.000244140625f + 1.0e-30f;
-                if (!(rn == rn)) rn = __builtin_inff();
-                if (r >= rows) rn = 0.0f;
+                // |second half of the row|_2, rounded up like E
+                const float rn = norm_up(scatter8(rpart + 8 * hb, lane), 1.0e-30f, false, r >= rows);
                 if ((lane & 7) == 0) {
                     o.rest[r] = rn;
                     if (rn > 0.0f) atomicMax(&rmax_bits, __float_as_uint(rn));
@@ -329,12 +510,7 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
 #else
             for (int u = threadIdx.x; u < u8n; u += NT) {
 #endif
-                const uint4 tq = src[u];
-                unsigned* po = reinterpret_cast<unsigned*>(dst + u);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
+                store_nt(dst + u, src[u]);
             }
         }
         if (o.rows8) {   // ... and row-major (scan-sized operands): unit un of row `row` sits at tile row >> 5, column un, row & 31
@@ -352,12 +528,7 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
             const uint4* src = reinterpret_cast<const uint4*>(img8);
             for (int u = threadIdx.x; u < uh * 4; u += NT) {
                 const int t = u / uh, w = u % uh;
-                const uint4 tq = src[t * (2 * uh) + w];
-                unsigned* po = reinterpret_cast<unsigned*>(dst + u);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
+                store_nt(dst + u, src[t * (2 * uh) + w]);
             }
         }
 #ifdef VFM_PABL_NOMX6
@@ -377,54 +548,23 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
                 const int r = item & (I8_GROUP - 1), blk = item >> 7, t = r >> 5, p = r & 31;
                 // the block's 32 halves: fp16 units (k-step 2 blk + u, half hh) of row p, in column order
                 const uint4* up = reinterpret_cast<const uint4*>(img16 + (size_t)t * (d * 32)) + (4 * blk) * 32 + p;
-                union {
-                    uint4 u[4];
-                    halfx32 h;
-                    unsigned w[16];
-                } v;
+                Block6 v;
                 v.u[0] = up[0];
                 v.u[1] = up[32];
                 v.u[2] = up[64];
                 v.u[3] = up[96];
-                ushortx2 m2 = {0, 0};   // packed maximum of the magnitudes (as 15-bit integers: the order of non-negative halves)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const unsigned a2 = v.w[i] & 0x7fff7fffu;
-                    m2 = __builtin_elementwise_max(m2, *reinterpret_cast<const ushortx2*>(&a2));
-                }
-                const unsigned am = max((unsigned)m2[0], (unsigned)m2[1]);
-                // am = (1 + f) 2^x: e = x - 2 when 1 + f <= 1.9375 (max / 2^e <= 7.75), else x - 1; Inf / NaN blocks: scale 1 (the
-                // residual turns E into Inf); normalised finite rows: e <= -2
-                int ex = (int)(am >> 10) - 15 - ((am & 0x3ffu) <= 0x3c0u ? 2 : 1);
-                ex = ex > 0 ? 0 : ex;
-                const float sc6 = __uint_as_float((unsigned)(ex + 127) << 23);
-                const intx6 codes = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v.h, sc6);
-                const halfx32 back = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(codes, 1.0f);   // the code values: exact in fp16
-                float e6 = 0.0f;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) {
-                    const float res = __builtin_fmaf(-(float)back[i], sc6, (float)v.h[i]);
-                    e6 = __builtin_fmaf(res, res, e6);
-                }
-                const int s6 = blk >> 1, l6 = (blk & 1) * 32 + p;
-                unsigned char* tile6 = img6 + (size_t)t * tb6;
-                *reinterpret_cast<uint4*>(tile6 + mx6_code_a(s6, l6)) =
-                    make_uint4((unsigned)codes[0], (unsigned)codes[1], (unsigned)codes[2], (unsigned)codes[3]);
-                *reinterpret_cast<uint2*>(tile6 + mx6_code_b(s6, l6)) = make_uint2((unsigned)codes[4], (unsigned)codes[5]);
+                int ex;
+                float e6;
+                const intx6 codes = convert_block6(v, ex, e6);
+                store_codes<false>(img6 + (size_t)t * tb6, blk >> 1, (blk & 1) * 32 + p, codes);
                 scb[r * 16 + blk] = (unsigned char)(ex + 127);
                 e6p[blk * I8_GROUP + r] = e6;
             }
             __syncthreads();
-            if (threadIdx.x < 2 * I8_GROUP) {   // the d / 64 scales of MFMA lane (hh, p) of tile t: its 8 bytes of the scale plane
+            if (threadIdx.x < 2 * I8_GROUP) {
                 const int r = threadIdx.x & (I8_GROUP - 1), hh = threadIdx.x >> 7;
-                unsigned lo = 0u, hi = 0u;
-                for (int s6 = 0; s6 < (nconv >> 1); ++s6) {
-                    const unsigned b = scb[r * 16 + 2 * s6 + hh];
-                    if (s6 < 4) lo |= b << (8 * s6);
-                    else hi |= b << (8 * (s6 - 4));
-                }
-                *reinterpret_cast<uint2*>(img6 + (size_t)(r >> 5) * tb6 + mx6_scale_at(d >> 6, 0, hh * 32 + (r & 31))) = make_uint2(lo, hi);
-            } else if (threadIdx.x < 3 * I8_GROUP) {   // E of the fp6 image per row: blocks in order; rounded up like the int8 one
+                store_scales(img6 + (size_t)(r >> 5) * tb6, d >> 6, scb, r, hh, nconv);
+            } else if (threadIdx.x < 3 * I8_GROUP) {   // E6 per row: one of four copies.  Blocks in order; rounded up like the int8 one
                 const int r = threadIdx.x - 2 * I8_GROUP;
                 float acc = 0.0f, acch = 0.0f;
                 for (int blk = 0; blk < nconv; ++blk) {
@@ -453,26 +593,14 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
             for (int uu = threadIdx.x; uu < 4 * u6p; uu += NT) {
 #endif
                 const int u = (uu / u6p) * u6t + uu % u6p;
-                const uint4 tq = src[u];
-                unsigned* po = reinterpret_cast<unsigned*>(dst + u);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
+                store_nt(dst + u, src[u]);
             }
         }
         if constexpr (F16) {
             const int u16n = (d >> 4) * 64 * 4;
             uint4* dst = o.tiles + (int64_t)grp * u16n;
             const uint4* src = reinterpret_cast<const uint4*>(img16);
-            for (int u = threadIdx.x; u < u16n; u += NT) {
-                const uint4 tq = src[u];
-                unsigned* po = reinterpret_cast<unsigned*>(dst + u);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
-            }
+            for (int u = threadIdx.x; u < u16n; u += NT) store_nt(dst + u, src[u]);
         }
         if constexpr (MX6 && WAVES != 8) {
             if (gnext < groups) {
@@ -481,18 +609,10 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
             }
         }
         if (threadIdx.x == 0) {
-            o.gstep[grp] = qstep;
-            o.gerr[grp] = __uint_as_float(emax_bits);
-            o.grest[grp] = __uint_as_float(rmax_bits);
+            store_group<true, MX6>(o, grp, qstep, emax_bits, rmax_bits, e6max_bits, e6hmax_bits);
             if constexpr (MX6) {
-                o.gerr6[grp] = __uint_as_float(e6max_bits);
-                o.gerr6h[grp] = __uint_as_float(e6hmax_bits);
-                o.gstep6[grp] = MX6_FIX_STEP;
                 e6max_bits = 0u;
                 e6hmax_bits = 0u;
-            } else if (o.gerr6) {
-                o.gerr6[grp] = o.gerr6h[grp] = __builtin_inff();
-                o.gstep6[grp] = 0.0f;
             }
             amax_bits = 0u;   // for the next group (read again only behind the next two barriers)
             emax_bits = 0u;
@@ -514,11 +634,12 @@ __global__ __launch_bounds__(WAVES * 64) void prep_chunk_kernel(Rows x1, int64_t
 // registers, ~45 KB of LDS.  The dispatcher places such a workgroup on a compute unit that is running a coarse workgroup (332 of
 // 512 registers per SIMD lane, 90 of 160 KB), its loads and VALU work run under the other's MFMAs.
 //   wave w = rows 32 w .. of the group = one fragment tile of every image; batch b = rows 8 b .. of the tile.
-//   pass 1: per batch the rows' sums of squares (oracle order: lane l owns chunks l, l + 64), 1 / |row| (scatter8), the largest
-//           normalised magnitude; the batch's registers then take the next batch.
-//   pass 2: per batch quantise (as prep_chunk_kernel: same arithmetic, same order -- the images and every E are bit-identical to
-//           its), transpose through a 3 KB per-wave slice of the LDS and store 128-byte runs (8 rows of a 16-byte unit column);
-//           the fp16 values of the columns the fp6 image covers go through the LDS the same way: lane = (row, 32-column block).
+//   pass 1: per batch the rows' sums of squares (oracle order: fold4 over the lane's chunks l, l + 64), 1 / |row| (scatter8), the
+//           largest normalised magnitude; the batch's registers then take the next batch.
+//   pass 2: per batch quantise (group_step, quant4<true>: prep_chunk_kernel calls the same functions; E and the rest by norm_up's
+//           lines -- the images and every E are bit-identical to its), transpose through a 3 KB per-wave slice of the LDS and store 128-byte runs (8 rows of
+//           a 16-byte unit column); the fp16 values of the columns the fp6 image covers go through the LDS the same way: lane =
+//           (row, 32-column block), converted by convert_block6's arithmetic (a copy here, see below); then the group's tail (group_tail's steps, a copy).
 // ---------------------------------------------------------------------------------------------
 template <int D, bool HALF>
 __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __restrict__ x1, int64_t rows1, PrepOut o1, int groups1,
@@ -579,19 +700,6 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
             v[j][i] = t;
         }
     };
-    auto scatter8 = [&](const float* p) __attribute__((always_inline)) {   // (prep_chunk_kernel's: lane l ends with row l >> 3)
-        const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
-        float q4[4], q2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q4[j] = (b5 ? p[j + 4] : p[j]) + __shfl_xor(b5 ? p[j] : p[j + 4], 32);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) q2[j] = (b4 ? q4[j + 2] : q4[j]) + __shfl_xor(b4 ? q4[j] : q4[j + 2], 16);
-        float q1 = (b3 ? q2[1] : q2[0]) + __shfl_xor(b3 ? q2[0] : q2[1], 8);
-        q1 = q1 + __shfl_xor(q1, 4);
-        q1 = q1 + __shfl_xor(q1, 2);
-        q1 = q1 + __shfl_xor(q1, 1);
-        return q1;
-    };
     // ---- pass 1
 #pragma unroll
     for (int j = 0; j < 8; ++j) load_row_keep(0, j);
@@ -604,17 +712,11 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
             float p = 0.0f;
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
-                if (lane + 64 * i < NCH) {
-                    float t;
-                    t = v[j][i].x * v[j][i].x; p = p + t;
-                    t = v[j][i].y * v[j][i].y; p = p + t;
-                    t = v[j][i].z * v[j][i].z; p = p + t;
-                    t = v[j][i].w * v[j][i].w; p = p + t;
-                }
+                if (lane + 64 * i < NCH) p = fold4(p, v[j][i]);
             }
             part[j] = p;
         }
-        const float my_inv = inv_norm_from_sumsq(scatter8(part));   // of row lane >> 3 of the batch
+        const float my_inv = inv_norm_from_sumsq(scatter8(part, lane));   // of row lane >> 3 of the batch
         if ((lane & 7) == 0) {
             l_inv[wave * 32 + 8 * b + (lane >> 3)] = my_inv;
             o.inv[row0 + 8 * b + (lane >> 3)] = my_inv;
@@ -634,15 +736,12 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
     __syncthreads();   // the maxima are initialised
     if (lane == 0 && lmax > 0.0f) atomicMax(&amax_bits, __float_as_uint(lmax));
     __syncthreads();
-    const float amax = __uint_as_float(amax_bits);
-    const bool usable = amax > 0.0f && amax < 3.0e38f;
-    const float qstep = usable ? amax / 127.0f : 1.0f;
-    const float inv_qstep = usable ? 127.0f / amax : 0.0f;
+    float qstep, inv_qstep;
+    group_step(__uint_as_float(amax_bits), qstep, inv_qstep);
     // ---- pass 2
     unsigned char* my8 = l_i8[wave];
     unsigned char* my16 = l_h16[wave];
-    const int tb6 = mx6_tile_bytes(D >> 6);
-    unsigned char* tile6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + wave) * (size_t)tb6;
+    unsigned char* tile6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + wave) * (size_t)mx6_tile_bytes(D >> 6);
     uint4* tile8 = o.tiles8 + ((size_t)grp * 4 + wave) * (size_t)(NU * 32);
     uint4* tile8h = o.tiles8h + ((size_t)grp * 4 + wave) * (size_t)((NU >> 1) * 32);
 #pragma unroll 1
@@ -659,31 +758,10 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
                     // normalised values exactly as faiss leaves them in fp32
                     const float nv[4] = {v[j][i].x * iv, v[j][i].y * iv, v[j][i].z * iv, v[j][i].w * iv};
                     if (8 * c >= D) r2 = r2 + (nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] + nv[3] * nv[3]);  // columns >= d / 2
-                    int qi[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float qf = rintf(nv[e] * inv_qstep);
-                        qf = fminf(fmaxf(qf, -127.0f), 127.0f);
-                        const float res = __builtin_fmaf(-qstep, qf, nv[e]);
-                        e2 = __builtin_fmaf(res, res, e2);
-                        qi[e] = (int)qf;
-                    }
-                    const unsigned packed = __builtin_amdgcn_perm((unsigned)qi[1], (unsigned)qi[0], 0x0c0c0400u) |
-                                            __builtin_amdgcn_perm((unsigned)qi[3], (unsigned)qi[2], 0x04000c0cu);
-                    *reinterpret_cast<unsigned*>(my8 + j * RS8 + 4 * c) = packed;
+                    *reinterpret_cast<unsigned*>(my8 + j * RS8 + 4 * c) = quant4<true>(nv, qstep, inv_qstep, e2);
                     if (c < 8 * nconv) {   // quarter k of (row, block): 8 halves = chunks 2 k, 2 k + 1 of the block
-                        // (the fp32 product is rounded to fp16: hidden from the compiler, which otherwise turns product + conversion into
-                        // one v_fma_mixlo_f16 -- a single rounding -- in SOME instantiations of this kernel: 1 % of the rows then carry an
-                        // fp16 value one ulp off the definition, and E differs between the forms of the preparation)
-                        float nh[4] = {nv[0], nv[1], nv[2], nv[3]};
-                        asm volatile("" : "+v"(nh[0]), "+v"(nh[1]), "+v"(nh[2]), "+v"(nh[3]));
-                        half4 h;
-                        h[0] = (_Float16)nh[0];
-                        h[1] = (_Float16)nh[1];
-                        h[2] = (_Float16)nh[2];
-                        h[3] = (_Float16)nh[3];
                         const int blk = c >> 3, k = (c & 7) >> 1, sub = c & 1;
-                        *reinterpret_cast<half4*>(my16 + ((size_t)(k * nitems + j * nconv + blk) * 16 + sub * 8)) = h;
+                        *reinterpret_cast<half4*>(my16 + ((size_t)(k * nitems + j * nconv + blk) * 16 + sub * 8)) = round_half4(nv);
                     }
                 }
             }
@@ -692,9 +770,10 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
             if (b < 3) load_row(b + 1, j);
         }
         {
-            float en = sqrtf(scatter8(part)) * 1.000244140625f + 1.0e-30f;
+            // (norm_up's lines for E and the rest together, kept as a copy with the kernel's tail: see there)
+            float en = sqrtf(scatter8(part, lane)) * 1.000244140625f + 1.0e-30f;
             if (!(en == en)) en = __builtin_inff();
-            float rn = sqrtf(scatter8(rpart)) * 1.000244140625f + 1.0e-30f;
+            float rn = sqrtf(scatter8(rpart, lane)) * 1.000244140625f + 1.0e-30f;
             if (!(rn == rn)) rn = __builtin_inff();
             const int64_t r = row0 + 8 * b + (lane >> 3);
             if (r >= rows) en = rn = 0.0f;
@@ -709,23 +788,15 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // int8: unit column u of the batch's 8 rows = 128 consecutive bytes of the tile
+        // (this batch store -- tile, tiles8h twin, rows8 copy -- stands a second time in prep_once_kernel: as one function it moved that
+        // kernel's VGPRs, 137 -> 141 at <256, false, false>.  Change both.)
 #pragma unroll
         for (int rd = 0; rd < (NU * 8 + 63) / 64; ++rd) {
             const int e = rd * 64 + lane, u = e >> 3, j = e & 7;
             if (e < NU * 8) {
                 const uint4 tq = *reinterpret_cast<const uint4*>(my8 + j * RS8 + 16 * u);
-                unsigned* po = reinterpret_cast<unsigned*>(tile8 + u * 32 + 8 * b + j);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
-                if (!HALF && u < (NU >> 1)) {   // the first d / 2 columns again, as tiles of their own
-                    unsigned* ph = reinterpret_cast<unsigned*>(tile8h + u * 32 + 8 * b + j);
-                    __builtin_nontemporal_store(tq.x, ph);
-                    __builtin_nontemporal_store(tq.y, ph + 1);
-                    __builtin_nontemporal_store(tq.z, ph + 2);
-                    __builtin_nontemporal_store(tq.w, ph + 3);
-                }
+                store_nt(tile8 + u * 32 + 8 * b + j, tq);
+                if (!HALF && u < (NU >> 1)) store_nt(tile8h + u * 32 + 8 * b + j, tq);   // the first d / 2 columns again, as tiles of their own
             }
         }
         if (o.rows8) {   // row-major copy (scan-sized operands): the batch's rows as they lie in the slice
@@ -736,19 +807,16 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
                     *reinterpret_cast<uint4*>(o.rows8 + (size_t)(row0 + 8 * b + j) * D + 16 * u) = *reinterpret_cast<const uint4*>(my8 + j * RS8 + 16 * u);
             }
         }
-        // fp6: lane = (row j, block) of the batch -- prep_chunk_kernel's conversion
+        // fp6: lane = (row j, block) of the batch
 #pragma unroll
         for (int item0 = 0; item0 < nitems; item0 += 64) {
             const int item = item0 + lane;
             if (item >= nitems) break;
             const int j = item / nconv, blk = item - j * nconv, p = 8 * b + j;
-            union {
-                uint4 u[4];
-                halfx32 h;
-                unsigned w[16];
-            } vv;
+            Block6 vv;
 #pragma unroll
             for (int k = 0; k < 4; ++k) vv.u[k] = *reinterpret_cast<const uint4*>(my16 + (size_t)(k * nitems + item) * 16);
+            // (convert_block6's lines, kept as a copy: through the function <384, false> spilled 15 VGPRs instead of 14, scratch 60 -> 64)
             ushortx2 m2 = {0, 0};
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -767,21 +835,16 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
                 const float res = __builtin_fmaf(-(float)back[i], sc6, (float)vv.h[i]);
                 e6 = __builtin_fmaf(res, res, e6);
             }
-            const int s6 = blk >> 1, l6 = (blk & 1) * 32 + p;
-            unsigned* pa = reinterpret_cast<unsigned*>(tile6 + mx6_code_a(s6, l6));
-            __builtin_nontemporal_store((unsigned)codes[0], pa);
-            __builtin_nontemporal_store((unsigned)codes[1], pa + 1);
-            __builtin_nontemporal_store((unsigned)codes[2], pa + 2);
-            __builtin_nontemporal_store((unsigned)codes[3], pa + 3);
-            unsigned* pb = reinterpret_cast<unsigned*>(tile6 + mx6_code_b(s6, l6));
-            __builtin_nontemporal_store((unsigned)codes[4], pb);
-            __builtin_nontemporal_store((unsigned)codes[5], pb + 1);
+            store_codes<true>(tile6, blk >> 1, (blk & 1) * 32 + p, codes);
             l_sc[wave * 32 + p][blk] = (unsigned char)(ex + 127);
             l_e6[blk][wave * 32 + p] = e6;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();   // (the batch's slices of the LDS are read: the next batch may overwrite them)
     }
+    // The group's tail: group_tail's steps, kept as a copy.  Through the function (and with E / rest above through norm_up) the
+    // resource usage was the same but <384, false> measured 0.8 % slower at flags 8; with these lines its code is what it was.
+    const int tb6 = mx6_tile_bytes(D >> 6);
     __syncthreads();
     {   // the d / 64 scales of MFMA lane (hh, p) of tile t: its 8 bytes of the scale plane
         const int r = threadIdx.x & (I8_GROUP - 1), hh = threadIdx.x >> 7;
@@ -794,7 +857,7 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
         unsigned char* t6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + (r >> 5)) * (size_t)tb6;
         *reinterpret_cast<uint2*>(t6 + mx6_scale_at(D >> 6, 0, hh * 32 + (r & 31))) = make_uint2(lo, hi);
     }
-    if (threadIdx.x < I8_GROUP) {   // E of the fp6 image per row: blocks in order; rounded up like the int8 one
+    if (threadIdx.x < I8_GROUP) {   // E6 per row: one of four copies.  Blocks in order; rounded up like the int8 one
         const int r = threadIdx.x;
         float acc = 0.0f, acch = 0.0f;
         for (int blk = 0; blk < nconv; ++blk) {
@@ -835,8 +898,9 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
 // Definition of THIS form's int8 image (it is not byte-identical to the other two forms'): with h = fp16(v), v the fp32-normalised
 // element, q = rint(h * 127 / amax) (within [-127, 127] by itself, see quant_chunk), amax the group's largest |v| in fp32 as before;
 // E = |h - s q|_2 + |v - h|_2: the first term MEASURED and rounded up, the second BOUNDED by the constant PREP_F16_ROUNDING (the fp16
-// rounding of a unit row: ~1.4e-4 measured beside ~1e-2, 4.9e-4 as the bound).  The fp6 image, err6 / err6h, 1 / |row|, rest / grest and
-// every group datum are the other forms', bit for bit (same arithmetic on the same values).
+// rounding of a unit row: ~1.4e-4 measured beside ~1e-2, 4.9e-4 as the bound: norm_up<true>).  The fp6 image, err6 / err6h, 1 / |row|,
+// rest / grest and every group datum are the other forms', bit for bit: the same functions (fold4, scatter8, round_half4, norm_up,
+// group_step, convert_block6, store_codes, group_tail) on the same values.
 //
 // PERSIST (coarse_variant 44): the same kernel as a grid of at most two workgroups per compute unit, each walking the groups blockIdx.x,
 // blockIdx.x + gridDim.x, ... of the concatenated (map, scan) list -- static striding, no workgroup ever waits for another.  What it
@@ -853,7 +917,7 @@ __global__ __launch_bounds__(256, 3) void prep_stream_kernel(const float* __rest
 // barriers), rint / packing / the tile stores, the scan's row-major copy, err / gstep / gerr -- and pass 1 keeps only what the fp6 half
 // image is converted from: the first chunks (the second chunks of d = 384 lie past column d / 2: 32 registers less).  inv, the fp6 half
 // image with its scales, err6h / gerr6h (err6 / gerr6: infinite, as with HALF), gstep6, rest / grest and the PrepZero ranges are the
-// bytes of the form without the flag: the same arithmetic on the same values.  The int8 regions of the operand stay unwritten.
+// bytes of the form without the flag: the same functions on the same values.  The int8 regions of the operand stay unwritten.
 template <int D, bool HALF, bool PERSIST, bool NOI8 = false>
 __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restrict__ x1, int64_t rows1, PrepOut o1, int groups1,
                                                            const float* __restrict__ x2, int64_t rows2, PrepOut o2, int groups, PrepZero z) {
@@ -926,19 +990,6 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     }
     const int wave = tid >> 6;
     const bool lo = lane < 32;
-    auto scatter8 = [&](const float* p) __attribute__((always_inline)) {   // (prep_chunk_kernel's: lane l ends with row l >> 3)
-        const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
-        float q4[4], q2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q4[j] = (b5 ? p[j + 4] : p[j]) + __shfl_xor(b5 ? p[j] : p[j + 4], 32);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) q2[j] = (b4 ? q4[j + 2] : q4[j]) + __shfl_xor(b4 ? q4[j] : q4[j + 2], 16);
-        float q1 = (b3 ? q2[1] : q2[0]) + __shfl_xor(b3 ? q2[0] : q2[1], 8);
-        q1 = q1 + __shfl_xor(q1, 4);
-        q1 = q1 + __shfl_xor(q1, 2);
-        q1 = q1 + __shfl_xor(q1, 1);
-        return q1;
-    };
     // v_permlane32_swap(a, b): result 0 = {a lanes 0-31 | b lanes 0-31}, result 1 = {a lanes 32-63 | b lanes 32-63} (rows of 32 lanes)
     auto lo_lo = [&](float a, float b) __attribute__((always_inline)) {   // lanes 0-31: a's lower half; lanes 32-63: b's LOWER half
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
@@ -949,15 +1000,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         return __uint_as_float((unsigned)sw[1]);
     };
     auto pack4 = [&](const float (&nv)[4]) __attribute__((always_inline)) {
-        // (the fp32 product is rounded to fp16 as a value of its own -- see prep_stream_kernel: hidden from the compiler, which otherwise
-        // fuses product and conversion into one v_fma_mixlo_f16, a single rounding)
-        float nh[4] = {nv[0], nv[1], nv[2], nv[3]};
-        asm volatile("" : "+v"(nh[0]), "+v"(nh[1]), "+v"(nh[2]), "+v"(nh[3]));
-        half4 h;
-        h[0] = (_Float16)nh[0];
-        h[1] = (_Float16)nh[1];
-        h[2] = (_Float16)nh[2];
-        h[3] = (_Float16)nh[3];
+        const half4 h = round_half4(nv);
         uint2 u;
         __builtin_memcpy(&u, &h, 8);
         // (as two PACKED registers from here on: left to itself the compiler keeps the four halves in four registers until their last use
@@ -972,15 +1015,6 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         nv[1] = (float)h[1];
         nv[2] = (float)h[2];
         nv[3] = (float)h[3];
-    };
-    // sum of a chunk's squares onto p in the oracle's order: ((((p + x^2) + y^2) + z^2) + w^2)
-    auto fold4 = [&](float p, const float4& t) __attribute__((always_inline)) {
-        float q;
-        q = t.x * t.x; p = p + q;
-        q = t.y * t.y; p = p + q;
-        q = t.z * t.z; p = p + q;
-        q = t.w * t.w; p = p + q;
-        return p;
     };
     const bool second = gidx >= groups1;
     const int grp = second ? gidx - groups1 : gidx;
@@ -1023,7 +1057,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
                 part[2 * jp + 1] = lo ? sb : part[2 * jp + 1];
             }
         }
-        const float my_inv = inv_norm_from_sumsq(scatter8(part));   // of row lane >> 3 of the batch
+        const float my_inv = inv_norm_from_sumsq(scatter8(part, lane));   // of row lane >> 3 of the batch
         if ((lane & 7) == 0) o.inv[row0 + 8 * b + (lane >> 3)] = my_inv;
         float rpart[8], ivs[8];
 #pragma unroll
@@ -1064,10 +1098,8 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
             }
         }
         {
-            float rn = sqrtf(scatter8(rpart)) * 1.000244140625f + 1.0e-30f;
-            if (!(rn == rn)) rn = __builtin_inff();
             const int64_t r = row0 + 8 * b + (lane >> 3);
-            if (r >= rows) rn = 0.0f;
+            const float rn = norm_up(scatter8(rpart, lane), 1.0e-30f, false, r >= rows);
             if ((lane & 7) == 0) {
                 o.rest[r] = rn;
                 if (rn > 0.0f) atomicMax(&rmax_bits, __float_as_uint(rn));
@@ -1081,10 +1113,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         __syncthreads();
         if (lane == 0 && lmax > 0.0f) atomicMax(&amax_bits, __float_as_uint(lmax));
         __syncthreads();
-        const float amax = __uint_as_float(amax_bits);
-        const bool usable = amax > 0.0f && amax < 3.0e38f;
-        qstep = usable ? amax / 127.0f : 1.0f;
-        inv_qstep = usable ? 127.0f / amax : 0.0f;
+        group_step(__uint_as_float(amax_bits), qstep, inv_qstep);
     }
     const int next = gidx + (int)gridDim.x;
     if constexpr (PERSIST) {
@@ -1094,8 +1123,7 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
     // ---- pass 2: from the registers
     unsigned char* my8 = l_i8[wave];
     unsigned char* my16 = l_h16[wave];
-    const int tb6 = mx6_tile_bytes(D >> 6);
-    unsigned char* tile6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + wave) * (size_t)tb6;
+    unsigned char* tile6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + wave) * (size_t)mx6_tile_bytes(D >> 6);
     uint4* tile8 = o.tiles8 + ((size_t)grp * 4 + wave) * (size_t)(NU * 32);
     uint4* tile8h = o.tiles8h + ((size_t)grp * 4 + wave) * (size_t)((NU >> 1) * 32);
     // one chunk of a row: quantise (codes to the batch's int8 slice), residual against the fp16 value, the halves to the fp6 staging
@@ -1109,21 +1137,11 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         }
         float nv[4];
         unpack4(hh, nv);
-        int qi[4];
         float e2 = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            // (no clamp: |h| <= fp16(amax) <= amax (1 + 2^-11) and inv_qstep <= (127 / amax)(1 + 2^-24), so |h inv_qstep| < 127.07 and the
-            // rounded value is within [-127, 127] by itself -- two of this loop's eight VALU operations per element, in a kernel the
-            // ablations put on the VALU (profiles/r06_ablations_prep_once.txt).  A NaN element converts to code 0; its row's E is infinite.)
-            const float qf = rintf(nv[e] * inv_qstep);
-            const float res = __builtin_fmaf(-qstep, qf, nv[e]);
-            e2 = __builtin_fmaf(res, res, e2);
-            qi[e] = (int)qf;
-        }
-        const unsigned packed = __builtin_amdgcn_perm((unsigned)qi[1], (unsigned)qi[0], 0x0c0c0400u) |
-                                __builtin_amdgcn_perm((unsigned)qi[3], (unsigned)qi[2], 0x04000c0cu);
-        *reinterpret_cast<unsigned*>(my8 + jr * RS8 + 4 * c) = packed;
+        // (no clamp: |h| <= fp16(amax) <= amax (1 + 2^-11) and inv_qstep <= (127 / amax)(1 + 2^-24), so |h inv_qstep| < 127.07 and the
+        // rounded value is within [-127, 127] by itself -- two of the eight VALU operations per element, in a kernel the ablations put
+        // on the VALU (profiles/r06_ablations_prep_once.txt).  A NaN element converts to code 0; its row's E is infinite.)
+        *reinterpret_cast<unsigned*>(my8 + jr * RS8 + 4 * c) = quant4<false>(nv, qstep, inv_qstep, e2);
         if (c < 8 * nconv) {   // quarter k of (row, block): 8 halves = chunks 2 k, 2 k + 1 of the block
             const int blk = c >> 3, k = (c & 7) >> 1, sub = c & 1;
             *reinterpret_cast<uint2*>(my16 + ((size_t)(k * nitems + jr * nconv + blk) * 16 + sub * 8)) = hh;
@@ -1147,10 +1165,8 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         }
         if constexpr (!NOI8) {
             // E = |h - s q|_2 (measured, rounded up) + |v - h|_2 (bounded: PREP_F16_ROUNDING)
-            float en = (sqrtf(scatter8(part)) * 1.000244140625f + PREP_F16_ROUNDING) * 1.0000002384185791f + 1.0e-30f;
-            if (!(en == en)) en = __builtin_inff();
             const int64_t r = row0 + 8 * b + (lane >> 3);
-            if (r >= rows) en = 0.0f;
+            const float en = norm_up<true>(scatter8(part, lane), 1.0e-30f, false, r >= rows);
             if ((lane & 7) == 0) {
                 o.err[r] = en;
                 if (en > 0.0f) atomicMax(&emax_bits, __float_as_uint(en));
@@ -1160,24 +1176,16 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // int8: unit column u of the batch's 8 rows = 128 consecutive bytes of the tile
+        // (this batch store -- tile, tiles8h twin, rows8 copy -- stands a second time in prep_stream_kernel: as one function it moved
+        // this kernel's VGPRs, 137 -> 141 at <256, false, false>.  Change both.)
 #ifndef VFM_POABL_NOST8
 #pragma unroll
         for (int rd = 0; rd < (NOI8 ? 0 : (NU * 8 + 63) / 64); ++rd) {
             const int e = rd * 64 + lane, u = e >> 3, j = e & 7;
             if (e < NU * 8) {
                 const uint4 tq = *reinterpret_cast<const uint4*>(my8 + j * RS8 + 16 * u);
-                unsigned* po = reinterpret_cast<unsigned*>(tile8 + u * 32 + 8 * b + j);
-                __builtin_nontemporal_store(tq.x, po);
-                __builtin_nontemporal_store(tq.y, po + 1);
-                __builtin_nontemporal_store(tq.z, po + 2);
-                __builtin_nontemporal_store(tq.w, po + 3);
-                if (!HALF && u < (NU >> 1)) {   // the first d / 2 columns again, as tiles of their own
-                    unsigned* ph = reinterpret_cast<unsigned*>(tile8h + u * 32 + 8 * b + j);
-                    __builtin_nontemporal_store(tq.x, ph);
-                    __builtin_nontemporal_store(tq.y, ph + 1);
-                    __builtin_nontemporal_store(tq.z, ph + 2);
-                    __builtin_nontemporal_store(tq.w, ph + 3);
-                }
+                store_nt(tile8 + u * 32 + 8 * b + j, tq);
+                if (!HALF && u < (NU >> 1)) store_nt(tile8h + u * 32 + 8 * b + j, tq);   // the first d / 2 columns again, as tiles of their own
             }
         }
 #endif
@@ -1189,47 +1197,20 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
                     *reinterpret_cast<uint4*>(o.rows8 + (size_t)(row0 + 8 * b + j) * D + 16 * u) = *reinterpret_cast<const uint4*>(my8 + j * RS8 + 16 * u);
             }
         }
-        // fp6: lane = (row j, block) of the batch -- prep_chunk_kernel's conversion
+        // fp6: lane = (row j, block) of the batch
 #ifndef VFM_POABL_NOMX6
 #pragma unroll
         for (int item0 = 0; item0 < nitems; item0 += 64) {
             const int item = item0 + lane;
             if (item >= nitems) break;
             const int j = item / nconv, blk = item - j * nconv, p = 8 * b + j;
-            union {
-                uint4 u[4];
-                halfx32 h;
-                unsigned w[16];
-            } vv;
+            Block6 vv;
 #pragma unroll
             for (int k = 0; k < 4; ++k) vv.u[k] = *reinterpret_cast<const uint4*>(my16 + (size_t)(k * nitems + item) * 16);
-            ushortx2 m2 = {0, 0};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const unsigned a2 = vv.w[i] & 0x7fff7fffu;
-                m2 = __builtin_elementwise_max(m2, *reinterpret_cast<const ushortx2*>(&a2));
-            }
-            const unsigned am = max((unsigned)m2[0], (unsigned)m2[1]);
-            int ex = (int)(am >> 10) - 15 - ((am & 0x3ffu) <= 0x3c0u ? 2 : 1);
-            ex = ex > 0 ? 0 : ex;
-            const float sc6 = __uint_as_float((unsigned)(ex + 127) << 23);
-            const intx6 codes = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vv.h, sc6);
-            const halfx32 back = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(codes, 1.0f);
-            float e6 = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) {
-                const float res = __builtin_fmaf(-(float)back[i], sc6, (float)vv.h[i]);
-                e6 = __builtin_fmaf(res, res, e6);
-            }
-            const int s6 = blk >> 1, l6 = (blk & 1) * 32 + p;
-            unsigned* pa = reinterpret_cast<unsigned*>(tile6 + mx6_code_a(s6, l6));
-            __builtin_nontemporal_store((unsigned)codes[0], pa);
-            __builtin_nontemporal_store((unsigned)codes[1], pa + 1);
-            __builtin_nontemporal_store((unsigned)codes[2], pa + 2);
-            __builtin_nontemporal_store((unsigned)codes[3], pa + 3);
-            unsigned* pb = reinterpret_cast<unsigned*>(tile6 + mx6_code_b(s6, l6));
-            __builtin_nontemporal_store((unsigned)codes[4], pb);
-            __builtin_nontemporal_store((unsigned)codes[5], pb + 1);
+            int ex;
+            float e6;
+            const intx6 codes = convert_block6(vv, ex, e6);
+            store_codes<true>(tile6, blk >> 1, (blk & 1) * 32 + p, codes);
             l_sc[wave * 32 + p][blk] = (unsigned char)(ex + 127);
             l_e6[blk][wave * 32 + p] = e6;
         }
@@ -1237,51 +1218,11 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();   // (the batch's slices of the LDS are read: the next batch may overwrite them)
     }
-    __syncthreads();
-    {   // the d / 64 scales of MFMA lane (hh, p) of tile t: its 8 bytes of the scale plane
-        const int r = tid & (I8_GROUP - 1), hh = tid >> 7;
-        unsigned lo4 = 0u, hi4 = 0u;
-        for (int s6 = 0; s6 < (nconv >> 1); ++s6) {
-            const unsigned bsc = l_sc[r][2 * s6 + hh];
-            if (s6 < 4) lo4 |= bsc << (8 * s6);
-            else hi4 |= bsc << (8 * (s6 - 4));
-        }
-        unsigned char* t6 = reinterpret_cast<unsigned char*>(o.tiles6) + ((size_t)grp * 4 + (r >> 5)) * (size_t)tb6;
-        *reinterpret_cast<uint2*>(t6 + mx6_scale_at(D >> 6, 0, hh * 32 + (r & 31))) = make_uint2(lo4, hi4);
-    }
-    if (tid < I8_GROUP) {   // E of the fp6 image per row: blocks in order; rounded up like the int8 one
-        const int r = tid;
-        float acc = 0.0f, acch = 0.0f;
-        for (int blk = 0; blk < nconv; ++blk) {
-            acc = acc + l_e6[blk][r];
-            if (blk + 1 == (NBLK >> 1)) acch = acc;
-        }
-        float e6n = sqrtf(acc) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
-        float e6h = sqrtf(acch) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
-        if (!(e6n == e6n) || HALF) e6n = __builtin_inff();
-        if (!(e6h == e6h)) e6h = __builtin_inff();
-        const int64_t row = (int64_t)grp * I8_GROUP + r;
-        if (row >= rows) e6n = e6h = 0.0f;
-        o.err6[row] = e6n;
-        o.err6h[row] = e6h;
-        if (e6n > 0.0f) atomicMax(&e6max_bits, __float_as_uint(e6n));
-        if (e6h > 0.0f) atomicMax(&e6hmax_bits, __float_as_uint(e6h));
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if constexpr (!NOI8) {
-            o.gstep[grp] = qstep;
-            o.gerr[grp] = __uint_as_float(emax_bits);
-        }
-        o.grest[grp] = __uint_as_float(rmax_bits);
-        o.gerr6[grp] = __uint_as_float(e6max_bits);
-        o.gerr6h[grp] = __uint_as_float(e6hmax_bits);
-        o.gstep6[grp] = MX6_FIX_STEP;
-    }
+    group_tail<D, HALF, NOI8>(o, grp, rows, tid, &l_sc[0][0], &l_e6[0][0], qstep, emax_bits, rmax_bits, e6max_bits, e6hmax_bits);
     if constexpr (!PERSIST) {
         break;
     } else {
-        // (the scales and E of this group were read from l_sc / l_e6 before the barrier above, and the next group writes them only
+        // (the scales and E of this group were read from l_sc / l_e6 before group_tail's last barrier, and the next group writes them only
         // behind three more -- one, at the top of its pass 1, without the int8 image: no barrier of its own is needed here)
         if (next >= groups) break;
         gidx = next;
@@ -1292,8 +1233,8 @@ __global__ __launch_bounds__(256, 2) void prep_once_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // The fp6 image for the wider rows (d = 512, 768: the half-width pass in fp6 reads its first d / 128 k-steps), by kernels of their
 // own behind prep_chunk_kernel (whose LDS cannot hold an fp16 copy of such a group): a thread takes one (row, 32-column block),
-// reads its 32 floats, normalises them with the 1 / |row| prep_chunk_kernel left, rounds to fp16 and converts exactly as that
-// kernel's second half does (same scale rule, v_cvt_scalef32_pk32_fp6_f16, residual measured against the fp16 values); the blocks
+// reads its 32 floats, normalises them with the 1 / |row| prep_chunk_kernel left, rounds to fp16 and converts with the function
+// that kernel's second half calls (convert_block6: scale rule, v_cvt_scalef32_pk32_fp6_f16, residual measured against the fp16 values); the blocks
 // of a row are NBLK consecutive lanes, so the row's sum is a fixed xor tree.  The block scales of k-steps 0 .. 7 go to the tile's
 // first scale plane, those of k-steps 8 .. 11 to the second one behind the codes (mx6_scale_at; spare scale bytes are never
 // read).  prep_mx6_group_kernel then takes the maximum E of every group.
@@ -1332,10 +1273,7 @@ __global__ __launch_bounds__(256) void prep_mx6_rows_kernel(Rows x1, int64_t row
         stage[rr * nf4 + bb * 8 + (jj ^ (bb & 7))] = t;
     }
     __syncthreads();
-    union {
-        halfx32 h;
-        unsigned w[16];
-    } v;
+    Block6 v;
 #pragma unroll
     for (int i = 0; i < 16; ++i) v.w[i] = 0u;
     if (active && r < rows) {
@@ -1350,24 +1288,9 @@ __global__ __launch_bounds__(256) void prep_mx6_rows_kernel(Rows x1, int64_t row
             v.h[4 * i + 3] = (_Float16)(t.w * iv);
         }
     }
-    ushortx2 m2 = {0, 0};
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const unsigned a2 = v.w[i] & 0x7fff7fffu;
-        m2 = __builtin_elementwise_max(m2, *reinterpret_cast<const ushortx2*>(&a2));
-    }
-    const unsigned am = max((unsigned)m2[0], (unsigned)m2[1]);
-    int ex = (int)(am >> 10) - 15 - ((am & 0x3ffu) <= 0x3c0u ? 2 : 1);   // as in prep_chunk_kernel's conversion
-    ex = ex > 0 ? 0 : ex;
-    const float sc6 = __uint_as_float((unsigned)(ex + 127) << 23);
-    const intx6 codes = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v.h, sc6);
-    const halfx32 back = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(codes, 1.0f);
-    float e6 = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-        const float res = __builtin_fmaf(-(float)back[i], sc6, (float)v.h[i]);
-        e6 = __builtin_fmaf(res, res, e6);
-    }
+    int ex;
+    float e6;
+    const intx6 codes = convert_block6(v, ex, e6);
     if (!active) e6 = 0.0f;
     float e6f = e6, e6hs = blk < (nblk >> 1) ? e6 : 0.0f;   // all converted columns / the first d / 2
 #pragma unroll
@@ -1376,6 +1299,7 @@ __global__ __launch_bounds__(256) void prep_mx6_rows_kernel(Rows x1, int64_t row
         e6hs = e6hs + __shfl_xor(e6hs, off);
     }
     if (blk == 0 && !beyond) {
+        // E6 per row: one of four copies (through norm_up this kernel's VGPRs moved 47 -> 50).  prep_mx6_group_kernel takes the maxima.
         float e6n = sqrtf(e6f) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
         float e6h = sqrtf(e6hs) * 1.000244140625f + (MX6_F16_ROUNDING + MX6_SLACK);
         if (!(e6n == e6n) || o.mx6_half) e6n = __builtin_inff();
@@ -1387,8 +1311,7 @@ __global__ __launch_bounds__(256) void prep_mx6_rows_kernel(Rows x1, int64_t row
     if (active) {
         const int p = (int)(r & 31), s6 = blk >> 1, l6 = (blk & 1) * 32 + p, ks = d >> 6;
         unsigned char* tile = reinterpret_cast<unsigned char*>(o.tiles6) + (size_t)(r >> 5) * (size_t)mx6_tile_bytes(ks);
-        *reinterpret_cast<uint4*>(tile + mx6_code_a(s6, l6)) = make_uint4((unsigned)codes[0], (unsigned)codes[1], (unsigned)codes[2], (unsigned)codes[3]);
-        *reinterpret_cast<uint2*>(tile + mx6_code_b(s6, l6)) = make_uint2((unsigned)codes[4], (unsigned)codes[5]);
+        store_codes<false>(tile, s6, l6, codes);
         tile[mx6_scale_at(ks, s6, l6)] = (unsigned char)(ex + 127);
     }
 }
