@@ -46,9 +46,10 @@ def rows(n, m, d, seed=0, common=False):
 FAST_SHAPES = [(1, 1, 128, 1), (1, 5, 384, 8), (33, 127, 128, 2), (33, 129, 384, 5), (257, 300, 128, 8), (257, 4097, 384, 8),
                (33, 4097, 128, 5), (257, 1, 384, 2), (1, 300, 128, 5), (257, 5, 128, 8), (1, 127, 384, 1), (257, 129, 128, 1),
                (1, 4097, 128, 2), (33, 300, 384, 2)]
-# the same N, M and k at d of {33, 128, 512}
+# the same N, M and k at d of {33, 128, 512}; then the two sides of the row norm's paths: d = 1024 is the last width whose sum of
+# squares takes the float4 chunks (all four of a lane in use), d = 1028 the first multiple of 4 that takes the element loop
 EXACT_SHAPES = [(1, 1, 33, 1), (33, 5, 128, 8), (257, 300, 512, 5), (33, 129, 33, 2), (1, 127, 512, 8), (257, 4097, 33, 8),
-                (33, 4097, 128, 1), (257, 1, 128, 2), (1, 300, 33, 5), (33, 127, 512, 2)]
+                (33, 4097, 128, 1), (257, 1, 128, 2), (1, 300, 33, 5), (33, 127, 512, 2), (33, 129, 1024, 2), (33, 129, 1028, 2)]
 
 
 @pytest.mark.parametrize("n,m,d,k", FAST_SHAPES)

@@ -2,7 +2,8 @@
 // (match_select_kernel), int8 rescan of candidate chunks (match_rescan_kernel), fp32 refinement of crowded lists
 // (match_refine_kernel, match_filter_refine_kernel), the exact fp64 decision (match_rescore_kernel), the all-pairs fp64
 // kernel (EXACT mode and overflow fallback) and the cosine threshold + compaction (VoxelHashMap.cpp:501-511, 587-600).
-#include "match_internal.h"
+// The fp64 chains, the tie rule and the arg-max of the decision kernels: match_exact.h.
+#include "match_exact.h"
 
 namespace vfmm {
 namespace {
@@ -1821,54 +1822,6 @@ __global__ __launch_bounds__(256) void match_filter_refine_kernel(Rows q, const 
     R.finish(qi, mycand, cand_cnt, fb_count, fb_list, stats);
 }
 
-// exact score of normalised rows, sequential k, fp64 (products of two fp32 are exact in fp64)
-__device__ __forceinline__ double dot_norm_f64(const float* __restrict__ qrow_n, Rows b, int64_t brow, float invb, int d) {
-    double acc = 0.0;
-    for (int k = 0; k < d; k += 4) {
-        const float4 bv = b.ld4(brow + k);
-        const float b0 = bv.x * invb, b1 = bv.y * invb, b2 = bv.z * invb, b3 = bv.w * invb;
-        acc = acc + (double)qrow_n[k + 0] * (double)b0;
-        acc = acc + (double)qrow_n[k + 1] * (double)b1;
-        acc = acc + (double)qrow_n[k + 2] * (double)b2;
-        acc = acc + (double)qrow_n[k + 3] * (double)b3;
-    }
-    return acc;
-}
-
-// exact score of ONE pair by one lane: the products of match_rescore_kernel's batches (fp32 normalisation, exact fp64 product), added
-// in ascending k.  Two buffers of 32 columns: the loads of the next 32 are in flight while a buffer's products are added.
-__device__ __forceinline__ double dot_pair_f64(Rows q, int64_t qe, float iq, Rows b, int64_t be, float ib, int d) {
-    double acc = 0.0;
-    auto add4 = [&](const float4& qv, const float4& bv) __attribute__((always_inline)) {
-        acc = acc + (double)(qv.x * iq) * (double)(bv.x * ib);
-        acc = acc + (double)(qv.y * iq) * (double)(bv.y * ib);
-        acc = acc + (double)(qv.z * iq) * (double)(bv.z * ib);
-        acc = acc + (double)(qv.w * iq) * (double)(bv.w * ib);
-    };
-    float4 q0[8], b0[8], q1[8], b1[8];
-    auto fetch = [&](float4 (&qq)[8], float4 (&bb)[8], int k) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            qq[i] = q.ld4(qe + k + 4 * i);
-            bb[i] = b.ld4(be + k + 4 * i);
-        }
-    };
-    auto use = [&](const float4 (&qq)[8], const float4 (&bb)[8]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) add4(qq[i], bb[i]);
-    };
-    const int dmain = d & ~63;
-    if (dmain) fetch(q0, b0, 0);
-    for (int k = 0; k < dmain; k += 64) {
-        fetch(q1, b1, k + 32);
-        use(q0, b0);
-        if (k + 64 < dmain) fetch(q0, b0, k + 64);
-        use(q1, b1);
-    }
-    for (int k = dmain; k < d; k += 4) add4(q.ld4(qe + k), b.ld4(be + k));   // d % 4 == 0
-    return acc;
-}
-
 // Exact decision among the candidates: one workgroup (4 waves) owns 64 queries; thread t < 64 = query t.
 //   single-row candidates (the common case, ~1.3 per query): the block's (query, candidate) pairs are
 //   flattened and taken 64 at a time; per batch and per 96-wide k chunk the four waves compute the fp64
@@ -2020,10 +1973,10 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
                     if (s_j[sl] >= 0 && 4 * l4 < kn) {
                         const float iqq = s_iq[sl], ibb = s_ib[sl];
                         double* dst = P + sl * RS_STRIDE + 4 * l4;
-                        dst[0] = (double)(qv[it].x * iqq) * (double)(bv[it].x * ibb);
-                        dst[1] = (double)(qv[it].y * iqq) * (double)(bv[it].y * ibb);
-                        dst[2] = (double)(qv[it].z * iqq) * (double)(bv[it].z * ibb);
-                        dst[3] = (double)(qv[it].w * iqq) * (double)(bv[it].w * ibb);
+                        dst[0] = prod_norm_f64(qv[it].x, iqq, bv[it].x, ibb);
+                        dst[1] = prod_norm_f64(qv[it].y, iqq, bv[it].y, ibb);
+                        dst[2] = prod_norm_f64(qv[it].z, iqq, bv[it].z, ibb);
+                        dst[3] = prod_norm_f64(qv[it].w, iqq, bv[it].w, ibb);
                     }
                 }
                 __syncthreads();
@@ -2051,10 +2004,7 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
             for (int k = lo; k < hi; ++k) {
                 const long long j = (long long)p_j[k - E0];
                 const double sc = pscore[k - E0];
-                if (bj < 0 || sc > best || (sc == best && j < bj)) {
-                    best = sc;
-                    bj = j;
-                }
+                take_if_before(sc, j, best, bj);
             }
         }
         __syncthreads();
@@ -2085,18 +2035,12 @@ __global__ __launch_bounds__(256) void match_rescore_kernel(Rows q, const float*
                     const long long j = base + li;
                     if (j < m) {
                         const double sc = dot_norm_f64(qn, b, j * (int64_t)d, invb[j], d);
-                        if (rj < 0 || sc > rbest || (sc == rbest && j < rj)) {
-                            rbest = sc;
-                            rj = j;
-                        }
+                        take_if_before(sc, j, rbest, rj);
                     }
                 }
             }
             wave_argmax(rbest, rj);
-            if (lane == ql && rj >= 0 && (bj < 0 || rbest > best || (rbest == best && rj < bj))) {
-                best = rbest;
-                bj = rj;
-            }
+            if (lane == ql) take_if_before(rbest, rj, best, bj);
         }
     }
     if (!have) return;
@@ -2136,11 +2080,13 @@ __global__ __launch_bounds__(256) void match_exact_kernel(Rows q, const float* _
         long long bj = -1;
         for (long long j = threadIdx.x; j < m; j += 256) {
             const double s = dot_norm_f64(qn, b, j * (int64_t)d, invb ? invb[j] : 1.0f, d);
-            if (bj < 0 || s > best) {
+            if (bj < 0 || s > best) {   // (a thread's j ascends: an equal score never replaces an earlier row -- decided_before's answer)
                 best = s;
                 bj = j;
             }
         }
+        // block_argmax's steps, a copy: with the call the compiler scheduled the loop above as one dependent chain (the fourth product
+        // behind the third sum) and vfm_match_ip_top1(EXACT) at 2 000 x 200 000 x 384 took 360.9 ms instead of 357.5
         wave_argmax(best, bj);
         if (lane_id() == 0) {
             rs[threadIdx.x >> 6] = best;
@@ -2148,11 +2094,7 @@ __global__ __launch_bounds__(256) void match_exact_kernel(Rows q, const float* _
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w)
-                if (rj[w] >= 0 && (rj[0] < 0 || rs[w] > rs[0] || (rs[w] == rs[0] && rj[w] < rj[0]))) {
-                    rs[0] = rs[w];
-                    rj[0] = rj[w];
-                }
+            for (int w = 1; w < 4; ++w) take_if_before(rs[w], rj[w], rs[0], rj[0]);
             idx_out[qi] = (m > 0) ? rj[0] : -1;
             sim_out[qi] = (m > 0) ? (float)rs[0] : 0.0f;
         }
@@ -2236,16 +2178,28 @@ __global__ __launch_bounds__(1024) void threshold_compact_kernel(const float* __
     if (threadIdx.x == 0) *count = base;
 }
 
-// 1/|row| only (EXACT mode)
+// 1/|row| only (the EXACT modes), one wave per row.  The sum of squares in the oracle's order (orc_sumsq_f32: element c goes to
+// partial (c / 4) % 64 in ascending c, then an xor butterfly): row_sumsq_wave where its float4 chunks apply, element loads otherwise
 __global__ __launch_bounds__(256) void inv_norm_kernel(const float* __restrict__ x, int64_t rows, int d,
                                                        float* __restrict__ inv_out) {
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    float4 v[4];
-    float nr = row_sumsq_wave(x + r * (int64_t)d, d, v);
-    float inv = inv_norm_from_sumsq(nr);
+    const float* row = x + r * (int64_t)d;
+    float nr = 0.0f;
+    if ((d & 3) == 0 && d <= 1024) {
+        float4 v[4];
+        nr = row_sumsq_wave(row, d, v);
+    } else {
+        for (int c0 = 4 * lane_id(); c0 < d; c0 += 256)
+            for (int c = c0; c < c0 + 4 && c < d; ++c) {
+                const float t = row[c] * row[c];
+                nr = nr + t;
+            }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) nr = nr + __shfl_xor(nr, off);
+    }
     // faiss leaves zero rows untouched: scaling by 1 reproduces that
-    if (lane_id() == 0) inv_out[r] = (nr > 0.0f) ? inv : 1.0f;
+    if (lane_id() == 0) inv_out[r] = (nr > 0.0f) ? inv_norm_from_sumsq(nr) : 1.0f;
 }
 
 template <int QB>
@@ -2461,15 +2415,20 @@ int launch_select_dense(const SearchWs& w, const CoarseArgs& a, const float* qin
     return VFM_OK;
 }
 
+int launch_inv_norm(const float* x, int64_t rows, int d, float* inv_out, hipStream_t st) {
+    hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, d, inv_out);
+    VFM_CHECK_LAUNCH("inv_norm_kernel");
+    return VFM_OK;
+}
+
 // EXACT mode of vfm_match_ip_top1: all-pairs fp64; ws holds 1/|row| of both operands
 int exact_ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, int64_t* idx_out, float* sim_out, void* ws,
                   hipStream_t st) {
     VfmCarver c(ws);
     float* invq = c.take<float>((size_t)n);
     float* invb = c.take<float>((size_t)m);
-    hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q, n, d, invq);
-    hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, b, m, d, invb);
-    VFM_CHECK_LAUNCH("inv_norm_kernel");
+    VFM_TRY(launch_inv_norm(q, n, d, invq, st));
+    VFM_TRY(launch_inv_norm(b, m, d, invb, st));
     const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
     hipLaunchKernelGGL(match_exact_kernel, dim3(grid), dim3(256), (((size_t)d * 4 + 15) & ~(size_t)15) + 64, st, q,
                        invq, b, invb, n, m, d, (const int*)nullptr, (const int*)nullptr, idx_out, sim_out);

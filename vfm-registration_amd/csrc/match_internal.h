@@ -340,18 +340,7 @@ __device__ __forceinline__ float l2_scale(const unsigned* max_bits) {
     return ldexpf(1.0f, -e);
 }
 
-// arg-max over a wavefront, ties -> lowest index (the oracle's rule)
-__device__ __forceinline__ void wave_argmax(double& s, long long& j) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double so = __shfl_xor(s, off);
-        const long long jo = __shfl_xor(j, off);
-        if (jo >= 0 && (j < 0 || so > s || (so == s && jo < j))) {
-            s = so;
-            j = jo;
-        }
-    }
-}
+// (wave_argmax and the rest of the fp64 decision: match_exact.h)
 
 // =============================================================================================
 // host side
@@ -897,6 +886,8 @@ int launch_i8_rescans(const SearchWs& w, const CoarseArgs& a, const Prepared& Q,
 int probe_half_select(const SearchPlan& plan, const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, float gate, hipStream_t st);
 int exact_ip_top1(const float* q, int64_t n, const float* b, int64_t m, int d, int64_t* idx_out, float* sim_out, void* ws,
                   hipStream_t st);
+// inv_out[r] = 1 / |row r of x| in fp32, the sum of squares in the oracle's order (orc_sumsq_f32), any d >= 1; zero rows get 1
+int launch_inv_norm(const float* x, int64_t rows, int d, float* inv_out, hipStream_t st);
 // match_l2_narrow.hip (VFM_MATCH_NARROW, d <= VFM_L2_NARROW_MAX_D): one direction of the f32-MFMA Euclidean search -- query i = row
 // (qperm ? qperm[i] : i) of q, among the m rows of b -- in a workspace of l2n_dir_bytes(nq, m, d); max_bits as l2_maxnorm_kernel left it
 // for BOTH sets; *evals (device) is incremented by the number of exact evaluations

@@ -4,7 +4,7 @@
 // their own on the f32 MFMA (VFM_MATCH_NARROW, match_l2_narrow.hip); the entry points below route to it.
 #include <hipcub/hipcub.hpp>
 
-#include "match_internal.h"
+#include "match_exact.h"
 
 namespace vfmm {
 namespace {
@@ -31,33 +31,18 @@ __global__ __launch_bounds__(256) void nn_l2_kernel(const float* __restrict__ a,
         double best = 0.0;
         long long bj = -1;
         for (long long j = threadIdx.x; j < m; j += 256) {
-            const float* p = b + j * (int64_t)d;
-            double acc = 0.0;
-            for (int k = 0; k < d; ++k) {
-                const double t = (double)qa[k] - (double)p[k];
-                acc = acc + t * t;
-            }
-            if (bj < 0 || acc < best) {
+            const double acc = l2_dist_f64(qa, b + j * (int64_t)d, d);
+            if (bj < 0 || acc < best) {   // (a thread's j ascends: an equal distance never replaces an earlier row)
                 best = acc;
                 bj = j;
             }
         }
-        // arg-min: negate so that wave_argmax applies (x -> -x is exact)
+        // arg-min: negate so that the arg-max applies (x -> -x is exact)
         double neg = -best;
-        wave_argmax(neg, bj);
-        if (lane_id() == 0) {
-            rs[threadIdx.x >> 6] = neg;
-            rj[threadIdx.x >> 6] = bj;
-        }
-        __syncthreads();
+        block_argmax(neg, bj, rs, rj);   // (rs / rj are rewritten behind the two barriers at the top of the next query)
         if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w)
-                if (rj[w] >= 0 && (rj[0] < 0 || rs[w] > rs[0] || (rs[w] == rs[0] && rj[w] < rj[0]))) {
-                    rs[0] = rs[w];
-                    rj[0] = rj[w];
-                }
-            nn[qi] = rj[0];
-            if (d2) d2[qi] = -rs[0];
+            nn[qi] = bj;
+            if (d2) d2[qi] = -neg;
         }
     }
 }
@@ -155,16 +140,6 @@ __global__ __launch_bounds__(256) void l2_prep_kernel(const float* __restrict__ 
     }
 }
 
-// oracle order: acc += (double(a_k) - double(b_k))^2, k ascending
-__device__ __forceinline__ double l2_dist_f64(const float* __restrict__ qa, const float* __restrict__ brow, int d) {
-    double acc = 0.0;
-    for (int k = 0; k < d; ++k) {
-        const double t = (double)qa[k] - (double)brow[k];
-        acc = acc + t * t;
-    }
-    return acc;
-}
-
 // exact decision among the candidates of match_select_kernel: one wave per query
 __global__ __launch_bounds__(256) void l2_rescore_kernel(const float* __restrict__ q, const float* __restrict__ b, int64_t n,
                                                          int64_t m, int d, const int* __restrict__ cand_cnt,
@@ -194,10 +169,7 @@ __global__ __launch_bounds__(256) void l2_rescore_kernel(const float* __restrict
                 if (base + li < m) {
                     const long long j = perm ? (long long)perm[base + li] : base + li;
                     const double s = -l2_dist_f64(qa, b + j * (int64_t)d, d);
-                    if (bj < 0 || s > best || (s == best && j < bj)) {
-                        best = s;
-                        bj = j;
-                    }
+                    take_if_before(s, j, best, bj);
                 }
             }
         } else {
@@ -207,10 +179,7 @@ __global__ __launch_bounds__(256) void l2_rescore_kernel(const float* __restrict
                 for (int k = lane; k < d; k += 64) bb[k] = b[j * (int64_t)d + k];
                 __builtin_amdgcn_wave_barrier();
                 const double s = -l2_dist_f64(qa, bb, d);  // same chain in every lane (LDS broadcast reads)
-                if (bj < 0 || s > best || (s == best && j < bj)) {
-                    best = s;
-                    bj = j;
-                }
+                take_if_before(s, j, best, bj);
             }
         }
     }
@@ -220,8 +189,6 @@ __global__ __launch_bounds__(256) void l2_rescore_kernel(const float* __restrict
         if (d2_out) d2_out[qi] = -best;
     }
 }
-
-
 
 // =============================================================================================
 // Row A6 on the INT8 coarse pass (round 3; d = 256 ... 768 in steps of 128).  VERDICT r2: north_star's named matcher -- all-pairs
@@ -525,11 +492,10 @@ __global__ __launch_bounds__(256) void l2i8_rescore_kernel(const float* __restri
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 if (k0 + u >= nk4) break;
-                double tt;
-                tt = (double)av[u].x - (double)bv[u].x; acc = acc + tt * tt;
-                tt = (double)av[u].y - (double)bv[u].y; acc = acc + tt * tt;
-                tt = (double)av[u].z - (double)bv[u].z; acc = acc + tt * tt;
-                tt = (double)av[u].w - (double)bv[u].w; acc = acc + tt * tt;
+                acc = l2_step_f64(acc, av[u].x, bv[u].x);
+                acc = l2_step_f64(acc, av[u].y, bv[u].y);
+                acc = l2_step_f64(acc, av[u].z, bv[u].z);
+                acc = l2_step_f64(acc, av[u].w, bv[u].w);
             }
         }
         return acc;

@@ -20,7 +20,7 @@
 // CU).  A wave merges its two lane halves (they hold different map rows of the same queries), every (query, slice) leaves one
 // (d^2, index) partial, l2n_merge_kernel takes the lexicographic minimum (smaller d^2, then lower index) over the slices.  No
 // atomics on a result; one atomic per wave on the evaluation counter (include/vfmreg_debug.h).
-#include "match_internal.h"
+#include "match_exact.h"
 
 #include <utility>
 
@@ -82,7 +82,7 @@ struct L2nArgs {
     unsigned long long* evals;
 };
 
-// the oracle's loop: acc = acc + t * t, t = (double)a[k] - (double)b[k], k ascending (the build passes -ffp-contract=off).  Both rows
+// the oracle's loop, one l2_step_f64 (match_exact.h) per column, k ascending.  Both rows
 // are loaded first -- in one go up to 34 columns, 16 at a time beyond -- so that a decision waits for memory a few times, not per
 // column; the padding column (d odd) is read as 0 - 0 and adds an exact +0.
 template <int KP>
@@ -101,10 +101,7 @@ __device__ __forceinline__ double l2n_exact(const float* __restrict__ qa, const 
         }
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            if (k0 + u < KP) {
-                const double t = (double)av[u] - (double)bv[u];
-                acc = acc + t * t;
-            }
+            if (k0 + u < KP) acc = l2_step_f64(acc, av[u], bv[u]);
         }
     }
     return acc;
@@ -137,7 +134,7 @@ __device__ __forceinline__ void l2n_flush(const L2nArgs& p, const float* __restr
         --best.np;
         const double v = l2n_exact<KP>(qrow, p.b + j * (int64_t)p.d, p.d);
         ++evals;
-        if (best.j < 0 || v < best.d2 || (v == best.d2 && j < best.j)) {
+        if (nearer_before(v, j, best.d2, best.j)) {
             best.d2 = v;
             best.j = j;
         }
@@ -273,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void l2n_sweep_kernel(L2nArgs p) {
         l2n_flush<KP>(p, qrow[u], best[u], evals);
         const double od = __shfl_xor(best[u].d2, 32);
         const long long oj = __shfl_xor(best[u].j, 32);
-        if (oj >= 0 && (best[u].j < 0 || od < best[u].d2 || (od == best[u].d2 && oj < best[u].j))) {
+        if (nearer_before(od, oj, best[u].d2, best[u].j)) {
             best[u].d2 = od;
             best[u].j = oj;
         }
@@ -297,7 +294,7 @@ __global__ void l2n_merge_kernel(const double* __restrict__ pd2, const int* __re
     for (int s = 0; s < nslices; ++s) {
         const double v = pd2[(size_t)s * (size_t)n + (size_t)i];
         const long long j = pj[(size_t)s * (size_t)n + (size_t)i];
-        if (j >= 0 && (bj < 0 || v < best || (v == best && j < bj))) {
+        if (nearer_before(v, j, best, bj)) {
             best = v;
             bj = j;
         }

@@ -7,7 +7,8 @@
 // faiss inner-product heap.  Column 0 is what vfm_match_ip_top1 returns.
 //
 // EXACT (any d >= 1): all pairs in fp64 on the vector ALUs (match_topk_exact_kernel), one workgroup per query, a sorted list of
-// VFM_MATCH_TOPK_MAX entries per thread, then k rounds of a workgroup-wide arg-max over the lists' heads.
+// VFM_MATCH_TOPK_MAX entries per thread, then k rounds of a workgroup-wide arg-max over the lists' heads.  The score chain, the
+// order and the arg-max are the top-1 search's own (match_exact.h), and so is 1 / |row| (launch_inv_norm, match_finish.hip).
 //
 // FAST (d = 128 / 256 / 384, at most 2^24 padded map rows; anything else given FAST runs EXACT, as the top-1 entry point falls back;
 // the d = 512 and d = 640 / 768 kernel shapes of the top-1 search are out of scope here):
@@ -37,7 +38,7 @@
 // barrier -- always 0, so that the slow path's global atomics and loads, which the compiler counts on the same counter, cannot shift
 // what a non-zero count would mean.  The record slot comes from an LDS atomic; the publishing atomicMax does not return; the one
 // returning access (the re-read of tau) makes the wave wait for the tiles in flight, which is why it sits in the slow path only.
-#include "match_internal.h"
+#include "match_exact.h"
 
 #include <cfloat>
 
@@ -242,30 +243,7 @@ __global__ __launch_bounds__(512) void match_topk_coarse_kernel(TopkArgs a) {
 // ---------------------------------------------------------------------------------------------
 // the exact decision
 // ---------------------------------------------------------------------------------------------
-// The score of a pair: the chain of orc_dot_f64 on the fp32-normalised rows (products of two fp32 are exact in fp64; the library is
-// built with -ffp-contract=off, and a fused multiply-add of an exact product rounds the same way).  It is dot_norm_f64 of
-// match_finish.hip, which lives in that file's anonymous namespace, restated for rows of any width: aligned float4 loads where
-// d % 4 == 0, element loads otherwise -- the same values in the same order.
-__device__ __forceinline__ double topk_dot_f64(const float* __restrict__ qrow_n, const float* __restrict__ brow, float invb, int d) {
-    double acc = 0.0;
-    if ((d & 3) == 0) {
-        for (int k = 0; k < d; k += 4) {
-            const float4 bv = *reinterpret_cast<const float4*>(brow + k);
-            const float b0 = bv.x * invb, b1 = bv.y * invb, b2 = bv.z * invb, b3 = bv.w * invb;
-            acc = acc + (double)qrow_n[k + 0] * (double)b0;
-            acc = acc + (double)qrow_n[k + 1] * (double)b1;
-            acc = acc + (double)qrow_n[k + 2] * (double)b2;
-            acc = acc + (double)qrow_n[k + 3] * (double)b3;
-        }
-    } else {
-        for (int k = 0; k < d; ++k) {
-            const float bk = brow[k] * invb;
-            acc = acc + (double)qrow_n[k] * (double)bk;
-        }
-    }
-    return acc;
-}
-
+// The score of a pair is dot_norm_any_f64 (match_exact.h): the chain of orc_dot_f64 on the fp32-normalised rows, for rows of any width.
 // a thread's k best pairs, best first: (score descending, map row ascending); j < 0: empty slot
 struct TopList {
     double s[TOPK_MAX];
@@ -280,7 +258,7 @@ struct TopList {
     __device__ __forceinline__ void insert(double sc, long long row) {
 #pragma unroll
         for (int i = 0; i < TOPK_MAX; ++i) {
-            if (row >= 0 && (j[i] < 0 || sc > s[i] || (sc == s[i] && row < j[i]))) {
+            if (decided_before(sc, row, s[i], j[i])) {
                 const double ts = s[i];
                 const long long tj = j[i];
                 s[i] = sc;
@@ -304,25 +282,11 @@ struct TopList {
 // at most one list.  red_s / red_j: [2][4] in LDS.
 __device__ __forceinline__ void block_emit_topk(TopList& T, int k, double* red_s, long long* red_j, int64_t* __restrict__ idx_row,
                                                 float* __restrict__ sim_row) {
-    const int wave = threadIdx.x >> 6;
     for (int r = 0; r < k; ++r) {
         double s = T.s[0];
         long long j = T.j[0];
-        wave_argmax(s, j);
-        double* rs = red_s + (r & 1) * 4;
-        long long* rj = red_j + (r & 1) * 4;
-        if (lane_id() == 0) {
-            rs[wave] = s;
-            rj[wave] = j;
-        }
-        __syncthreads();   // (the buffers alternate: round r + 1 writes the other pair while a late thread still reads this one)
-        s = rs[0];
-        j = rj[0];
-        for (int w = 1; w < 4; ++w)
-            if (rj[w] >= 0 && (j < 0 || rs[w] > s || (rs[w] == s && rj[w] < j))) {
-                s = rs[w];
-                j = rj[w];
-            }
+        // (the buffers alternate: round r + 1 writes the other pair while a late thread still reads this one)
+        block_argmax(s, j, red_s + (r & 1) * 4, red_j + (r & 1) * 4);
         if (threadIdx.x == 0) {
             idx_row[r] = j >= 0 ? j : -1;
             sim_row[r] = j >= 0 ? (float)s : -FLT_MAX;   // the padding of a faiss inner-product heap
@@ -350,7 +314,7 @@ __global__ __launch_bounds__(256) void match_topk_exact_kernel(const float* __re
         __syncthreads();
         TopList T;
         T.clear();
-        for (long long j = threadIdx.x; j < m; j += 256) T.insert(topk_dot_f64(qn, b + j * (int64_t)d, invb[j], d), j);
+        for (long long j = threadIdx.x; j < m; j += 256) T.insert(dot_norm_any_f64(qn, Rows(b), j * (int64_t)d, invb[j], d), j);
         block_emit_topk(T, k, red_s, red_j, idx_out + qi * k, sim_out + qi * k);
     }
 }
@@ -387,7 +351,7 @@ __global__ __launch_bounds__(256) void match_topk_finish_kernel(const float* __r
     T.clear();
     for (unsigned i = threadIdx.x; i < cnt; i += 256) {
         const long long j = (long long)rec[(size_t)qi * TOPK_RECORD_CAP + i].x;
-        T.insert(topk_dot_f64(qn, b + j * (int64_t)d, invb[j], d), j);
+        T.insert(dot_norm_any_f64(qn, Rows(b), j * (int64_t)d, invb[j], d), j);
     }
     block_emit_topk(T, k, red_s, red_j, idx_out + qi * k, sim_out + qi * k);
 }
@@ -428,24 +392,6 @@ __global__ __launch_bounds__(256) void match_topk_bound_kernel(int64_t n, int k,
         }
     }
     if (lane == 0 && kth) atomicMax(tau + qi, kth);
-}
-
-// 1 / |row| for rows of any width, in the oracle's order (orc_sumsq_f32: element c goes to partial (c / 4) % 64 in ascending c, then
-// an xor butterfly); zero rows get 1 -- faiss leaves them untouched --, one wave per row
-__global__ __launch_bounds__(256) void topk_inv_norm_kernel(const float* __restrict__ x, int64_t rows, int d, float* __restrict__ inv_out) {
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const float* row = x + r * (int64_t)d;
-    const int lane = lane_id();
-    float p = 0.0f;
-    for (int c0 = 4 * lane; c0 < d; c0 += 256)
-        for (int c = c0; c < c0 + 4 && c < d; ++c) {
-            const float t = row[c] * row[c];
-            p = p + t;
-        }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off);
-    if (lane == 0) inv_out[r] = (p > 0.0f) ? inv_norm_from_sumsq(p) : 1.0f;
 }
 
 __global__ void topk_pad_kernel(int64_t total, int64_t* __restrict__ idx_out, float* __restrict__ sim_out) {
@@ -529,9 +475,8 @@ VFM_EXPORT int vfm_match_ip_topk(const float* q, int64_t n, const float* b, int6
         VfmCarver c(ws);
         float* invq = c.take<float>((size_t)n);
         float* invb = c.take<float>((size_t)m);
-        hipLaunchKernelGGL(topk_inv_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, q, n, d, invq);
-        hipLaunchKernelGGL(topk_inv_norm_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, b, m, d, invb);
-        VFM_CHECK_LAUNCH("topk_inv_norm_kernel");
+        VFM_TRY(launch_inv_norm(q, n, d, invq, st));
+        VFM_TRY(launch_inv_norm(b, m, d, invb, st));
         hipLaunchKernelGGL(match_topk_exact_kernel, dim3(egrid), dim3(256), ((size_t)d * 4 + 15) & ~(size_t)15, st, q, (const float*)invq, b,
                            (const float*)invb, n, m, d, k, (const int*)nullptr, (const int*)nullptr, idx_out, sim_out);
         VFM_CHECK_LAUNCH("match_topk_exact_kernel");
