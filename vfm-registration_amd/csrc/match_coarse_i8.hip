@@ -244,7 +244,8 @@ __global__ __launch_bounds__(512, 2) void match_coarse_i8q2_kernel(CoarseArgs a)
                 const unsigned w1 = max(s1[j], (unsigned)__shfl_xor(s1[j], 32));   // the chunk's best score (all lanes)
                 s1[j] = 0u;
                 if (counted && lane < 32 && fuse_live[j]) {
-                    // the bound of match_select_half_kernel: best exact score of the chunk <= s_q s_c S_half + A + B_c + r_q R_c
+                    // the bound of match_select_half_kernel (match_select.h: chunk_upper_half; this kernel's own registers, slack
+                    // folded into A): best exact score of the chunk <= s_q s_c S_half + A + B_c + r_q R_c
                     const float up = (i8_sq[j] * sb) * (float)((int)w1 - I8_OFFSET) + (i8_A[j] + i8_mult[j] * be) + (fuse_rq[j] * rb + 1.0e-6f);
                     if (!(up < a.gate)) {   // rare: a handful per query where the pass is used at all
                         const int64_t q = (int64_t)(qt0 + j) * 32 + lane;

@@ -244,8 +244,8 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
         const int chunk = c0 + ci;
         const bool padded = chunk >= a.first_pad_chunk;     // zero-padded rows score exactly 0
         if constexpr (FUSE) {
-            // The bound of match_select_half_kernel -- best exact score of the chunk <= x + A + B_c + r_q R_c -- against the gate, as a
-            // threshold on x (one more 1e-6 for the rearrangement; x is the fp32 score itself: the records round it up to their
+            // The bound of match_select_half_kernel (match_select.h: chunk_upper_half; evaluated here in this kernel's own pinned
+            // registers) -- best exact score of the chunk <= x + A + B_c + r_q R_c -- against the gate, as a threshold on x (one more 1e-6 for the rearrangement; x is the fp32 score itself: the records round it up to their
             // 2^-20 grid, which MX6_SLACK pays for either way).  Each half-wave tests the maximum of ITS 64 rows and the two halves
             // meet as scalar masks: no cross-lane exchange, no per-lane branch (the ablations put the first form of this emit -- swap,
             // compare, exec-masked branch per query set -- at 10 % of the kernel).  m = queries of the set with a surviving chunk.

@@ -1,9 +1,12 @@
 // match_finish.hip -- from coarse records to the oracle's answer: candidate selection
-// (match_select_kernel), int8 rescan of candidate chunks (match_rescan_kernel), fp32 refinement of crowded lists
-// (match_refine_kernel, match_filter_refine_kernel), the exact fp64 decision (match_rescore_kernel), the all-pairs fp64
-// kernel (EXACT mode and overflow fallback) and the cosine threshold + compaction (VoxelHashMap.cpp:501-511, 587-600).
+// (match_select_kernel and its forms laid out for the sweep: _top2, _half, _best; match_bin_survivors_kernel), int8 rescan of
+// candidate chunks (match_rescan_kernel), fp32 refinement of crowded lists (match_refine_kernel, match_filter_refine_kernel), the
+// exact fp64 decision (match_rescore_kernel), the all-pairs fp64 kernel (EXACT mode and overflow fallback) and the cosine threshold +
+// compaction (VoxelHashMap.cpp:501-511, 587-600).
+// The steps the selection kernels share -- bounds, staging, sweep, placement, epilogue: match_select.h.
 // The fp64 chains, the tie rule and the arg-max of the decision kernels: match_exact.h.
 #include "match_exact.h"
+#include "match_select.h"
 
 namespace vfmm {
 namespace {
@@ -32,8 +35,8 @@ __global__ __launch_bounds__(64 * SELECT_GROUPS) void match_select_kernel(const 
         lub[qq] = 0u;
     }
     float2* lchunk = reinterpret_cast<float2*>(select_smem);
-    if (ib.qerr && chunk_lds)  // every thread walks ~nchunks / 16 chunks: their (step, max E) once per workgroup into LDS
-        for (int c = threadIdx.x; c < nchunks; c += 64 * SELECT_GROUPS) lchunk[c] = make_float2(ib.bstep[c], ib.berr[c]);
+    // every thread walks ~nchunks / 16 chunks: their (step, max E) once per workgroup into LDS
+    if (ib.qerr && chunk_lds) stage_chunk_bounds<64 * SELECT_GROUPS>(lchunk, ib, nchunks);
     __syncthreads();
     if (ib.qerr) {
         // Records of the int8 pass: integer scores in the units of (query group step) x (map chunk step).  In exact score
@@ -44,8 +47,15 @@ __global__ __launch_bounds__(64 * SELECT_GROUPS) void match_select_kernel(const 
         // kernel (qmax holds its float_key).  Every chunk with upper_c >= qlow is a candidate:
         // the oracle's arg-max row is inside one of them, and match_refine_kernel finds the rows (int8 rescan, then fp32).
         // fp32 evaluation of the bounds: three roundings on magnitudes <= 2 -- 1e-6 of slack covers them.
-        const float eq = ib.qerr[q], sq = ib.qstep[q >> 7];
-        const float A = eq * 1.0001220703125f, mult = 1.0001220703125f + eq, slack = 1.0e-6f;
+        // These two branches are the A/B reference ("coarse_variant" 20) of match_select_top2_kernel and match_select_best_kernel.
+        // Their sweeps keep the text they had before match_select.h, `bound` and `up1` being chunk_upper's expression written out:
+        // the compiler unswitches these loops on chunk_lds as they stand; through sweep_query_records, chunk_bounds and chunk_upper
+        // the finish call of a top-2 search at C2 took 0.198 ms instead of 0.144, and of the two wordings of the best-score loop
+        // that were compiled once per case one lost 14 % on int8 bounds and the other 1.4 - 3.4 % on fp6 bounds
+        // (profiles/select_refactor.md).  A change to chunk_upper has to be made here too.
+        const float sq = ib.qstep[q >> 7];
+        const QueryBound qb = query_bound(ib.qerr[q]);
+        const float A = qb.A, mult = qb.mult, slack = SELECT_SLACK;
         const float qlow = key_float(qmax[q]);  // -Inf: no un-padded chunk exists -> every chunk is a candidate
         float maxup = -__builtin_inff();
         if (ib.top2) {
@@ -133,47 +143,18 @@ __global__ __launch_bounds__(64 * SELECT_GROUPS) void match_select_kernel(const 
     }
     }
     __syncthreads();
-    if (g == 0 && ib.qerr) {
-        // load figure of the int8 pass: candidate chunks that match_refine_kernel will rescan (the caller's feedback for
-        // choosing between this pass and the fp16 one on duplicate-rich maps: vfm_match_search_rescans_async); one atomic
-        // per workgroup
-        int mine = 0;
-        // (top-2 records: whole-chunk entries count 1, single-row entries 1/32 -- 48 KB of int8 tiles against 1.5 KB of fp32 row)
-        if (q < n && invq[q] != 0.0f && !(key_float(lub[qq]) < gate) && lcnt[qq] <= cap)
-            mine = ib.top2 ? lresc[qq] + ((lcnt[qq] - lresc[qq]) >> 5) : lcnt[qq];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-        if (qq == 0 && mine > 0) atomicAdd(fb_count + 5, mine);
-    }
+    // load figure of the int8 pass: candidate chunks that match_refine_kernel will rescan; one atomic per workgroup
+    if (g == 0 && ib.qerr)
+        add_load_figure(fb_count, q < n ? bounded_query_load(invq[q], key_float(lub[qq]) < gate, lcnt[qq], ib.top2 ? lresc[qq] : lcnt[qq], cap) : 0);
     if (g == 0 && q < n) {
         const int cnt = lcnt[qq];
-        // statistics (vfm_debug_match_stats): [2] candidate entries, [8 + b] queries with 2^(b-1) < entries <= 2^b
-        if (stats && invq[q] != 0.0f) {
-            atomicAdd(fb_count + 2, cnt);
-            int bin = 0;
-            while ((1 << bin) < cnt && bin < 15) ++bin;
-            atomicAdd(fb_count + 8 + bin, 1);
-        }
-        if (invq[q] == 0.0f) {
-            cand_cnt[q] = 0;  // zero query row: decided directly (index 0, score 0)
-        } else if (ib.qerr && key_float(lub[qq]) < gate) {
-            // no row of the map can reach the caller's similarity gate (VoxelHashMap.cpp:501-511 drops such queries):
-            // the query is not resolved further -- match_rescore_kernel reports (index -1, similarity -2)
-            cand_cnt[q] = -2;
-        } else if (cnt > cap) {
-            cand_cnt[q] = -1;  // overflow: decided by the exact all-pairs kernel
-            const int slot = atomicAdd(fb_count, 1);
-            fb_list[slot] = (int)q;
-        } else {
-            cand_cnt[q] = cnt;
-        }
+        close_query(SelectClose{invq, cand_cnt, fb_count, fb_list, stats}, q, cnt, ib.qerr && key_float(lub[qq]) < gate, cnt > cap, cnt);
     }
 }
 
-// Packed top-2 records of the int8 pass ([query tile][chunk][32], 8 bytes each): the int8 / top-2 branch of
-// match_select_kernel laid out for the sweep, as match_select_best_kernel below.  A lane owns two consecutive queries of the
-// tile and one chunk of a block of four: a wave's load instruction covers 4 chunks x 32 queries = 1 KiB of consecutive
-// record bytes.  Queries that provably end below the gate record nothing (see match_select_best_kernel).
+// Packed top-2 records of the int8 pass ([query tile][chunk][32], 8 bytes each): the int8 / top-2 branch of match_select_kernel --
+// the same pieces of match_select.h, hence the same decision -- in the tile kernels' sweep with two queries per lane.  Queries that
+// provably end below the gate record nothing (dead_queries).
 constexpr int SELECT_TOP2_WAVES = 8;
 __global__ __launch_bounds__(64 * SELECT_TOP2_WAVES) void match_select_top2_kernel(
     const uint2* __restrict__ recs, int nchunks, int64_t n, int first_pad_chunk, const unsigned* __restrict__ qmax,
@@ -185,7 +166,6 @@ __global__ __launch_bounds__(64 * SELECT_TOP2_WAVES) void match_select_top2_kern
     __shared__ unsigned lub[32];  // float_key of the largest upper bound over the query's chunks
     __shared__ unsigned lmaxe;
     __shared__ int ldead[32];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int qt = blockIdx.x;
     if (threadIdx.x < 32) {
         lcnt[threadIdx.x] = 0;
@@ -195,130 +175,62 @@ __global__ __launch_bounds__(64 * SELECT_TOP2_WAVES) void match_select_top2_kern
     if (threadIdx.x == 0) lmaxe = 0u;
     __syncthreads();
     float2* lchunk = reinterpret_cast<float2*>(select_smem);
-    if (chunk_lds) {
-        float me = 0.0f;
-        for (int c = threadIdx.x; c < nchunks; c += 64 * SELECT_TOP2_WAVES) {
-            const float2 v = make_float2(ib.bstep[c], ib.berr[c]);
-            lchunk[c] = v;
-            me = fmaxf(me, v.y);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) me = fmaxf(me, __shfl_xor(me, off));
-        if (lane == 0) atomicMax(&lmaxe, float_key(me));
-    }
+    if (chunk_lds) raise_workgroup_max(&lmaxe, stage_chunk_bounds<64 * SELECT_TOP2_WAVES>(lchunk, ib, nchunks));
     __syncthreads();
-    const int lq = (lane & 15) * 2, lc = lane >> 4;
+    const int lq = TileLane<2>().lq;
     const int64_t q0 = (int64_t)qt * 32 + lq;   // the lane's two queries
-    const float sq = ib.qstep[q0 >> 7], slack = 1.0e-6f;
-    float A[2], mult[2], qlow[2], maxup[2];
-    unsigned deadmask = 0u;
-    const float maxe = chunk_lds ? key_float(lmaxe) : __builtin_inff();
+    const float sq = ib.qstep[q0 >> 7];
+    QueryBound qb[2];
+    float qlow[2], maxup[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const float eq = ib.qerr[q0 + j];
-        A[j] = eq * 1.0001220703125f;
-        mult[j] = 1.0001220703125f + eq;
+        qb[j] = query_bound(ib.qerr[q0 + j]);
         qlow[j] = key_float(qmax[q0 + j]);
         maxup[j] = -__builtin_inff();
-        const bool dead = qlow[j] + 2.0f * (A[j] + mult[j] * maxe) + 1.0e-5f < gate;
-        deadmask |= dead ? (1u << j) : 0u;
     }
-    const uint4* src = reinterpret_cast<const uint4*>(recs + (size_t)qt * nchunks * 32) + (lane & 15);
-    for (int c = first_pad_chunk; c < nchunks && deadmask; ++c) {  // padded chunks are not covered by qlow
-        const uint4 r = src[(size_t)c * 16];
-        const unsigned r1[2] = {r.x, r.z};
-        const float sc = sq * ib.bstep[c], be = ib.berr[c];
+    const uint4* tile = reinterpret_cast<const uint4*>(recs + (size_t)qt * nchunks * 32);
+    const unsigned deadmask = dead_queries<2>(qb, qlow, chunk_lds ? key_float(lmaxe) : __builtin_inff(), gate, sq, ib, first_pad_chunk,
+                                              nchunks, lq, q0, n, invq, ldead, [&](int c, int (&S)[2]) {
+                                                  const uint4 r = tile_chunk_records<2>(tile, c);
+                                                  S[0] = top2_first_score(r.x);
+                                                  S[1] = top2_first_score(r.z);
+                                              });
+    sweep_tile_records<2, SELECT_TOP2_WAVES>(tile, nchunks, [&](int c, uint4 rec) {
+        const float2 cb2 = chunk_bounds(lchunk, chunk_lds, ib, c);
+        const float sc = sq * cb2.x;
+        const unsigned r1[2] = {rec.x, rec.z}, r2[2] = {rec.y, rec.w};
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-            if (!(sc * (float)((int)(r1[j] | 127u) - I8_OFFSET) + (A[j] + mult[j] * be + slack) < gate)) deadmask &= ~(1u << j);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        if (q0 + j >= n || invq[q0 + j] == 0.0f) deadmask |= 1u << j;
-        if (threadIdx.x < 16) ldead[lq + j] = (deadmask >> j) & 1u;
-    }
-    const int nblocks = (nchunks + 3) >> 2;
-    for (int cb0 = wave; cb0 < nblocks; cb0 += 8 * SELECT_TOP2_WAVES) {
-        uint4 rec[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int cb = cb0 + SELECT_TOP2_WAVES * u;
-            rec[u] = (cb * 4 + lc < nchunks) ? src[((size_t)cb * 4 + lc) * 16] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = (cb0 + SELECT_TOP2_WAVES * u) * 4 + lc;
-            if (c >= nchunks) continue;
-            const float2 cb2 = chunk_lds ? lchunk[c] : make_float2(ib.bstep[c], ib.berr[c]);
-            const float sc = sq * cb2.x;
-            const unsigned r1[2] = {rec[u].x, rec[u].z}, r2[2] = {rec[u].y, rec[u].w};
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float bound = A[j] + mult[j] * cb2.y + slack;
-                const float up1 = sc * (float)((int)(r1[j] | 127u) - I8_OFFSET) + bound;
-                maxup[j] = fmaxf(maxup[j], up1);
-                if (up1 >= qlow[j] && !((deadmask >> j) & 1u)) {
-                    const int slot = atomicAdd(&lcnt[lq + j], 1);
-                    // the best row's index rides in the low 7 bits: a candidate chunk whose SECOND-best score cannot reach
-                    // qlow is a single-row entry and needs no rescan
-                    const float up2 = sc * (float)((int)(r2[j] | 63u) - I8_OFFSET) + bound;
-                    const unsigned rescan = (up2 >= qlow[j] || c >= first_pad_chunk) ? 1u : 0u;
-                    if (rescan) atomicAdd(&lresc[lq + j], 1);
-                    if (slot < cap) cand[(size_t)(q0 + j) * cap + slot] = ((unsigned)c << 8) | (rescan << 7) | (r1[j] & 127u);
-                }
+        for (int j = 0; j < 2; ++j) {
+            const float up1 = chunk_upper(sc, top2_first_score(r1[j]), qb[j], cb2.y);
+            maxup[j] = fmaxf(maxup[j], up1);
+            if (up1 >= qlow[j] && !((deadmask >> j) & 1u)) {
+                const int slot = atomicAdd(&lcnt[lq + j], 1);
+                // the best row's index rides in the low 7 bits: a candidate chunk whose SECOND-best score cannot reach
+                // qlow is a single-row entry and needs no rescan
+                const float up2 = chunk_upper(sc, top2_second_score(r2[j]), qb[j], cb2.y);
+                const unsigned rescan = (up2 >= qlow[j] || c >= first_pad_chunk) ? 1u : 0u;
+                if (rescan) atomicAdd(&lresc[lq + j], 1);
+                if (slot < cap) cand[(size_t)(q0 + j) * cap + slot] = ((unsigned)c << 8) | (rescan << 7) | (r1[j] & 127u);
             }
         }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        float v = maxup[j];
-        v = fmaxf(v, __shfl_xor(v, 16));
-        v = fmaxf(v, __shfl_xor(v, 32));
-        if (lane < 16) atomicMax(&lub[lq + j], float_key(v));
-    }
+        return false;
+    });
+    raise_query_max<2>(lub, lq, maxup);
     __syncthreads();
-    if (threadIdx.x < 64) {   // one wave: the tile's 32 queries
-        const int qq = lane & 31;
-        const int64_t q = (int64_t)qt * 32 + qq;
-        const bool live = lane < 32 && q < n;
-        const int cnt = lcnt[qq];
-        // load figure (vfm_match_search_rescans_async): whole-chunk entries count 1, single-row entries 1/32 -- 48 KB of int8
-        // tiles against 1.5 KB of fp32 row
-        int mine = 0;
-        if (live && invq[q] != 0.0f && !(key_float(lub[qq]) < gate) && cnt <= cap) mine = lresc[qq] + ((cnt - lresc[qq]) >> 5);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-        if (lane == 0 && mine > 0) atomicAdd(fb_count + 5, mine);
-        if (live) {
-            if (stats && invq[q] != 0.0f) {
-                atomicAdd(fb_count + 2, cnt);
-                int bin = 0;
-                while ((1 << bin) < cnt && bin < 15) ++bin;
-                atomicAdd(fb_count + 8 + bin, 1);
-            }
-            const bool dead = ldead[qq] != 0;
-            if (invq[q] == 0.0f) {
-                cand_cnt[q] = 0;  // zero query row: decided directly (index 0, score 0)
-            } else if (key_float(lub[qq]) < gate) {
-                cand_cnt[q] = -2;  // no row of the map can reach the caller's similarity gate
-            } else if (cnt > cap || dead) {
-                cand_cnt[q] = -1;  // overflow (or a "dead" query lifted past the gate after all): the all-pairs kernel decides
-                const int slot = atomicAdd(fb_count, 1);
-                fb_list[slot] = (int)q;
-            } else {
-                cand_cnt[q] = cnt;
-            }
-        }
-    }
+    close_tile_queries(
+        SelectClose{invq, cand_cnt, fb_count, fb_list, stats}, qt, n, lcnt, true,
+        [&](int qq, int64_t q, int cnt) { return bounded_query_load(invq[q], key_float(lub[qq]) < gate, cnt, lresc[qq], cap); },
+        [&](int qq, int) { return key_float(lub[qq]) < gate; }, [&](int qq, int cnt) { return cnt > cap || ldead[qq] != 0; },
+        [&](int, int cnt) { return cnt; });
 }
 
 // Half-width pass (VFM_RECORDS_HALF): the records hold the best integer score of every (query, chunk) over the FIRST d / 2
 // columns.  With r_q = |second half of the normalised query|, R_c = max over the chunk's rows of |second half of the row|
 // (both rounded up, prep_chunk_kernel) and the quantisation bound A + B_c of the full rows (an upper bound for any subset of
-// columns):      best exact score of chunk c  <=  s_q s_c S_half(c) + A + B_c + r_q R_c       (Cauchy-Schwarz on the other half)
+// columns):      best exact score of chunk c  <=  s_q s_c S_half(c) + A + B_c + r_q R_c       (chunk_upper_half)
 // A chunk survives for a query iff that bound reaches the gate; the survivors are binned per chunk (or left in the query's
 // list) for the full-width int8 rescan, whose hit test is then the gate itself.  A query without survivors provably has no
-// match (cand_cnt = -2).  Same sweep layout as match_select_best_kernel.
+// match (cand_cnt = -2).  cand == NULL: the probe (vfm_match_search_probe_half), the survivors are only counted.
 __global__ __launch_bounds__(64 * 8) void match_select_half_kernel(
     const unsigned* __restrict__ best, int nchunks, int64_t n, const float* __restrict__ invq, I8Bounds ib,
     const float* __restrict__ qrest, const float* __restrict__ grest, float gate, int chunk_lds, int* __restrict__ cand_cnt,
@@ -327,7 +239,6 @@ __global__ __launch_bounds__(64 * 8) void match_select_half_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char select_smem[];  // the chunks' (step, max E) and max |rest|
     __shared__ int lcnt[32];
     __shared__ int lov[32];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int qt = blockIdx.x;
     if (threadIdx.x < 32) {
         lcnt[threadIdx.x] = 0;
@@ -335,116 +246,62 @@ __global__ __launch_bounds__(64 * 8) void match_select_half_kernel(
     }
     float2* lchunk = reinterpret_cast<float2*>(select_smem);
     float* lrest = reinterpret_cast<float*>(lchunk + nchunks);
-    if (chunk_lds)
-        for (int c = threadIdx.x; c < nchunks; c += 64 * 8) {
-            lchunk[c] = make_float2(ib.bstep[c], ib.berr[c]);
-            lrest[c] = grest[c];
-        }
+    if (chunk_lds) stage_chunk_bounds<64 * 8>(lchunk, ib, nchunks, [&](int c) { lrest[c] = grest[c]; });
     __syncthreads();
-    const int lq = (lane & 7) * 4, lc = lane >> 3;
+    const int lq = TileLane<4>().lq;
     const int64_t q0 = (int64_t)qt * 32 + lq;   // the lane's four queries (rows of the padded tile always exist)
-    const float sq = ib.qstep[q0 >> 7], slack = 1.0e-6f;
-    float A[4], mult[4], rq[4];
+    const float sq = ib.qstep[q0 >> 7];
+    QueryBound qb[4];
+    float rq[4];
     unsigned livemask = 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float eq = ib.qerr[q0 + j];
-        A[j] = eq * 1.0001220703125f;
-        mult[j] = 1.0001220703125f + eq;
+        qb[j] = query_bound(ib.qerr[q0 + j]);
         rq[j] = qrest[q0 + j];
         if (q0 + j < n && invq[q0 + j] != 0.0f) livemask |= 1u << j;
     }
-    const uint4* src = reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32) + lane;
-    const int nblocks = (nchunks + 7) >> 3;
-    for (int cb0 = wave; cb0 < nblocks; cb0 += 8 * 8) {
-        if (cand) {
-            // The guard, early: once four queries of a lane average 4 x HALF_GUARD_PER_QUERY surviving chunks the search is going to
-            // take the gate pass anyway (half_guard_kernel) -- raise its flag now, leave a load figure that says so, and stop: on
-            // descriptors that are all alike the full sweep (31 million survivors, each a few atomics) took 21 ms.  Every workgroup
-            // stops at the flag; the gate pass ignores what the lists hold.
-            if (__hip_atomic_load(fb_count + HALF_GUARD_FLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-        }
-        bool stop = false;
-        uint4 rec[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int cb = cb0 + 8 * u;
-            rec[u] = (cb * 8 + lc < nchunks) ? src[(size_t)cb * 64] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = (cb0 + 8 * u) * 8 + lc;
-            if (c >= nchunks || stop) continue;
+    const SelectLists L{bin_cnt, bins, bin_cap, cand, cap};
+    sweep_tile_records<4, 8>(
+        reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32), nchunks,
+        // The guard, early: once four queries of a lane average 4 x HALF_GUARD_PER_QUERY surviving chunks the search is going to
+        // take the gate pass anyway (half_guard_kernel) -- raise its flag now, leave a load figure that says so, and stop: on
+        // descriptors that are all alike the full sweep (31 million survivors, each a few atomics) took 21 ms.  Every workgroup
+        // stops at the flag; the gate pass ignores what the lists hold.
+        [&] { return !(cand && __hip_atomic_load(fb_count + HALF_GUARD_FLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0); },
+        [&](int c, uint4 rec) {
             if (cand && lcnt[lq] + lcnt[lq + 1] + lcnt[lq + 2] + lcnt[lq + 3] > 16 * HALF_GUARD_PER_QUERY) {
                 if (atomicExch(fb_count + HALF_GUARD_FLAG, 1) == 0) atomicExch(fb_count + 5, 0x3FFFFFFF);
-                stop = true;
-                continue;
+                return true;
             }
-            const float2 cb2 = chunk_lds ? lchunk[c] : make_float2(ib.bstep[c], ib.berr[c]);
+            const float2 cb2 = chunk_bounds(lchunk, chunk_lds, ib, c);
             const float rb = chunk_lds ? lrest[c] : grest[c];
             const float sc = sq * cb2.x;
-            const unsigned r4[4] = {rec[u].x, rec[u].y, rec[u].z, rec[u].w};
+            const unsigned r4[4] = {rec.x, rec.y, rec.z, rec.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                // fp32 evaluation: five roundings on magnitudes <= 2 -- 2e-6 of slack covers them
-                const float up = sc * (float)((int)r4[j] - I8_OFFSET) + (A[j] + mult[j] * cb2.y + slack) + (rq[j] * rb + slack);
+                const float up = chunk_upper_half(sc, best_score(r4[j]), qb[j], cb2.y, rq[j], rb);
                 if (!(up < gate) && ((livemask >> j) & 1u)) {
-                    int slot = atomicAdd(&lcnt[lq + j], 1);
-                    if (!cand) continue;  // probe (vfm_match_search_probe_half): the survivors are only counted
-                    if (bins) {
-                        // (a full bin is not touched again: on descriptors that are all alike every query survives in every
-                        // chunk, and 31 million atomics on 1563 addresses were most of this kernel's time there)
-                        const unsigned seen = __hip_atomic_load(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned pos = seen >= (unsigned)bin_cap ? seen : atomicAdd(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], 1u);
-                        if (pos < (unsigned)bin_cap) {
-                            bins[(size_t)c * bin_cap + pos] = (int)(q0 + j);
-                            slot = cap;
-                        } else {
-                            slot = atomicAdd(&lov[lq + j], 1);
-                        }
-                    }
-                    if (slot < cap) cand[(size_t)(q0 + j) * cap + slot] = ((unsigned)c << 8) | 128u;  // whole-chunk entry
+                    const int slot = atomicAdd(&lcnt[lq + j], 1);
+                    if (!cand) continue;  // probe: the survivors are only counted
+                    // (with bins the look at the counter comes first always: a full bin is not touched again)
+                    if (bins) place_candidate(L, q0 + j, c, true, &lov[lq + j]);
+                    else own_list_entry(L, q0 + j, slot, c);
                 }
             }
-        }
-        if (stop) break;
-    }
+            return false;
+        });
     __syncthreads();
-    if (threadIdx.x < 64) {   // one wave: the tile's 32 queries
-        const int qq = lane & 31;
-        const int64_t q = (int64_t)qt * 32 + qq;
-        const bool live = lane < 32 && q < n;
-        const int cnt = lcnt[qq];
-        int mine = (live && (cnt <= cap || !cand)) ? cnt : 0;   // load figure (vfm_match_search_rescans_async): surviving chunks
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-        if (lane == 0 && mine > 0) atomicAdd(fb_count + 5, mine);
-        if (live && cand) {
-            if (stats && invq[q] != 0.0f) {
-                atomicAdd(fb_count + 2, cnt);
-                int bin = 0;
-                while ((1 << bin) < cnt && bin < 15) ++bin;
-                atomicAdd(fb_count + 8 + bin, 1);
-            }
-            if (invq[q] == 0.0f) {
-                cand_cnt[q] = 0;  // zero query row: decided directly (index 0, score 0)
-            } else if (cnt == 0) {
-                cand_cnt[q] = -2;  // no chunk can hold a row at the gate
-            } else if (cnt > cap) {
-                cand_cnt[q] = -1;  // more surviving chunks than a list holds: the all-pairs kernel decides
-                const int slot = atomicAdd(fb_count, 1);
-                fb_list[slot] = (int)q;
-            } else {
-                cand_cnt[q] = bins ? lov[qq] : cnt;
-            }
-        }
-    }
+    close_tile_queries(
+        SelectClose{invq, cand_cnt, fb_count, fb_list, stats}, qt, n, lcnt, cand != nullptr,
+        [&](int, int64_t, int cnt) { return (cnt <= cap || !cand) ? cnt : 0; },   // load figure: surviving chunks
+        [&](int, int cnt) { return cnt == 0; },                                  // no chunk can hold a row at the gate
+        [&](int, int cnt) { return cnt > cap; }, [&](int qq, int cnt) { return bins ? lov[qq] : cnt; });
 }
 
 // VFM_RECORDS_MX6_HALF_FUSED: the fused fp6 half-width kernel (match_coarse_mx6.hip) has tested every (query, chunk) pair against
 // the gate itself and left each workgroup's survivors in a slot of the record buffer -- [count, query block, first chunk, overflow]
 // + entries (chunk of the slice << 9 | query of the block).  This kernel does the placement match_select_half_kernel does for its
-// survivors: into the chunk's rescan bin, past a full bin into the query's own list.  One wave per slot; ~11 000 entries at C2 on
+// survivors (place_candidate; the own list's length is cand_cnt itself).  One wave per slot; ~11 000 entries at C2 on
 // SURVEY D.2 data (0.56 per query) against the 122 MB sweep of the records this replaces.  With the guard up (a slot overflowed:
 // descriptors that are all alike) nothing is placed: match_gatepass_kernel decides every query.
 __global__ __launch_bounds__(256) void match_bin_survivors_kernel(const unsigned* __restrict__ surv, int slot_words, const int* __restrict__ fb_count,
@@ -453,6 +310,7 @@ __global__ __launch_bounds__(256) void match_bin_survivors_kernel(const unsigned
     if (fb_count[HALF_GUARD_FLAG] != 0) return;
     const int nslots = fb_count[MX6_GRID_SLOT];
     const int lane = lane_id(), nwaves = (int)gridDim.x * 4;
+    const SelectLists L{bin_cnt, bins, bin_cap, cand, cap};
     for (int sidx = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); sidx < nslots; sidx += nwaves) {
         const unsigned* slot = surv + (size_t)sidx * slot_words;
         const unsigned cnt = slot[0], qb = slot[1], c0 = slot[2];
@@ -464,22 +322,14 @@ __global__ __launch_bounds__(256) void match_bin_survivors_kernel(const unsigned
             const unsigned e = slot[4 + i];
             const int chunk = (int)(c0 + (e >> qshift));
             const int64_t q = (int64_t)qb * qper + (int64_t)(e & ((1u << qshift) - 1u));
-            const unsigned pos = atomicAdd(&bin_cnt[(size_t)chunk * BIN_CNT_STRIDE], 1u);
-            if (pos < (unsigned)bin_cap) {
-                bins[(size_t)chunk * bin_cap + pos] = (int)q;
-            } else {   // a full bin leaves the entry in the query's own list (match_rescan_kernel)
-                const int own = atomicAdd(&cand_cnt[q], 1);
-                if (own < cap) cand[(size_t)q * cap + own] = ((unsigned)chunk << 8) | 128u;
-            }
+            place_candidate(L, q, chunk, false, &cand_cnt[q]);
         }
     }
 }
 
-// Best-score records of the int8 pass ([query tile][chunk][32], 4 bytes each): the same decision as the int8 branch of
-// match_select_kernel, laid out for the sweep.  One workgroup per query tile; a lane owns four consecutive queries of the
-// tile and one chunk of a block of eight, so a wave's load instruction covers 8 chunks x 32 queries = 1 KiB of consecutive
-// record bytes (the general kernel reads two 128-byte pieces per instruction: 103 us for the 125 MB of C2's records; this
-// one is bound by the sweep itself).
+// Best-score records of the int8 pass ([query tile][chunk][32], 4 bytes each): the int8 branch of match_select_kernel -- the same
+// pieces of match_select.h, hence the same decision -- in the tile kernels' sweep with four queries per lane (the general kernel
+// reads two 128-byte pieces per instruction: 103 us for the 125 MB of C2's records; this one is bound by the sweep itself).
 constexpr int SELECT_BEST_WAVES = 8;
 constexpr int SELECT_BEST_LCAND = 6144;   // candidates of a query tile staged in the LDS (192 per query; beyond: the direct path)
 __global__ __launch_bounds__(64 * SELECT_BEST_WAVES) void match_select_best_kernel(
@@ -492,14 +342,11 @@ __global__ __launch_bounds__(64 * SELECT_BEST_WAVES) void match_select_best_kern
     __shared__ int lov[32];       // bins != NULL: those of them that did not fit their chunk's bin (they go to the query's own list)
     __shared__ unsigned lub[32];  // float_key of the largest upper bound over the query's chunks
     __shared__ unsigned lmaxe;    // float_key of the largest max E over the chunks
-    __shared__ int ldead[32];     // the query records nothing (see below)
-    // The tile's candidates, (query of the tile << 27) | chunk: a candidate costs two LDS atomics inside the sweep; the global
-    // side -- the chunk's bin (a returning atomic on one of ~1500 addresses) or the query's own list -- is done behind the
-    // sweep for all of them at once.  Inside the sweep every candidate had stalled its wave for a round trip: 151 us against
-    // 70 at 12 candidate chunks per query (lifted descriptors) and 317 at 46 (the fp6 pass's bounds).
+    __shared__ int ldead[32];     // the query records nothing (dead_queries)
+    // The tile's candidates (stage_candidate): 151 us against 70 with the global side inside the sweep at 12 candidate chunks per
+    // query (lifted descriptors) and 317 at 46 (the fp6 pass's bounds).
     __shared__ unsigned lcand[SELECT_BEST_LCAND];
     __shared__ int lcand_n;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int qt = blockIdx.x;
     if (threadIdx.x < 32) {
         lcnt[threadIdx.x] = 0;
@@ -514,103 +361,51 @@ __global__ __launch_bounds__(64 * SELECT_BEST_WAVES) void match_select_best_kern
     float2* lchunk = reinterpret_cast<float2*>(select_smem);
     unsigned* lhist = reinterpret_cast<unsigned*>(lchunk + nchunks);   // chunk_lds == 2: the tile's candidates per chunk, then the bins' positions
     const bool hist = chunk_lds == 2 && bins != nullptr;
-    if (chunk_lds) {
-        float me = 0.0f;
-        for (int c = threadIdx.x; c < nchunks; c += 64 * SELECT_BEST_WAVES) {
-            const float2 v = make_float2(ib.bstep[c], ib.berr[c]);
-            lchunk[c] = v;
-            if (hist) lhist[c] = 0u;
-            me = fmaxf(me, v.y);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) me = fmaxf(me, __shfl_xor(me, off));
-        if (lane == 0) atomicMax(&lmaxe, float_key(me));
-    }
+    if (chunk_lds)
+        raise_workgroup_max(&lmaxe, stage_chunk_bounds<64 * SELECT_BEST_WAVES>(lchunk, ib, nchunks, [&](int c) {
+                                if (hist) lhist[c] = 0u;
+                            }));
     __syncthreads();
-    const int lq = (lane & 7) * 4, lc = lane >> 3;
+    const int lq = TileLane<4>().lq;
     const int64_t q0 = (int64_t)qt * 32 + lq;   // the lane's four queries (rows of the padded tile always exist)
-    const float sq = ib.qstep[q0 >> 7], slack = 1.0e-6f;
-    float A[4], mult[4], qlow[4], maxup[4];
-    // "dead": the query provably ends below the gate, so its candidates are not even recorded (at C2 the unmatched half of
-    // the scan would write sixteen entries per query).  Every un-padded chunk has upper_c = lower_c + 2 (A + mult E_c) up
-    // to roundings of 1e-6 and lower_c <= qlow, so the largest upper bound over them is below qlow + 2 (A + mult max E)
-    // + 1e-5; the (at most two) padded chunks are not covered by qlow: their records are looked at here.  Should the sweep
-    // find the largest upper bound at or above the gate after all, the query goes to the all-pairs kernel (epilogue).
-    // Zero query rows (decided directly) and the rows that pad the last tile record nothing either.
-    unsigned deadmask = 0u;
-    const float maxe = chunk_lds ? key_float(lmaxe) : __builtin_inff();
+    const float sq = ib.qstep[q0 >> 7];
+    QueryBound qb[4];
+    float qlow[4], maxup[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float eq = ib.qerr[q0 + j];
-        A[j] = eq * 1.0001220703125f;
-        mult[j] = 1.0001220703125f + eq;
+        qb[j] = query_bound(ib.qerr[q0 + j]);
         qlow[j] = key_float(qmax[q0 + j]);  // -Inf: no un-padded chunk exists -> every chunk is a candidate
         maxup[j] = -__builtin_inff();
-        const bool dead = qlow[j] + 2.0f * (A[j] + mult[j] * maxe) + 1.0e-5f < gate;
-        deadmask |= dead ? (1u << j) : 0u;
     }
-    for (int c = first_pad_chunk; c < nchunks && deadmask; ++c) {
-        const uint4 r = reinterpret_cast<const uint4*>(best + ((size_t)qt * nchunks + c) * 32)[lane & 7];
-        const unsigned r4[4] = {r.x, r.y, r.z, r.w};
-        const float sc = sq * ib.bstep[c], be = ib.berr[c];
+    const uint4* tile = reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32);
+    const unsigned deadmask = dead_queries<4>(qb, qlow, chunk_lds ? key_float(lmaxe) : __builtin_inff(), gate, sq, ib, first_pad_chunk,
+                                              nchunks, lq, q0, n, invq, ldead, [&](int c, int (&S)[4]) {
+                                                  const uint4 r = tile_chunk_records<4>(tile, c);
+                                                  S[0] = best_score(r.x);
+                                                  S[1] = best_score(r.y);
+                                                  S[2] = best_score(r.z);
+                                                  S[3] = best_score(r.w);
+                                              });
+    // candidate (query qq of the tile, chunk c): lov counts the own list's entries with bins or without.  crowded: a tile with more
+    // than 64 candidate chunks per query looks at the bin's counter first (place_candidate)
+    const SelectLists L{bin_cnt, bins, bin_cap, cand, cap};
+    auto place = [&](int qq, int c, bool crowded) { place_candidate(L, (int64_t)qt * 32 + qq, c, crowded, &lov[qq]); };
+    sweep_tile_records<4, SELECT_BEST_WAVES>(tile, nchunks, [&](int c, uint4 rec) {
+        const float2 cb2 = chunk_bounds(lchunk, chunk_lds, ib, c);
+        const float sc = sq * cb2.x;
+        const unsigned r4[4] = {rec.x, rec.y, rec.z, rec.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (!(sc * (float)((int)r4[j] - I8_OFFSET) + (A[j] + mult[j] * be + slack) < gate)) deadmask &= ~(1u << j);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (q0 + j >= n || invq[q0 + j] == 0.0f) deadmask |= 1u << j;
-        if (threadIdx.x < 8) ldead[lq + j] = (deadmask >> j) & 1u;
-    }
-    const uint4* src = reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32) + lane;
-    const int nblocks = (nchunks + 7) >> 3;
-    // candidate (query qq of the tile, chunk c): chunk-major rescan -> the query joins the chunk's bin, a full bin leaves the entry
-    // with the query; otherwise the entry goes to the query's own list (lov counts the list's entries either way)
-    // (crowded: a tile with more than 64 candidate chunks per query looks at the counter first -- on descriptors that are all alike
-    // every bin is full after the first tiles, and 31 million atomics on 1563 addresses were most of the kernel's time then; below
-    // that the look is a second trip to the memory side per candidate for nothing)
-    auto place = [&](int qq, int c, bool crowded) {
-        const int64_t q = (int64_t)qt * 32 + qq;
-        if (bins) {
-            const unsigned seen = crowded ? __hip_atomic_load(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-            const unsigned pos = seen >= (unsigned)bin_cap ? seen : atomicAdd(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], 1u);
-            if (pos < (unsigned)bin_cap) {
-                bins[(size_t)c * bin_cap + pos] = (int)q;
-                return;
+        for (int j = 0; j < 4; ++j) {
+            const float up1 = chunk_upper(sc, best_score(r4[j]), qb[j], cb2.y);
+            maxup[j] = fmaxf(maxup[j], up1);
+            // (zero-padded rows score exactly 0: a padded chunk is a candidate only if 0 is inside the bounds)
+            if (up1 >= qlow[j] && !((deadmask >> j) & 1u)) {
+                atomicAdd(&lcnt[lq + j], 1);
+                if (!stage_candidate(lcand, &lcand_n, SELECT_BEST_LCAND, lq + j, c)) place(lq + j, c, true);   // the staging buffer is full: placed on the spot
             }
         }
-        const int slot = atomicAdd(&lov[qq], 1);
-        if (slot < cap) cand[(size_t)q * cap + slot] = ((unsigned)c << 8) | 128u;  // whole-chunk entry
-    };
-    for (int cb0 = wave; cb0 < nblocks; cb0 += 8 * SELECT_BEST_WAVES) {
-        uint4 rec[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int cb = cb0 + SELECT_BEST_WAVES * u;
-            rec[u] = (cb * 8 + lc < nchunks) ? src[(size_t)cb * 64] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = (cb0 + SELECT_BEST_WAVES * u) * 8 + lc;
-            if (c >= nchunks) continue;
-            const float2 cb2 = chunk_lds ? lchunk[c] : make_float2(ib.bstep[c], ib.berr[c]);
-            const float sc = sq * cb2.x;
-            const unsigned r4[4] = {rec[u].x, rec[u].y, rec[u].z, rec[u].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float bound = A[j] + mult[j] * cb2.y + slack;
-                const float up1 = sc * (float)((int)r4[j] - I8_OFFSET) + bound;
-                maxup[j] = fmaxf(maxup[j], up1);
-                // (zero-padded rows score exactly 0: a padded chunk is a candidate only if 0 is inside the bounds)
-                if (up1 >= qlow[j] && !((deadmask >> j) & 1u)) {
-                    atomicAdd(&lcnt[lq + j], 1);
-                    const int at = atomicAdd(&lcand_n, 1);
-                    if (at < SELECT_BEST_LCAND) lcand[at] = ((unsigned)(lq + j) << 27) | (unsigned)c;
-                    else place(lq + j, c, true);   // the staging buffer is full: placed on the spot
-                }
-            }
-        }
-    }
+        return false;
+    });
     __syncthreads();
     {
         const int ncand = lcand_n < SELECT_BEST_LCAND ? lcand_n : SELECT_BEST_LCAND;
@@ -650,68 +445,24 @@ __global__ __launch_bounds__(64 * SELECT_BEST_WAVES) void match_select_best_kern
             }
             __syncthreads();
             for (int i = threadIdx.x; i < ncand; i += 64 * SELECT_BEST_WAVES) {
-                const unsigned e = lcand[i];
-                const int qq = (int)(e >> 27), c = (int)(e & 0xFFFFu);
-                const unsigned pos = lhist[c] + ((e >> 16) & 31u);
-                const int64_t q = (int64_t)qt * 32 + qq;
-                if (pos < (unsigned)bin_cap) {
-                    bins[(size_t)c * bin_cap + pos] = (int)q;
-                } else {
-                    const int slot = atomicAdd(&lov[qq], 1);
-                    if (slot < cap) cand[(size_t)q * cap + slot] = ((unsigned)c << 8) | 128u;  // whole-chunk entry
-                }
+                const unsigned e = lcand[i];   // (query << 27) | (rank << 16) | chunk
+                const int qq = staged_query(e), c = (int)(e & 0xFFFFu);
+                settle_candidate(L, (int64_t)qt * 32 + qq, c, lhist[c] + ((e >> 16) & 31u), &lov[qq]);
             }
         } else
         for (int i = threadIdx.x; i < ncand; i += 64 * SELECT_BEST_WAVES) {
             const unsigned e = lcand[i];
-            place((int)(e >> 27), (int)(e & 0x7FFFFFFu), crowded);
+            place(staged_query(e), staged_chunk(e), crowded);
         }
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float v = maxup[j];
-        v = fmaxf(v, __shfl_xor(v, 8));
-        v = fmaxf(v, __shfl_xor(v, 16));
-        v = fmaxf(v, __shfl_xor(v, 32));
-        if (lane < 8) atomicMax(&lub[lq + j], float_key(v));
-    }
+    raise_query_max<4>(lub, lq, maxup);
     __syncthreads();
-    if (threadIdx.x < 64) {   // one wave: the tile's 32 queries
-        const int qq = lane & 31;
-        const int64_t q = (int64_t)qt * 32 + qq;
-        const bool live = lane < 32 && q < n;
-        const int cnt = lcnt[qq];
-        // load figure of the int8 pass (vfm_match_search_rescans_async): candidate chunks match_rescan_kernel will rescan
-        int mine = 0;
-        if (live && invq[q] != 0.0f && !(key_float(lub[qq]) < gate) && cnt <= cap) mine = cnt;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
-        if (lane == 0 && mine > 0) atomicAdd(fb_count + 5, mine);
-        if (live) {
-            if (stats && invq[q] != 0.0f) {
-                atomicAdd(fb_count + 2, cnt);
-                int bin = 0;
-                while ((1 << bin) < cnt && bin < 15) ++bin;
-                atomicAdd(fb_count + 8 + bin, 1);
-            }
-            const bool dead = ldead[qq] != 0;
-            if (invq[q] == 0.0f) {
-                cand_cnt[q] = 0;  // zero query row: decided directly (index 0, score 0)
-            } else if (key_float(lub[qq]) < gate) {
-                cand_cnt[q] = -2;  // no row of the map can reach the caller's similarity gate
-            } else if (cnt > cap || dead) {
-                // overflow, or a padded chunk lifted a query past the gate whose candidates were not recorded: decided by the
-                // exact all-pairs kernel
-                cand_cnt[q] = -1;
-                const int slot = atomicAdd(fb_count, 1);
-                fb_list[slot] = (int)q;
-            } else {
-                // chunk-major rescan: the list holds only the entries that missed their bins; match_rescan_chunk_kernel
-                // appends the rows it finds behind what match_rescan_kernel makes of these
-                cand_cnt[q] = lov[qq];
-            }
-        }
-    }
+    close_tile_queries(
+        SelectClose{invq, cand_cnt, fb_count, fb_list, stats}, qt, n, lcnt, true,
+        [&](int qq, int64_t q, int cnt) { return bounded_query_load(invq[q], key_float(lub[qq]) < gate, cnt, cnt, cap); },
+        [&](int qq, int) { return key_float(lub[qq]) < gate; },
+        // overflow, or a padded chunk lifted a query past the gate whose candidates were not recorded
+        [&](int qq, int cnt) { return cnt > cap || ldead[qq] != 0; }, [&](int qq, int) { return lov[qq]; });
 }
 
 // int8 pass, chunk-major rescan (best-score records, many queries per chunk): one workgroup per map chunk scores the chunk's
@@ -974,8 +725,8 @@ int launch_rescan_chunk(const SearchWs& w, int nchunks, int64_t n, int64_t m, in
 // wave (match_coarse_mx6.hip's, same operand order, same accumulation: the scores are the coarse kernel's) give x = the fp6 score of
 // 32 rows x 32 queries over the first d / 2 columns.
 //
-// Hit test per (query q, row r) -- emit_chunk's expression (the bound of match_select_half_kernel with mx6_bounds_half) with the ROW's
-// residual norm and rest norm in place of the chunk's maxima:
+// Hit test per (query q, row r) -- emit_chunk's expression (the bound of match_select_half_kernel -- match_select.h:
+// chunk_upper_half -- with mx6_bounds_half) with the ROW's residual norm and rest norm in place of the chunk's maxima:
 //     exact score of (q, r)  <=  x + A_q + (1 + 2^-13 + E_q) E_r + rest_q rest_r  (+ 2e-6 for the fp32 evaluation),
 // E = err6h, the image's residual over the columns the pass multiplies (MX6_SLACK, which pays for the MFMA's fp32 accumulation, is in
 // every E), rest = |second half of the normalised row|, rounded up (Cauchy-Schwarz on the columns the pass does not multiply).  A row is

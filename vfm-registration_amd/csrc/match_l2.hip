@@ -5,6 +5,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "match_exact.h"
+#include "match_select.h"
 
 namespace vfmm {
 namespace {
@@ -267,6 +268,9 @@ __global__ void l2i8_to_int_kernel(const int64_t* __restrict__ src, int* __restr
     if (i < n) dst[i] = src[i] < 0 ? 0 : (int)src[i];
 }
 
+// The selection of the int8 Euclidean search, from the tile kernels' pieces (match_select.h): the sweep frame twice, the bounds of
+// the cosine, the staged candidates, the placement, and the overflow class of the epilogue.  Its own: the (step, max E, lo, hi)
+// staging and the two Euclidean bounds.
 constexpr int SELECT_L2_WAVES = 8;
 constexpr int SELECT_L2_LCAND = 4096;
 __global__ __launch_bounds__(64 * SELECT_L2_WAVES) void match_select_l2_kernel(
@@ -279,7 +283,6 @@ __global__ __launch_bounds__(64 * SELECT_L2_WAVES) void match_select_l2_kernel(
     __shared__ unsigned llow[32];   // float_key of the query's lower bound of its best Euclidean score
     __shared__ unsigned lcand[SELECT_L2_LCAND];   // the tile's candidates: (query of the tile << 27) | chunk
     __shared__ int lcand_n;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int qt = blockIdx.x;
     if (threadIdx.x < 32) {
         lcnt[threadIdx.x] = 0;
@@ -294,112 +297,73 @@ __global__ __launch_bounds__(64 * SELECT_L2_WAVES) void match_select_l2_kernel(
             lchunk[c] = make_float4(ib.bstep[c], ib.berr[c], nh.x, nh.y);
         }
     __syncthreads();
-    const int lq = (lane & 7) * 4, lc = lane >> 3;
+    const int lq = TileLane<4>().lq;
     const int64_t q0 = (int64_t)qt * 32 + lq;   // the lane's four queries (rows of the padded tile always exist)
     const float sq = ib.qstep[q0 >> 7];
-    float A[4], mult[4], nq[4];
+    QueryBound qb[4];   // (the slack of the cosine's bounds folded into A)
+    float nq[4];
     unsigned livemask = 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float eq = ib.qerr[q0 + j];
-        A[j] = eq * 1.0001220703125f + 1.0e-6f;
-        mult[j] = 1.0001220703125f + eq;
+        qb[j] = query_bound_slack(ib.qerr[q0 + j]);
         nq[j] = qn[q0 + j];
         if (q0 + j < n) livemask |= 1u << j;
     }
-    const uint4* src = reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32) + lane;
-    const int nblocks = (nchunks + 7) >> 3;
+    const uint4* tile = reinterpret_cast<const uint4*>(best + (size_t)qt * nchunks * 32);
     auto chunk_data = [&](int c) { return chunk_lds ? lchunk[c] : make_float4(ib.bstep[c], ib.berr[c], cn[c].x, cn[c].y); };
     // sweep 1: qlow = the largest lower bound over the chunks
     float low[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (int cb0 = wave; cb0 < nblocks; cb0 += 8 * SELECT_L2_WAVES) {
-        uint4 rec[8];
+    sweep_tile_records<4, SELECT_L2_WAVES>(tile, nchunks, [&](int c, uint4 rec) {
+        const float4 cd = chunk_data(c);
+        const float sc = sq * cd.x;
+        const unsigned r4[4] = {rec.x, rec.y, rec.z, rec.w};
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int cb = cb0 + SELECT_L2_WAVES * u;
-            rec[u] = (cb * 8 + lc < nchunks) ? src[(size_t)cb * 64] : make_uint4(0u, 0u, 0u, 0u);
+        for (int j = 0; j < 4; ++j) {
+            const int S = best_score(r4[j]);
+            // (a chunk with zero-padded rows -- they score exactly 0 -- counts only where its best score is positive)
+            if (c >= first_pad_chunk && S <= 0) continue;
+            const float cosL = cos_lower(sc, S, qb[j], cd.y);
+            const float g_lo = __builtin_fmaf(nq[j] * cd.z, cosL, -0.5f * cd.z * cd.z);
+            const float g_hi = __builtin_fmaf(nq[j] * cd.w, cosL, -0.5f * cd.w * cd.w);
+            low[j] = fmaxf(low[j], fminf(g_lo, g_hi) - slack);
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = (cb0 + SELECT_L2_WAVES * u) * 8 + lc;
-            if (c >= nchunks) continue;
-            const float4 cd = chunk_data(c);
-            const float sc = sq * cd.x;
-            const unsigned r4[4] = {rec[u].x, rec[u].y, rec[u].z, rec[u].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int S = (int)r4[j] - I8_OFFSET;
-                // (a chunk with zero-padded rows -- they score exactly 0 -- counts only where its best score is positive)
-                if (c >= first_pad_chunk && S <= 0) continue;
-                const float cosL = sc * (float)S - (A[j] + mult[j] * cd.y);
-                const float g_lo = __builtin_fmaf(nq[j] * cd.z, cosL, -0.5f * cd.z * cd.z);
-                const float g_hi = __builtin_fmaf(nq[j] * cd.w, cosL, -0.5f * cd.w * cd.w);
-                low[j] = fmaxf(low[j], fminf(g_lo, g_hi) - slack);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float v = low[j];
-        v = fmaxf(v, __shfl_xor(v, 8));
-        v = fmaxf(v, __shfl_xor(v, 16));
-        v = fmaxf(v, __shfl_xor(v, 32));
-        if (lane < 8) atomicMax(&llow[lq + j], float_key(v));
-    }
+        return false;
+    });
+    raise_query_max<4>(llow, lq, low);
     __syncthreads();
     float qlow[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) qlow[j] = key_float(llow[lq + j]);   // -Inf: no chunk qualified -> every chunk is a candidate
-    // sweep 2 (the records come out of the L2 this time): the chunks whose upper bound reaches qlow.  A candidate costs one LDS
-    // atomic here; the global side (the chunk's bin, or the query's own list) is done afterwards for all of them at once -- a
+    // sweep 2 (the records come out of the L2 this time): the chunks whose upper bound reaches qlow, staged (stage_candidate) -- a
     // returning global atomic per candidate inside the sweep stalled the wave each time: 0.75 ms at C2's 250 000 candidates
-    for (int cb0 = wave; cb0 < nblocks; cb0 += 8 * SELECT_L2_WAVES) {
-        uint4 rec[8];
+    sweep_tile_records<4, SELECT_L2_WAVES>(tile, nchunks, [&](int c, uint4 rec) {
+        const float4 cd = chunk_data(c);
+        const float sc = sq * cd.x;
+        const unsigned r4[4] = {rec.x, rec.y, rec.z, rec.w};
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int cb = cb0 + SELECT_L2_WAVES * u;
-            rec[u] = (cb * 8 + lc < nchunks) ? src[(size_t)cb * 64] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int c = (cb0 + SELECT_L2_WAVES * u) * 8 + lc;
-            if (c >= nchunks) continue;
-            const float4 cd = chunk_data(c);
-            const float sc = sq * cd.x;
-            const unsigned r4[4] = {rec[u].x, rec[u].y, rec[u].z, rec[u].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float cosU = fmaxf(sc * (float)((int)r4[j] - I8_OFFSET) + (A[j] + mult[j] * cd.y), 0.0f);
-                const float nb = fminf(fmaxf(nq[j] * cosU, cd.z), cd.w);   // where qn nb cosU - nb^2 / 2 peaks inside [lo, hi]
-                const float up = __builtin_fmaf(nq[j] * nb, cosU, -0.5f * nb * nb) + slack;
-                if (up >= qlow[j] && ((livemask >> j) & 1u)) {
-                    atomicAdd(&lcnt[lq + j], 1);
-                    const int at = atomicAdd(&lcand_n, 1);
-                    if (at < SELECT_L2_LCAND) lcand[at] = ((unsigned)(lq + j) << 27) | (unsigned)c;
-                }
+        for (int j = 0; j < 4; ++j) {
+            const float cosU = fmaxf(cos_upper(sc, best_score(r4[j]), qb[j], cd.y), 0.0f);
+            const float nb = fminf(fmaxf(nq[j] * cosU, cd.z), cd.w);   // where qn nb cosU - nb^2 / 2 peaks inside [lo, hi]
+            const float up = __builtin_fmaf(nq[j] * nb, cosU, -0.5f * nb * nb) + slack;
+            if (up >= qlow[j] && ((livemask >> j) & 1u)) {
+                atomicAdd(&lcnt[lq + j], 1);
+                stage_candidate(lcand, &lcand_n, SELECT_L2_LCAND, lq + j, c);   // (a full buffer: the whole tile goes to the all-pairs kernel)
             }
         }
-    }
+        return false;
+    });
     __syncthreads();
     const int ncand = lcand_n;
     if (ncand <= SELECT_L2_LCAND) {
+        const SelectLists L{bin_cnt, bins, bin_cap, cand, cap};
         for (int i = threadIdx.x; i < ncand; i += 64 * SELECT_L2_WAVES) {
             const unsigned e = lcand[i];
-            const int qq = (int)(e >> 27), c = (int)(e & 0x7FFFFFFu);
-            const int64_t q = (int64_t)qt * 32 + qq;
-            int slot = -1;
-            if (bins) {  // chunk-major rescan: the query joins the chunk's bin; a full bin leaves the entry with the query
-                const unsigned seen = __hip_atomic_load(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned pos = seen >= (unsigned)bin_cap ? seen : atomicAdd(&bin_cnt[(size_t)c * BIN_CNT_STRIDE], 1u);
-                if (pos < (unsigned)bin_cap) bins[(size_t)c * bin_cap + pos] = (int)q;
-                else slot = atomicAdd(&lov[qq], 1);
-            } else {
-                slot = atomicAdd(&lov[qq], 1);
-            }
-            if (slot >= 0 && slot < cap) cand[(size_t)q * cap + slot] = ((unsigned)c << 8) | 128u;  // whole-chunk entry
+            const int qq = staged_query(e);
+            place_candidate(L, (int64_t)qt * 32 + qq, staged_chunk(e), true, &lov[qq]);
         }
     }
     __syncthreads();
+    // No gate and no zero-row rule here: the epilogue shares the overflow class only (send_to_all_pairs).
     if (threadIdx.x < 32) {
         const int qq = threadIdx.x;
         const int64_t q = (int64_t)qt * 32 + qq;
@@ -409,12 +373,8 @@ __global__ __launch_bounds__(64 * SELECT_L2_WAVES) void match_select_l2_kernel(
             if (cnt > cap || ncand > SELECT_L2_LCAND) {
                 // more candidate chunks than a list (or the tile's staging buffer) holds: the all-pairs kernel decides.  (The
                 // staging buffer overflows only when the tile's 32 queries average more than 128 candidate chunks each.)
-                if (cnt > 0 || ncand > SELECT_L2_LCAND) {
-                    cand_cnt[q] = -1;
-                    fb_list[atomicAdd(fb_count, 1)] = (int)q;
-                } else {
-                    cand_cnt[q] = 0;
-                }
+                if (cnt > 0 || ncand > SELECT_L2_LCAND) send_to_all_pairs(q, cand_cnt, fb_count, fb_list);
+                else cand_cnt[q] = 0;
             } else {
                 cand_cnt[q] = lov[qq];   // entries in the query's own list (everything, without bins)
             }
