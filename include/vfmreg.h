@@ -633,6 +633,27 @@ int vfm_icp_grid_update(const int64_t *keys, const int32_t *start, const double 
                         double max_distance, int64_t *keys_out, int32_t *start_out, double *pts_out, int32_t *info_out, void *ws,
                         size_t ws_bytes, vfm_stream_t stream);
 
+/* vfm_icp_grid_update with the provenance of its output points, for a map that keeps a payload per point (VoxelHashMap::Update of the
+ * 387-column map, VoxelHashMap.cpp:701-715, 746-757, 781-787: the descriptor rows move with their points).  src_out (int32, sized for
+ * nk + m entries): src_out[q] = t if output point q is old point t, nk + s if it is new input point s (s: the index into xyz_new);
+ * written are src_out[0, n_kept).  Keys, starts, points and info_out are bit for bit those of vfm_icp_grid_update on the same input --
+ * the same kernels run --, and so are the argument rules, the workspace (vfm_icp_grid_update_workspace_bytes) and the promise about
+ * writes.  One enqueue, no host synchronisation. */
+int vfm_icp_grid_update_src(const int64_t *keys, const int32_t *start, const double *pts, int32_t nv, int64_t nk, const double *xyz_new,
+                            int64_t m, const double *T_host, double voxel_size, int32_t max_points_per_voxel, const double *origin_host,
+                            double max_distance, int64_t *keys_out, int32_t *start_out, double *pts_out, int32_t *info_out,
+                            int32_t *src_out, void *ws, size_t ws_bytes, vfm_stream_t stream);
+
+/* The payload's move: rows_out[q] = (src[q] < nk ? rows_old[src[q]] : rows_new[src[q] - nk]) for q < min(*n_out_dev, n_max), rows of
+ * row_bytes bytes (a positive multiple of 4) -- width- and type-blind: fp32 or fp64 descriptor rows, norms, flags.  n_out_dev is in
+ * DEVICE memory (info_out + 1 of the update: the two calls are two enqueues with no read-back between them); n_max bounds it (the
+ * rows rows_out and src hold).  A row moves with 16-byte accesses when row_bytes % 16 == 0 and rows_old, rows_new and rows_out are
+ * 16-byte aligned, else dword by dword: the same bytes out.  A wave moves whole rows.  An src entry outside [0, nk + m) writes nothing
+ * for its row and sets no error (a caller's bug).  Nothing behind min(*n_out_dev, n_max) * row_bytes is written; rows_out aliases no
+ * input.  nk + m <= 2^30, n_max <= 2^30; n_max == 0 is valid (nothing is launched). */
+int vfm_rows_merge(const void *rows_old, int64_t nk, const void *rows_new, int64_t m, int64_t row_bytes, const int32_t *src,
+                   const int32_t *n_out_dev, int64_t n_max, void *rows_out, vfm_stream_t stream);
+
 /* ------------------------------------------------------------------ FPFH descriptors (Open3D 0.18 baseline) */
 
 /* The CPU work of extract_fpfh_features (src/vfm-reg/src/vfm_reg/descriptors.py:19-44), which the reference runs in Open3D 0.18.

@@ -8,6 +8,10 @@
 //   vfm_icp_grid_update   VoxelHashMap::Update for the 3-D map (VoxelHashMap.cpp:693-699, 733-744, 772-779) on the sorted-key CSR that
 //                         vfm_icp_nearest reads: the new points' keys are sorted (m of them, not the map), their runs are merged into the
 //                         old key list by two rank searches, far voxels are dropped, and one scatter writes the new grid.
+//   vfm_icp_grid_update_src  the same update (the same kernels: the scatter takes a nullable pointer) that also says where every output
+//                         point came from -- the provenance a map needs to move a payload (descriptor rows) along with its points
+//   vfm_rows_merge        that move: rows_out[q] = row src[q] of (rows_old | rows_new), rows of any width that is a multiple of 4 bytes,
+//                         a wave per row (several short rows per wave), 16-byte accesses where width and pointers allow; a pure copy
 //
 // HBM-bound fp64, -ffp-contract=off, every expression spelled in the order the oracle (tests/odometry_oracle.py) replays.  No
 // floating-point atomic; the integer atomics (the status flag, the count of accepted points) do not depend on an order.
@@ -235,7 +239,7 @@ __device__ __forceinline__ int upd_voxel_of(const int* __restrict__ start, int n
 }
 
 // The one scatter.  vpos / ppos: inclusive sums of alive / size over nv + m entries.  Thread t serves merged voxel t (its key and start),
-// old point t and sorted new point t.
+// old point t and sorted new point t.  src_out (nullable): where output point q came from -- old point t, or nk + s for new input point s.
 __global__ __launch_bounds__(256) void upd_scatter_kernel(const long long* __restrict__ keys, const int* __restrict__ start,
                                                           const double* __restrict__ pts, int nv, int64_t nk, int64_t m, int64_t total,
                                                           const int* __restrict__ mv_old, const int* __restrict__ mv_run,
@@ -247,7 +251,8 @@ __global__ __launch_bounds__(256) void upd_scatter_kernel(const long long* __res
                                                           const int* __restrict__ alive, const int* __restrict__ vpos,
                                                           const int* __restrict__ ppos, const int* __restrict__ cnt,
                                                           long long* __restrict__ keys_out, int* __restrict__ start_out,
-                                                          double* __restrict__ pts_out, int* __restrict__ info_out) {
+                                                          double* __restrict__ pts_out, int* __restrict__ info_out,
+                                                          int* __restrict__ src_out) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t < total && alive[t]) {
         const int j = mv_old[t];
@@ -262,6 +267,7 @@ __global__ __launch_bounds__(256) void upd_scatter_kernel(const long long* __res
             pts_out[3 * q] = pts[3 * t];
             pts_out[3 * q + 1] = pts[3 * t + 1];
             pts_out[3 * q + 2] = pts[3 * t + 2];
+            if (src_out) src_out[q] = (int)t;
         }
     }
     if (t < m) {
@@ -274,6 +280,7 @@ __global__ __launch_bounds__(256) void upd_scatter_kernel(const long long* __res
             pts_out[3 * q] = moved[3 * s];
             pts_out[3 * q + 1] = moved[3 * s + 1];
             pts_out[3 * q + 2] = moved[3 * s + 2];
+            if (src_out) src_out[q] = (int)(nk + s);   // (s: the index into xyz_new, not the sorted position)
         }
     }
     if (t == 0) {
@@ -359,6 +366,46 @@ bool update_sizes_ok(int64_t nv, int64_t nk, int64_t m) {
     return nv >= 0 && nk >= 0 && m >= 0 && nv <= nk && nk <= ICP_GRID_MAX_POINTS && m <= ICP_GRID_MAX_POINTS && nk + m <= ICP_GRID_MAX_POINTS;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ rows merge
+// A pure copy, HBM-bound: a row is U units of V (uint4 = 16 bytes, or a dword), lane l of a wave moves units l, l + 64, ... of its row, so
+// a wave's access is one contiguous stretch.  Rows shorter than 64 units share a wave: 64 / U of them, U lanes each (the lanes behind the
+// last whole row idle).  Up to ROWS_MERGE_BATCH loads of a lane are issued before its first store (a second row in flight per lane
+// showed no gain: DESIGN 7.7).  Waves stride over the rows; the row count is read from device memory, so the grid is sized for n_max and the waves beyond *n_out_dev leave at once.
+enum { ROWS_MERGE_THREADS = 256, ROWS_MERGE_BATCH = 4 };
+
+template <typename V>
+__global__ __launch_bounds__(ROWS_MERGE_THREADS) void rows_merge_kernel(const V* __restrict__ rows_old, int64_t nk, const V* __restrict__ rows_new,
+                                                                        int64_t m, int64_t U, const int* __restrict__ src,
+                                                                        const int* __restrict__ n_out_dev, int64_t n_max, V* __restrict__ rows_out) {
+    int64_t n = *n_out_dev;
+    n = n < n_max ? n : n_max;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * ROWS_MERGE_THREADS + threadIdx.x) >> 6;
+    const int64_t waves = ((int64_t)gridDim.x * ROWS_MERGE_THREADS) >> 6;
+    const int per_wave = U < 64 ? (int)(64 / U) : 1;            // rows of one wave's pass
+    const int sub = U < 64 ? lane / (int)U : 0;                  // this lane's row of the pass
+    const int64_t u0 = U < 64 ? lane % (int)U : lane;            // ... and its first unit
+    const int64_t step = U < 64 ? U : 64;                        // (a short row: one unit per lane, the loop below runs once)
+    if (sub >= per_wave) return;
+    for (int64_t q = wave * per_wave + sub; q < n; q += waves * per_wave) {
+        const int64_t s = src[q];
+        if (s < 0 || s >= nk + m) continue;                      // (a caller's error; nothing is written for the row)
+        const V* __restrict__ from = s < nk ? rows_old + s * U : rows_new + (s - nk) * U;
+        V* __restrict__ to = rows_out + q * U;
+        for (int64_t u = u0; u < U; u += ROWS_MERGE_BATCH * step) {
+            V v[ROWS_MERGE_BATCH];
+#pragma unroll
+            for (int k = 0; k < ROWS_MERGE_BATCH; ++k)
+                if (u + k * step < U) v[k] = from[u + k * step];
+#pragma unroll
+            for (int k = 0; k < ROWS_MERGE_BATCH; ++k)
+                if (u + k * step < U) to[u + k * step] = v[k];
+        }
+    }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 VFM_EXPORT int vfm_range_crop(const double* pts, int64_t n, int64_t stride, double min_range, double max_range, int64_t* idx_out,
@@ -396,10 +443,11 @@ VFM_EXPORT size_t vfm_icp_grid_update_workspace_bytes(int32_t nv, int64_t nk, in
     return used;
 }
 
-VFM_EXPORT int vfm_icp_grid_update(const int64_t* keys, const int32_t* start, const double* pts, int32_t nv, int64_t nk, const double* xyz_new,
-                                   int64_t m, const double* T_host, double voxel_size, int32_t max_points_per_voxel, const double* origin_host,
-                                   double max_distance, int64_t* keys_out, int32_t* start_out, double* pts_out, int32_t* info_out, void* ws,
-                                   size_t ws_bytes, vfm_stream_t stream) {
+// the body of both update entries; src_out: NULL for vfm_icp_grid_update
+static int grid_update(const int64_t* keys, const int32_t* start, const double* pts, int32_t nv, int64_t nk, const double* xyz_new, int64_t m,
+                       const double* T_host, double voxel_size, int32_t max_points_per_voxel, const double* origin_host, double max_distance,
+                       int64_t* keys_out, int32_t* start_out, double* pts_out, int32_t* info_out, int32_t* src_out, void* ws, size_t ws_bytes,
+                       vfm_stream_t stream) {
     VFM_CHECK_ARG(update_sizes_ok(nv, nk, m), "icp_grid_update: bad sizes (0 <= nv <= nk, nk + m <= 2^30)");
     VFM_CHECK_ARG((nv == 0) == (nk == 0), "icp_grid_update: a grid without voxels holds no points, and one with voxels holds some");
     VFM_CHECK_ARG(voxel_size > 0.0 && max_points_per_voxel >= 0, "icp_grid_update: bad voxel_size / max_points_per_voxel");
@@ -462,7 +510,52 @@ VFM_EXPORT int vfm_icp_grid_update(const int64_t* keys, const int32_t* start, co
     const int64_t widest = nk > total ? nk : total;
     hipLaunchKernelGGL(upd_scatter_kernel, dim3(grid3::blocks256(widest)), block, 0, st, okeys, start, pts, (int)nv, nk, m, total, w.mv_old, w.mv_run,
                        w.old_mv, w.run_mv, w.run_key, w.run_pos, w.run_old_count, w.run_take, w.rid, w.order, moved, w.size, w.alive, w.vpos,
-                       w.ppos, w.cnt, reinterpret_cast<long long*>(keys_out), start_out, pts_out, info_out);
+                       w.ppos, w.cnt, reinterpret_cast<long long*>(keys_out), start_out, pts_out, info_out, src_out);
     VFM_CHECK_LAUNCH("upd_scatter_kernel");
+    return VFM_OK;
+}
+
+VFM_EXPORT int vfm_icp_grid_update(const int64_t* keys, const int32_t* start, const double* pts, int32_t nv, int64_t nk, const double* xyz_new,
+                                   int64_t m, const double* T_host, double voxel_size, int32_t max_points_per_voxel, const double* origin_host,
+                                   double max_distance, int64_t* keys_out, int32_t* start_out, double* pts_out, int32_t* info_out, void* ws,
+                                   size_t ws_bytes, vfm_stream_t stream) {
+    return grid_update(keys, start, pts, nv, nk, xyz_new, m, T_host, voxel_size, max_points_per_voxel, origin_host, max_distance, keys_out,
+                       start_out, pts_out, info_out, nullptr, ws, ws_bytes, stream);
+}
+
+VFM_EXPORT int vfm_icp_grid_update_src(const int64_t* keys, const int32_t* start, const double* pts, int32_t nv, int64_t nk,
+                                       const double* xyz_new, int64_t m, const double* T_host, double voxel_size, int32_t max_points_per_voxel,
+                                       const double* origin_host, double max_distance, int64_t* keys_out, int32_t* start_out, double* pts_out,
+                                       int32_t* info_out, int32_t* src_out, void* ws, size_t ws_bytes, vfm_stream_t stream) {
+    VFM_CHECK_ARG(src_out || (int64_t)nv + m <= 0, "icp_grid_update_src: null pointer (src_out)");
+    return grid_update(keys, start, pts, nv, nk, xyz_new, m, T_host, voxel_size, max_points_per_voxel, origin_host, max_distance, keys_out,
+                       start_out, pts_out, info_out, src_out, ws, ws_bytes, stream);
+}
+
+VFM_EXPORT int vfm_rows_merge(const void* rows_old, int64_t nk, const void* rows_new, int64_t m, int64_t row_bytes, const int32_t* src,
+                              const int32_t* n_out_dev, int64_t n_max, void* rows_out, vfm_stream_t stream) {
+    VFM_CHECK_ARG(nk >= 0 && m >= 0 && nk + m <= ICP_GRID_MAX_POINTS && n_max >= 0 && n_max <= ICP_GRID_MAX_POINTS,
+                  "rows_merge: bad sizes (0 <= nk, m, n_max; nk + m and n_max <= 2^30)");
+    VFM_CHECK_ARG(row_bytes > 0 && row_bytes % 4 == 0 && row_bytes <= (int64_t)1 << 30, "rows_merge: row_bytes must be a positive multiple of 4");
+    if (n_max == 0) return VFM_OK;
+    VFM_CHECK_ARG(src && n_out_dev && rows_out, "rows_merge: null pointer");
+    VFM_CHECK_ARG((nk == 0 || rows_old) && (m == 0 || rows_new), "rows_merge: null pointer (rows)");
+    VFM_CHECK_ARG(rows_out != rows_old && rows_out != rows_new, "rows_merge: the output must not alias an input");
+    const bool wide = row_bytes % 16 == 0 && aligned16(rows_old) && aligned16(rows_new) && aligned16(rows_out);
+    const int64_t U = row_bytes / (wide ? 16 : 4);
+    const int64_t per_wave = U < 64 ? 64 / U : 1;
+    const int64_t waves = (n_max + per_wave - 1) / per_wave;
+    const int waves_per_block = ROWS_MERGE_THREADS / 64;
+    int64_t blocks = (waves + waves_per_block - 1) / waves_per_block;
+    const int64_t resident = 256 * 8;   // 256 CUs x 8 workgroups of 4 waves: every SIMD full; the waves stride over the rest
+    if (blocks > resident) blocks = resident;
+    hipStream_t st = (hipStream_t)stream;
+    if (wide)
+        hipLaunchKernelGGL(rows_merge_kernel<uint4>, dim3((unsigned)blocks), dim3(ROWS_MERGE_THREADS), 0, st, (const uint4*)rows_old, nk,
+                           (const uint4*)rows_new, m, U, src, n_out_dev, n_max, (uint4*)rows_out);
+    else
+        hipLaunchKernelGGL(rows_merge_kernel<uint32_t>, dim3((unsigned)blocks), dim3(ROWS_MERGE_THREADS), 0, st, (const uint32_t*)rows_old, nk,
+                           (const uint32_t*)rows_new, m, U, src, n_out_dev, n_max, (uint32_t*)rows_out);
+    VFM_CHECK_LAUNCH("rows_merge_kernel");
     return VFM_OK;
 }

@@ -106,6 +106,9 @@ SIGNATURES = {
     "vfm_icp_grid_update_workspace_bytes": (C.c_size_t, [C.c_int32, c_i64, c_i64]),
     "vfm_icp_grid_update": (C.c_int, [c_vp, c_vp, c_vp, C.c_int32, c_i64, c_vp, c_i64, c_vp, C.c_double, C.c_int32, c_vp, C.c_double,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_icp_grid_update_src": (C.c_int, [c_vp, c_vp, c_vp, C.c_int32, c_i64, c_vp, c_i64, c_vp, C.c_double, C.c_int32, c_vp, C.c_double,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_rows_merge": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "vfm_fpfh_workspace_bytes": (C.c_size_t, [c_i64]),
     "vfm_fpfh_grid_build": (C.c_int, [c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_fpfh_search_hybrid": (C.c_int, [c_vp, c_i64, c_vp, c_vp, C.c_double, C.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -277,10 +277,19 @@ def _solve6(JTJ: np.ndarray, rhs: np.ndarray):
 
 def _register_frame_nd(points: np.ndarray, voxel_map, initial_guess: np.ndarray, max_correspondance_distance: float, kernel: float):
     """Registration.cpp:197-382 (see the module docstring); returns (pose, src_, tgt_)."""
-    from .voxelization import down_sample_device, to_device_rows
+    from .voxelization import to_device_rows
+    rows, xyz = to_device_rows(points)
+    return _register_frame_nd_device(rows, xyz, voxel_map, initial_guess, max_correspondance_distance, kernel)
+
+
+def _register_frame_nd_device(rows: torch.Tensor, xyz: torch.Tensor, voxel_map, initial_guess: np.ndarray, max_correspondance_distance: float,
+                              kernel: float):
+    """``_register_frame_nd`` on a scan that is on the device already: ``rows`` [n, 387] (fp32 / fp64; only the descriptor columns are read)
+    and their coordinates ``xyz`` fp64 [n, 3] (the odometry loop's entry: its frame was uploaded once)."""
+    from .voxelization import down_sample_device
     lib = _lib.load()
     st = ops._stream()
-    rows, xyz = to_device_rows(points)
+    initial_guess = np.ascontiguousarray(initial_guess, dtype=np.float64)
     T0 = torch.from_numpy(initial_guess).cuda()
     source_3d = ops.transform_xyz(xyz, T0)                                      # :207-208 (descriptors carried through)
     _, sub_xyz, order = down_sample_device(rows, source_3d, 5.0)               # :216
@@ -444,7 +453,7 @@ def register_frame(points: np.ndarray, voxel_map, initial_guess: np.ndarray, max
         # when the caller passed src_ / tgt_; every other width > 3 takes RegisterFrame(VectorXd ...) (Registration.cpp:384-423, round 6):
         # the 3-D loop with the descriptor-weighted nearest neighbour as its search, against the map's rows of the same width (the
         # reference keeps those in map_x_; here the wide rows of a map live in one container whatever their width)
-        ncols = None if voxel_map.empty_n() else voxel_map._cloud("n")[0].shape[1]
+        ncols = voxel_map.width_n()
         if ncols is not None and points.shape[1] != ncols:
             raise ValueError("Invalid shape")   # (rows of a width the map does not hold: the reference's map_x_ would be empty or of another width)
         if points.shape[1] != POINT_SIZE:

@@ -9,8 +9,13 @@ voxel levels at 0.5 and 1.5 x the map's voxel size (``vfm_voxel_robin_level``, c
 ``original_frame_downsample``.
 
 The reference's class has its de-skew line commented out; here it runs when ``config.data.deskew`` is true (default false: the
-reference's behaviour), as the C++ pipeline (KissICP.cpp:69-103) and upstream do.  ``use_descriptors=True`` (a local map that carries
-descriptors) is not built."""
+reference's behaviour), as the C++ pipeline (KissICP.cpp:69-103) and upstream do.
+
+``use_descriptors=True`` (kiss_icp.py:47-113, the paper's VFM-seeded odometry) takes frames of 387 columns: ``source`` and
+``frame_downsample`` keep their 384 descriptor columns, the pose comes from the descriptor-seeded RegisterFrame
+(``icp._register_frame_nd_device``) against a local map that carries descriptors, and ``VoxelHashMap.update`` moves the map's descriptor
+rows along with its points (``vfm_icp_grid_update_src`` + ``vfm_rows_merge``).  The map's search operand is prepared again for the whole
+map every frame.  Frames of another width would need the reference's ``VectorXd`` local map, which is not built."""
 from __future__ import annotations
 
 import time
@@ -85,7 +90,7 @@ class KissICP:
     # ------------------------------------------------------------------ kiss_icp.py:47-113
     def register_frame(self, frame, timestamps, use_descriptors=False):
         if use_descriptors:
-            raise NotImplementedError("use_descriptors=True: a local map that carries descriptors is not built")
+            return self._register_frame_desc(frame, timestamps)
         frame = np.asarray(frame)
         if frame.ndim != 2 or frame.shape[1] < 3:
             raise ValueError("Invalid shape")
@@ -137,6 +142,66 @@ class KissICP:
 
         self.adaptive_threshold.update_model_deviation(np.linalg.inv(initial_guess) @ new_pose)
         self.local_map.update(frame_downsample, new_pose)
+        self.poses.append(new_pose)
+        self._tick("update", t0)
+        return new_pose, original_frame_downsample, True
+
+    def _register_frame_desc(self, frame, timestamps):
+        """register_frame(use_descriptors=True): the stages of ``register_frame`` with the descriptor columns kept on ``source`` and
+        ``frame_downsample`` (kiss_icp.py:65-79), the descriptor-seeded RegisterFrame (Registration.cpp:197-382) and the 387-column map"""
+        frame = np.asarray(frame)
+        if frame.ndim != 2 or frame.shape[1] < 3:
+            raise ValueError("Invalid shape")
+        if frame.shape[1] != icp.POINT_SIZE:     # (before anything is uploaded)
+            raise NotImplementedError(f"use_descriptors=True: descriptor odometry takes frames of {icp.POINT_SIZE} columns (xyz + "
+                                      f"{icp.POINT_SIZE - 3} descriptor columns), got {frame.shape[1]}; the VectorXd local map of other "
+                                      "widths is not built")
+        t0 = time.perf_counter() if self.profile else 0.0
+        rows = torch.from_numpy(np.ascontiguousarray(frame)).cuda()                # the frame's one upload, in its own dtype
+        if rows.dtype not in (torch.float32, torch.float64):
+            rows = rows.double()
+        n = rows.shape[0]
+        xyz = rows[:, :3].double().contiguous()                                     # (fp32 -> fp64 is exact: what pybind's cast gives)
+        deskewed = self.config.data.deskew and len(self.poses) >= 2 and n > 0
+        if deskewed:
+            stamps = torch.from_numpy(np.ascontiguousarray(timestamps, dtype=np.float64)).cuda()
+            xyz = self.compensator.deskew_device(xyz, self.poses, stamps)
+        t0 = self._tick("upload_deskew", t0)
+        idx = count = None
+        if self.config.data.preprocess and n > 0:
+            idx, count = self.preprocess.crop_device(xyz)
+        t0 = self._tick("crop", t0)
+        if n > 0:
+            down_idx, source_idx = self._levels(xyz, idx, count)
+        else:
+            down_idx = source_idx = torch.zeros(0, dtype=torch.int64, device=rows.device)
+        down_rows = rows[down_idx]                                                  # frame_downsample, all columns
+        if deskewed:
+            down_rows = down_rows.double()
+            down_rows[:, :3] = xyz[down_idx]
+        source_rows, source_xyz = rows[source_idx], xyz[source_idx].contiguous()   # (the search reads the descriptor columns only)
+        t0 = self._tick("voxel_chain", t0)
+
+        sigma = self.get_adaptive_threshold()
+        prediction = self.get_prediction_model()
+        last_pose = self.poses[-1] if self.poses else np.eye(4)
+        initial_guess = last_pose @ prediction
+
+        if source_rows.shape[0] == 0 or self.local_map.empty_n():
+            new_pose = np.ascontiguousarray(initial_guess, dtype=np.float64)       # Registration.cpp:204
+        else:
+            new_pose, _, _ = icp._register_frame_nd_device(source_rows, source_xyz, self.local_map, initial_guess, 3 * sigma, sigma / 3)
+        t0 = self._tick("icp", t0)
+
+        original_frame_downsample = down_rows.double().cpu().numpy()
+        t0 = self._tick("download", t0)
+
+        motion = np.linalg.inv(last_pose) @ new_pose
+        if np.linalg.norm(motion[:3, -1]) < self.map_update_threshold and len(self.poses) > 1:
+            return new_pose, original_frame_downsample, False
+
+        self.adaptive_threshold.update_model_deviation(np.linalg.inv(initial_guess) @ new_pose)
+        self.local_map.update(down_rows, new_pose)
         self.poses.append(new_pose)
         self._tick("update", t0)
         return new_pose, original_frame_downsample, True

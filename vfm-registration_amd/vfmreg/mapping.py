@@ -13,8 +13,10 @@ runs on the GPU through the C ABI; besides the reference's (source, target) coor
 indices are available (``get_vfm_correspondence_indices``), which makes the KD-tree index recovery
 of registration_node.py:288-317 unnecessary.
 
-``update`` and ``remove_far_away_points`` (mapping.py:59-75, 89-90; 3-column points) turn the 3-D map into the odometry's local map:
-from then on it lives as the sorted-key grid ICP searches, updated in place on the device (csrc/odometry.hip ``vfm_icp_grid_update``).
+``update`` and ``remove_far_away_points`` (mapping.py:59-75, 89-90) turn a map into the odometry's local map: from then on it lives as
+the sorted-key grid ICP searches, updated in place on the device (csrc/odometry.hip ``vfm_icp_grid_update``).  The 387-column map keeps
+its descriptor rows next to that grid, in the grid's order, and every update moves them along with the points
+(``vfm_icp_grid_update_src`` + ``vfm_rows_merge``).
 """
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ class VoxelHashMap:
         self._load = None       # pinned int32[1]: load figure of the last gated search
         self._load_pending = None
         self._xyz = None        # cached xyz_map() (it carries the ICP grid register_frame builds from it)
+        self._wide_grid = None  # the sorted-key grid of the N-D map once ``update`` ran on it: _chunks["n"] is then [(descriptors [n, d], grid.pts)]
         self._drop_icp_grids()
 
     def _drop_icp_grids(self):
@@ -135,9 +138,21 @@ class VoxelHashMap:
         self._xyz = None
         self._drop_icp_grids()
 
+    def width_n(self) -> Optional[int]:
+        """columns of the N-D map's rows (None: it is empty)"""
+        if self.empty_n():
+            return None
+        rows = self._chunks["n"][0][0]
+        return rows.shape[1] + (3 if self._wide_grid is not None else 0)
+
     def add_points_device(self, rows: torch.Tensor, xyz64: torch.Tensor):
         """add_points on rows that are already on the device (rows [n, w] fp32 / fp64, xyz64 [n, 3] fp64)."""
         kind = self._kind(rows.shape[1])
+        if kind == "n" and self._wide_grid is not None and not self.empty_n():
+            # an updated N-D map stays a grid: plain AddPoints through the update (no pose, nothing removed)
+            if rows.shape[1] != self.width_n():
+                raise ValueError("Invalid shape")
+            return self._grid_update_n(rows[:, 3:].contiguous(), xyz64, None, None)
         # VoxelBlock::AddPoint keeps a point iff its voxel holds fewer than max_points_per_voxel points
         # (VoxelHashMap.hpp:55-62).  The points already stored come first and are all within the cap,
         # so "first K per voxel of [stored..., new...]" restricted to the new rows is exactly that rule.
@@ -165,43 +180,130 @@ class VoxelHashMap:
     # grid's, in (voxel key, insertion) order -- which is what point_cloud() then returns: the reference's set of points, not its
     # robin-map order after erasures.  Every far voxel goes, where the reference's erase-while-iterating keeps some until
     # the next call.  A map on which neither was called is untouched by any of this.
+    #
+    # The 387-column map (VoxelHashMap.cpp:701-715, 746-757, 781-787) follows the same rule with its descriptor rows as a payload: the grid
+    # (keys, start, fp64 points) is kept in ``_wide_grid``, the descriptor columns alone as one contiguous [n, 384] tensor in the rows' dtype
+    # and the grid's order -- (voxel key, insertion), the row numbering of the searches from then on (ties to the lower row).  The update
+    # says where every output point came from and vfm_rows_merge moves the rows: two enqueues, one 6-int read-back.  A map filled by
+    # add_points converts at its first update (its kept rows enter an empty grid in insertion order).  Other widths (the reference's map_x_)
+    # are not kept as a local map.
     def update(self, points, pose: np.ndarray = np.eye(4)):
-        """mapping.py:59-75 for 3-column points (numpy, or fp64 [n, 3] on the device)"""
+        """mapping.py:59-75 for 3-column points (numpy, or fp64 [n, 3] on the device) and for rows of icp.POINT_SIZE = 387 columns (numpy
+        or a device tensor, float32 or float64)"""
+        from .icp import POINT_SIZE
         if not isinstance(points, torch.Tensor):
             points = np.asarray(points)
         if points.ndim != 2 or points.shape[1] < 3:
             raise ValueError("Invalid shape")  # mapping.py:73
-        if points.shape[1] != 3:
+        if points.shape[1] not in (3, POINT_SIZE):
             raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {points.shape[1]} (only 3-column "
-                                      "points are kept in a device-resident local map)")
+                                      f"points and {POINT_SIZE}-column rows are kept in a device-resident local map)")
         pose = np.ascontiguousarray(pose, dtype=np.float64)
         if pose.shape != (4, 4):
             raise ValueError("expected a 4 x 4 pose")
+        if points.shape[1] == POINT_SIZE:
+            if isinstance(points, torch.Tensor):
+                if not points.is_cuda:
+                    raise RuntimeError("points: expected a tensor on the ROCm device (no CPU path exists)")
+                rows = points if points.dtype in (torch.float32, torch.float64) else points.double()
+                xyz = rows[:, :3].double().contiguous()
+            else:
+                rows, xyz = to_device_rows(points)
+            return self._grid_update_n(rows[:, 3:].contiguous(), xyz, pose, pose[:3, 3])
         xyz = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).cuda()
         return self._grid_update(xyz.contiguous(), pose, pose[:3, 3])
 
     def remove_far_away_points(self, origin):
-        """mapping.py:89-90: drop every voxel whose first point is farther than max_distance from ``origin``"""
+        """mapping.py:89-90: drop every voxel whose first point is farther than max_distance from ``origin`` -- of the 3-D map and of the
+        387-column one (VoxelHashMap.cpp:772-787)"""
         origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
         if origin.shape != (3,):
             raise ValueError("expected an origin of 3 values")
-        return self._grid_update(None, None, origin)
+        if self.empty_n() or self.width_n() - 3 != self._descriptor_width():     # (rows of another width are no local map: left alone)
+            return self._grid_update(None, None, origin)
+        first = None
+        if not self.empty():
+            self._grid_update(None, None, origin)
+            first = self.last_update
+        self._grid_update_n(None, None, None, origin)
+        if first is not None:
+            self.last_update = {k: v + first[k] for k, v in self.last_update.items()}
+
+    @staticmethod
+    def _descriptor_width() -> int:
+        from .icp import POINT_SIZE
+        return POINT_SIZE - 3
+
+    def _read_update_info(self, info):
+        from .icp import OUT_OF_RANGE_MESSAGE
+        info_h = getattr(ops._tls, "icp_update_info", None)   # page-locked: the update's one read-back
+        if info_h is None:
+            info_h = ops._tls.icp_update_info = torch.zeros(6, dtype=torch.int32).pin_memory()
+        info_h.copy_(info, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        vals = info_h.tolist()
+        if vals[2]:
+            raise ValueError(OUT_OF_RANGE_MESSAGE)   # (the map is left as it was)
+        return vals
+
+    def _install_wide(self, out):
+        """the N-D map := the grid and payload rows an update returned (its one read-back happens here)"""
+        from .icp import VoxelGridDevice
+        n_voxels, n_kept, _, added, voxels_removed, points_removed = self._read_update_info(out["info"])
+        grid = VoxelGridDevice.__new__(VoxelGridDevice)
+        grid.voxel_size = self.voxel_size
+        grid.n_voxels, grid.n_kept = n_voxels, n_kept
+        grid.keys, grid.start, grid.pts = out["keys"][:n_voxels], out["start"][:n_voxels + 1], out["pts"][:n_kept]
+        desc = out["rows"][:n_kept]
+        self._wide_grid = grid if n_kept else None
+        self._chunks["n"] = [(desc, grid.pts)] if n_kept else []
+        if n_kept:
+            self._ordered["n"] = (desc, grid.pts)
+        else:
+            self._ordered.pop("n", None)
+        self._dev = None        # the search operand is prepared again for the whole map at the next search
+        self._prep = None
+        self._half = None
+        self._xyz = None
+        self.__dict__.pop("_icp_desc_grid", None)
+        self.last_update = dict(points_added=added, voxels_removed=voxels_removed, points_removed=points_removed)
+
+    def _grid_update_n(self, desc, xyz, pose, origin):
+        """Update / AddPoints / RemovePointsFarFromLocation of the N-D map: ``desc`` [m, d] contiguous and ``xyz`` fp64 [m, 3] on the device
+        (None: no new points), ``pose`` a host 4 x 4 or None, ``origin`` 3 host values or None (nothing is removed)"""
+        if desc is not None and desc.shape[0] == 0:
+            desc = xyz = None
+        if self._wide_grid is None and not self.empty_n():
+            # the first update of a map add_points filled: every stored row is a kept one, so they all enter an empty grid, in insertion order
+            chunks = self._chunks["n"]
+            rows = torch.cat([r for r, _ in chunks], dim=0) if len(chunks) > 1 else chunks[0][0]
+            old_xyz = torch.cat([x for _, x in chunks], dim=0) if len(chunks) > 1 else chunks[0][1]
+            if rows.shape[1] - 3 != self._descriptor_width():
+                raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {rows.shape[1]}")
+            self._install_wide(ops.icp_grid_update(None, None, None, old_xyz.contiguous(), None, self.voxel_size, self.max_points_per_voxel, None,
+                                                   self.max_distance, rows_new=rows[:, 3:].contiguous()))
+        g = self._wide_grid
+        if g is None and desc is None:
+            self.last_update = dict(points_added=0, voxels_removed=0, points_removed=0)
+            return
+        old = None if g is None else self._chunks["n"][0][0]
+        if old is not None and desc is not None:
+            if old.shape[1] != desc.shape[1]:
+                raise ValueError("Invalid shape")
+            if old.dtype != desc.dtype:      # mixed precisions: everything to double, as add_points_device does
+                old, desc = old.double(), desc.double()
+        out = ops.icp_grid_update(None if g is None else g.keys, None if g is None else g.start, None if g is None else g.pts, xyz, pose,
+                                  self.voxel_size, self.max_points_per_voxel, origin, self.max_distance, rows_old=old, rows_new=desc)
+        self._install_wide(out)
 
     def _grid_update(self, xyz, pose, origin):
-        from .icp import OUT_OF_RANGE_MESSAGE, VoxelGridDevice, _grid_of
+        from .icp import VoxelGridDevice, _grid_of
         g = _grid_of(self) if not self.empty() else None
         if xyz is not None and xyz.shape[0] == 0:
             xyz = None
         out = ops.icp_grid_update(None if g is None else g.keys, None if g is None else g.start, None if g is None else g.pts, xyz, pose,
                                   self.voxel_size, self.max_points_per_voxel, origin, self.max_distance)
-        info_h = getattr(ops._tls, "icp_update_info", None)   # page-locked: the update's one read-back
-        if info_h is None:
-            info_h = ops._tls.icp_update_info = torch.zeros(6, dtype=torch.int32).pin_memory()
-        info_h.copy_(out["info"], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        n_voxels, n_kept, status, added, voxels_removed, points_removed = info_h.tolist()
-        if status:
-            raise ValueError(OUT_OF_RANGE_MESSAGE)   # (the map is left as it was)
+        n_voxels, n_kept, _, added, voxels_removed, points_removed = self._read_update_info(out["info"])
         grid = VoxelGridDevice.__new__(VoxelGridDevice)
         grid.voxel_size = self.voxel_size
         grid.n_voxels, grid.n_kept = n_voxels, n_kept
@@ -236,6 +338,8 @@ class VoxelHashMap:
         if self._xyz is not None:   # (kept: a scene's map serves many scans, and the ICP grid built from it stays with it)
             return self._xyz
         m = VoxelHashMap(self.voxel_size, self.max_distance, self.max_points_per_voxel)
+        if self._wide_grid is not None and not self.empty_n():
+            m._icp_grid = (self._wide_grid.n_kept, self._wide_grid)     # the updated grid itself: icp._grid_of does not rebuild it
         m._chunks["3"] = [(x, x) for _, x in self._chunks.get("n", [])]
         if "n" in self._ordered:
             m._ordered["3"] = (self._ordered["n"][1], self._ordered["n"][1])
@@ -257,6 +361,8 @@ class VoxelHashMap:
         c = self._cloud("n")  # VoxelHashMap.cpp:664-676
         if c is None:
             return np.zeros((0, 3))
+        if self._wide_grid is not None:
+            return torch.cat((c[1], c[0].double()), dim=1).cpu().numpy()
         out = c[0].double().cpu().numpy()
         out[:, :3] = c[1].cpu().numpy()
         return out
@@ -265,7 +371,10 @@ class VoxelHashMap:
     def _device_map(self):
         if self._dev is None:
             rows, xyz = self._cloud("n")
-            self._dev = (rows[:, 3:].float().contiguous(), xyz)   # VoxelHashMap.cpp:472-473: static_cast<float>
+            if self._wide_grid is not None:       # the descriptor columns alone, contiguous: float32 rows go to the search as they are
+                self._dev = (rows if rows.dtype == torch.float32 else rows.float(), xyz)
+            else:
+                self._dev = (rows[:, 3:].float().contiguous(), xyz)   # VoxelHashMap.cpp:472-473: static_cast<float>
         return self._dev
 
     def search_device(self, q_rows: Optional[torch.Tensor], min_cosine_similarity: float, resolve_all: bool = False,

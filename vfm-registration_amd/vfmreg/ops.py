@@ -958,13 +958,52 @@ def deskew_scan(rows: torch.Tensor, timestamps: torch.Tensor, delta) -> torch.Te
     return out
 
 
+def rows_merge(rows_old: Optional[torch.Tensor], rows_new: Optional[torch.Tensor], src: torch.Tensor, n_out_dev: torch.Tensor,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vfm_rows_merge: ``out[q] = cat(rows_old, rows_new)[src[q]]`` for q < min(n_out_dev[0], len(src)) -- the payload rows of a grid update
+    in the new grid's order.  ``rows_old`` [nk, w] / ``rows_new`` [m, w]: device tensors of one dtype (4 or 8 bytes per element) and width, either
+    may be None; ``src``: int32 (the update's provenance); ``n_out_dev``: int32[>= 1] on the device (``info[1:]`` of the update).  Returns
+    ``out`` [len(src), w]; the rows behind the count are not written.  No read-back."""
+    given = [r for r in (rows_old, rows_new) if r is not None]
+    if not given:
+        raise ValueError("rows_merge: no rows")
+    for r, name in ((rows_old, "rows_old"), (rows_new, "rows_new")):
+        if r is not None:
+            _chk(r, given[0].dtype, name)
+            if r.dim() != 2 or r.shape[1] != given[0].shape[1]:
+                raise ValueError("Invalid shape")
+    _chk(src, torch.int32, "src")
+    _chk(n_out_dev, torch.int32, "n_out_dev")
+    w = int(given[0].shape[1])
+    row_bytes = w * given[0].element_size()
+    if row_bytes <= 0 or row_bytes % 4:
+        raise ValueError("rows_merge: a row must be a positive multiple of 4 bytes")
+    nk = 0 if rows_old is None else int(rows_old.shape[0])
+    m = 0 if rows_new is None else int(rows_new.shape[0])
+    n_max = int(src.shape[0])
+    if out is None:
+        out = torch.empty((max(n_max, 1), w), dtype=given[0].dtype, device=given[0].device)
+    else:
+        _chk(out, given[0].dtype, "out")
+        if out.dim() != 2 or out.shape[1] != w or out.shape[0] < n_max:
+            raise ValueError("Invalid shape")
+    _lib.check(_lib.load().vfm_rows_merge(rows_old.data_ptr() if nk else None, nk, rows_new.data_ptr() if m else None, m, row_bytes,
+                                          src.data_ptr() if n_max else None, n_out_dev.data_ptr(), n_max, out.data_ptr(), _stream()), "rows_merge")
+    return out
+
+
 def icp_grid_update(keys: Optional[torch.Tensor], start: Optional[torch.Tensor], pts: Optional[torch.Tensor], xyz_new: Optional[torch.Tensor],
-                    T, voxel_size: float, max_points_per_voxel: int, origin, max_distance: float, ws: Optional[torch.Tensor] = None):
+                    T, voxel_size: float, max_points_per_voxel: int, origin, max_distance: float, ws: Optional[torch.Tensor] = None,
+                    rows_old: Optional[torch.Tensor] = None, rows_new: Optional[torch.Tensor] = None):
     """vfm_icp_grid_update: VoxelHashMap::Update on the sorted-key grid (keys int64[nv], start int32[nv + 1], pts fp64[nk, 3]; all None:
     an empty grid).  ``xyz_new``: fp64 [m, 3] on the device or None; ``T``: a 4 x 4 on the host or None (points as they are); ``origin``:
     3 values on the host or None (nothing is removed).  Returns ``dict(keys, start, pts, info)`` of device tensors sized nv + m, nv + m + 1,
-    nk + m and 6 -- info = {n_voxels, n_kept, status, points_added, voxels_removed, points_removed}.  No read-back."""
+    nk + m and 6 -- info = {n_voxels, n_kept, status, points_added, voxels_removed, points_removed}.  No read-back.
+    ``rows_old`` [nk, w] / ``rows_new`` [m, w] (a payload per point, see ``rows_merge``; None where there are no such points): the update runs
+    as vfm_icp_grid_update_src and the dict also holds ``src`` (int32[nk + m]) and ``rows`` ([nk + m, w]: the payload in the new grid's order,
+    its first n_kept rows written) -- two enqueues, still no read-back."""
     lib = _lib.load()
+    payload = rows_old is not None or rows_new is not None
     nv = 0 if keys is None else int(keys.shape[0])
     nk = 0 if pts is None else int(pts.shape[0])
     m = 0 if xyz_new is None else int(xyz_new.shape[0])
@@ -992,9 +1031,20 @@ def icp_grid_update(keys: Optional[torch.Tensor], start: Optional[torch.Tensor],
     need = lib.vfm_icp_grid_update_workspace_bytes(nv, nk, m)
     if ws is None or ws.numel() < need:
         ws = _ws(need, dev)
-    _lib.check(lib.vfm_icp_grid_update(keys.data_ptr() if nv else None, start.data_ptr() if nv else None, pts.data_ptr() if nv else None, nv, nk,
-                                       xyz_new.data_ptr() if m else None, m, None if Th is None else Th.ctypes.data, float(voxel_size),
-                                       int(max_points_per_voxel), None if oh is None else oh.ctypes.data, float(max_distance),
-                                       keys_out.data_ptr(), start_out.data_ptr(), pts_out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       _stream()), "icp_grid_update")
-    return dict(keys=keys_out, start=start_out, pts=pts_out, info=info)
+    head = (keys.data_ptr() if nv else None, start.data_ptr() if nv else None, pts.data_ptr() if nv else None, nv, nk,
+            xyz_new.data_ptr() if m else None, m, None if Th is None else Th.ctypes.data, float(voxel_size), int(max_points_per_voxel),
+            None if oh is None else oh.ctypes.data, float(max_distance), keys_out.data_ptr(), start_out.data_ptr(), pts_out.data_ptr(),
+            info.data_ptr())
+    if not payload:
+        _lib.check(lib.vfm_icp_grid_update(*head, ws.data_ptr(), ws.numel(), _stream()), "icp_grid_update")
+        return dict(keys=keys_out, start=start_out, pts=pts_out, info=info)
+    if (0 if rows_old is None else int(rows_old.shape[0])) != nk or (0 if rows_new is None else int(rows_new.shape[0])) != m:
+        raise ValueError("expected one payload row per point")
+    src = torch.empty(nk + m, dtype=torch.int32, device=dev)
+    _lib.check(lib.vfm_icp_grid_update_src(*head, src.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "icp_grid_update_src")
+    if nk + m == 0:     # (an empty payload for an empty grid)
+        given = rows_old if rows_old is not None else rows_new
+        rows = torch.empty((1, given.shape[1]), dtype=given.dtype, device=dev)
+    else:
+        rows = rows_merge(rows_old if nk else None, rows_new if m else None, src, info[1:])
+    return dict(keys=keys_out, start=start_out, pts=pts_out, info=info, src=src, rows=rows)
