@@ -498,6 +498,58 @@ typedef struct {
 int vfm_lift_multicam(const double *pcl_4xn, int64_t n, int ncam, const vfm_lift_camera *cams_host,
                       int C, float *desc_out, uint8_t *filled, vfm_stream_t stream);
 
+/* ------------------------------------------------------------------ camera front end */
+
+/* The RobotCar image path of OxfordRobotcar.read_images (src/vfm-reg/src/dataloader/oxford_robotcar.py:103-136): Bayer demosaic,
+ * look-up-table undistortion, the uint8 cast, the bottom crop and the factor-2 resize.  No entry point allocates or keeps state. */
+#define VFM_BAYER_RGGB 0
+#define VFM_BAYER_GBRG 1
+#define VFM_BAYER_GRBG 2
+#define VFM_BAYER_BGGR 3
+
+/* colour_demosaicing.demosaicing_CFA_Bayer_bilinear: cfa H x W uint8 -> rgb_out H x W x 3 fp32 on 0..255 (not normalised).
+ * R, B = conv(CFA * mask, [[1,2,1],[2,4,2],[1,2,1]] / 4), G = conv(CFA * mask, [[0,1,0],[1,4,1],[0,1,0]] / 4), border `reflect`
+ * (d c b a | a b c d): on the outermost ring a mirrored pixel keeps its colour, so values there reach 573.75.  Every value is a
+ * multiple of 1/4: exact.  2 <= H, W <= 32768. */
+int vfm_demosaic_bilinear(const uint8_t *cfa, int64_t H, int64_t W, int pattern, float *rgb_out,
+                          vfm_stream_t stream);
+
+#define VFM_IMAGE_U8 0
+#define VFM_IMAGE_F32 1
+#define VFM_IMAGE_F64 2
+
+/* CameraModel.undistort (robotcar_sdk/python/camera_model.py:89-117): scipy's map_coordinates(order=1) per channel of an
+ * H x W x C image (dtype VFM_IMAGE_*; out has the same type and shape).  lut: the SDK's bilinear_lut, H*W x 2 fp64, column 0 = x,
+ * column 1 = y, row v*W + u for output pixel (v, u); 16-byte aligned.  fp64, unfused: a sample is inside iff 0 <= y <= H-1 and
+ * 0 <= x <= W-1, otherwise the result is exactly 0 (NaN and infinite entries included -- scipy leaves those undefined);
+ * f = x - floor(x), w0 = 1 - f, w1 = 1 - w0; t = sum (v[a][b] * wr[a]) * wc[b] in the order (0,0), (0,1), (1,0), (1,1); a tap past
+ * the last row / column has weight 0 and reads the clamped pixel.  Float images store t in their own type; uint8 images store
+ * scipy's integer output (t + 0.5 truncated, clamped to 0..255). */
+int vfm_undistort_lut(const void *image, int dtype, int64_t H, int64_t W, int C, const double *lut,
+                      void *out, vfm_stream_t stream);
+
+/* The fused front end for a whole rig: per camera demosaic -> undistort -> astype(uint8) -> drop crop_bottom rows -> (subsample 2)
+ * PIL's resize(BILINEAR).  out: uint8 RGB [(H - crop_bottom) / subsample][W / subsample][3].  Every output pixel demosaics its four
+ * taps on the fly, interpolates as vfm_undistort_lut does on the exact values and casts as numpy's astype(uint8) does: truncate,
+ * keep the low 8 bits (reachable only through the outermost ring's overshoot).  A table entry outside the frame gives exactly
+ * (0, 0, 0).  The demosaiced image is never written; cropped rows are never computed.  subsample 2 is Pillow's two 22-bit
+ * fixed-point passes (horizontal, uint8 rounding, vertical) over the cropped image held in the workspace; cropped height and width
+ * must then be even (VFM_EINVAL otherwise, and for any other factor).  The struct array is HOST memory, its pointers DEVICE;
+ * cameras may differ in size.  ws: vfm_rectify_bayer_workspace_bytes of the same records (0 when no camera subsamples). */
+#define VFM_RECTIFY_MAX_CAMS 8
+typedef struct {
+    const uint8_t *mosaic; /* H x W Bayer frame */
+    int64_t H, W;
+    int pattern;           /* VFM_BAYER_* */
+    const double *table;   /* bilinear_lut of this camera, H*W x 2 fp64, 16-byte aligned */
+    int64_t crop_bottom;   /* rows dropped at the bottom, 0 <= crop_bottom < H */
+    int subsample;         /* 1 or 2 */
+    uint8_t *out;
+} vfm_rectify_camera;
+size_t vfm_rectify_bayer_workspace_bytes(int ncam, const vfm_rectify_camera *cams_host);
+int vfm_rectify_bayer(int ncam, const vfm_rectify_camera *cams_host, void *ws, size_t ws_bytes,
+                      vfm_stream_t stream);
+
 /* transform_pcl (UT:47-54): xyz' = T[:3,:] @ [xyz;1], fp64. T: 16 fp64 on the device. */
 int vfm_transform_xyz_f64(const double *xyz, int64_t n, const double *T, double *out,
                           vfm_stream_t stream);

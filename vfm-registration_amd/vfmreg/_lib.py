@@ -28,6 +28,11 @@ class LiftCamera(C.Structure):  # vfm_lift_camera
                 ("Wup", C.c_int), ("rot_mode", C.c_int)]
 
 
+class RectifyCamera(C.Structure):  # vfm_rectify_camera
+    _fields_ = [("mosaic", C.c_void_p), ("H", C.c_int64), ("W", C.c_int64), ("pattern", C.c_int), ("table", C.c_void_p),
+                ("crop_bottom", C.c_int64), ("subsample", C.c_int), ("out", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/vfmreg.h one to one
 SIGNATURES = {
     "vfm_last_error": (C.c_char_p, []),
@@ -86,6 +91,10 @@ SIGNATURES = {
     "vfm_lift_multicam": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp]),
     "vfm_gather_bilinear_patchgrid": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp,
                                                 c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vfm_demosaic_bilinear": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, c_vp]),
+    "vfm_undistort_lut": (C.c_int, [c_vp, C.c_int, c_i64, c_i64, C.c_int, c_vp, c_vp, c_vp]),
+    "vfm_rectify_bayer_workspace_bytes": (C.c_size_t, [C.c_int, c_vp]),
+    "vfm_rectify_bayer": (C.c_int, [C.c_int, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_transform_xyz_f64": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vfm_voxel_first_workspace_bytes": (C.c_size_t, [c_i64]),
     "vfm_voxel_first": (C.c_int, [c_vp, c_i64, c_i64, C.c_double, C.c_int32, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),

@@ -2,8 +2,10 @@
 (src/vfm-reg/src/dataloader/{nclt,oxford_robotcar,kitti_odometry}.py):
 ``Dataset.project_pcl_to_image(pcl[4,N], image[H,W,3], camera) -> (u, v, pcl_indices)``.
 
-The file readers, undistortion, demosaicing and timestamp handling of those classes are dataset
-I/O and out of scope: the calibration they load is passed in.  The
+The file readers and timestamp handling of those classes are dataset I/O and out of scope
+(SURVEY.md section 2 rows 2-3): the calibration they load is passed in.  RobotCar's camera front
+end -- demosaic, undistortion, crop, subsample of a decoded Bayer frame -- is
+``OxfordRobotcar.rectify_images`` (csrc/camera.hip); NCLT's (cv2.remap) stays out.  The
 projection itself runs on the GPU (csrc/project.hip) in fp64 with the reference's operation order;
 integer outputs equal the reference's on the golden fixtures.
 """
@@ -83,6 +85,37 @@ class OxfordRobotcar(_Base):
         self.camera_model = camera_model
         self.image_subsample = image_subsample
         self.cameras = cameras or list(camera_model.keys())
+
+    # oxford_robotcar.py:111-124: (Bayer pattern, rows cropped at the bottom -- the hood / the area without LiDAR coverage)
+    FRONT_END = {"stereo/centre": ("GBRG", 150)}
+    FRONT_END_DEFAULT = ("RGGB", 200)
+
+    def rectify_images(self, raw: Dict[str, object], device: bool = False) -> Dict[str, object]:
+        """What ``read_images`` does after decoding a frame (oxford_robotcar.py:109-124,132-135), for the whole rig in ONE
+        ``ops.rectify_bayer`` call: ``raw`` {camera: uint8 Bayer mosaic [H, W], numpy or device tensor} -> {camera: uint8 RGB
+        [(H - crop) / s, W / s, 3]}, numpy by default, device tensors with ``device=True``.  ``camera_model[camera]`` must be a
+        vfmreg.camera_model.CameraModel (it holds the look-up table on the device)."""
+        s = int(self.image_subsample)
+        if s not in (1, 2):
+            raise NotImplementedError(f"image_subsample {s}: only PIL's Image.resize(BILINEAR) by 1 or 2 is restated")
+        cams = []
+        for camera, mosaic in raw.items():
+            assert camera in self.cameras, f"Camera {camera} not available"
+            pattern, crop = self.FRONT_END.get(camera, self.FRONT_END_DEFAULT)
+            if not isinstance(mosaic, torch.Tensor):
+                mosaic = torch.from_numpy(np.ascontiguousarray(mosaic, dtype=np.uint8))
+            H, W = mosaic.shape
+            if (H - crop) % s or W % s:
+                raise ValueError(f"{camera}: cropped size {H - crop} x {W} is not divisible by the subsample factor {s}")
+            cm = self.camera_model[camera]
+            if H * W != cm.bilinear_lut.shape[0]:
+                raise ValueError("Incorrect image size for camera model")
+            cams.append(dict(mosaic=mosaic, pattern=pattern, crop_bottom=crop, subsample=s, cm=cm))
+        for c in cams:   # everything above is judged without a device
+            c["mosaic"] = c["mosaic"].cuda()
+            c["table"] = c.pop("cm").lut_device()
+        outs = ops.rectify_bayer(cams)
+        return {camera: (o if device else o.cpu().numpy()) for camera, o in zip(raw.keys(), outs)}
 
     def projection_params(self, camera: str, image_shape) -> dict:
         assert camera in self.cameras, f"Camera {camera} not available"

@@ -443,6 +443,99 @@ def gather_bilinear(grid: torch.Tensor, Hup: int, Wup: int, rot_mode: int, image
                                                  u.shape[0], desc.data_ptr(), filled.data_ptr(), _stream()), "gather")
 
 
+# ----------------------------------------------------------------------------- camera front end
+BAYER_PATTERNS = {"RGGB": 0, "GBRG": 1, "GRBG": 2, "BGGR": 3}   # VFM_BAYER_*
+RECTIFY_MAX_CAMS = 8                                            # VFM_RECTIFY_MAX_CAMS
+_IMAGE_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}   # VFM_IMAGE_*
+
+
+def _bayer(pattern: str) -> int:
+    if pattern not in BAYER_PATTERNS:
+        raise ValueError(f"pattern: expected one of {sorted(BAYER_PATTERNS)}, got {pattern!r}")
+    return BAYER_PATTERNS[pattern]
+
+
+def _lut_rows(lut: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Shapes are judged before residence: a table of the wrong length is the reference's ValueError wherever the tensors live."""
+    if getattr(lut, "ndim", 0) != 2 or lut.shape[1] != 2 or lut.shape[0] != H * W:
+        raise ValueError("Incorrect image size for camera model")   # camera_model.py:103-104
+    return lut
+
+
+def demosaic_bilinear(cfa: torch.Tensor, pattern: str = "RGGB") -> torch.Tensor:
+    """colour_demosaicing.demosaicing_CFA_Bayer_bilinear: uint8 mosaic [H, W] -> float32 [H, W, 3] on 0..255 (border ``reflect``)."""
+    code = _bayer(pattern)
+    if getattr(cfa, "ndim", 0) != 2:
+        raise ValueError("cfa: expected a 2-D mosaic")
+    _chk(cfa, torch.uint8, "cfa")
+    out = torch.empty(cfa.shape + (3,), dtype=torch.float32, device=cfa.device)
+    _lib.check(_lib.load().vfm_demosaic_bilinear(cfa.data_ptr(), cfa.shape[0], cfa.shape[1], code, out.data_ptr(), _stream()),
+               "demosaic_bilinear")
+    return out
+
+
+def undistort_lut(image: torch.Tensor, bilinear_lut: torch.Tensor) -> torch.Tensor:
+    """CameraModel.undistort (robotcar_sdk camera_model.py:89-117): image [H, W, C] uint8 / float32 / float64, ``bilinear_lut``
+    [H*W, 2] fp64 in the SDK's layout (x, y); the result has the image's dtype, as scipy's map_coordinates(order=1) gives it."""
+    if not isinstance(image, torch.Tensor) or image.dtype not in _IMAGE_DTYPES:
+        raise TypeError(f"image: expected a uint8, float32 or float64 tensor, got {getattr(image, 'dtype', type(image))}")
+    if image.dim() != 3:
+        raise ValueError("Undistortion function only works with multi-channel images")   # camera_model.py:108-109
+    H, W, Cc = image.shape
+    _lut_rows(bilinear_lut, H, W)
+    _chk(image, image.dtype, "image")
+    _chk(bilinear_lut, torch.float64, "bilinear_lut")
+    out = torch.empty_like(image)
+    _lib.check(_lib.load().vfm_undistort_lut(image.data_ptr(), _IMAGE_DTYPES[image.dtype], H, W, Cc, bilinear_lut.data_ptr(),
+                                             out.data_ptr(), _stream()), "undistort_lut")
+    return out
+
+
+def rectify_bayer(cams: list, ws: Optional[torch.Tensor] = None) -> list:
+    """oxford_robotcar.py:109-124,132-135 for a whole rig in one call.  ``cams``: dicts with ``mosaic`` (uint8 [H, W]), ``pattern``
+    (a BAYER_PATTERNS name), ``table`` (bilinear_lut [H*W, 2] fp64), ``crop_bottom`` (rows), ``subsample`` (1 or 2) and optionally
+    ``out`` (uint8 [(H - crop_bottom) / s, W / s, 3]).  Returns the output tensors in camera order."""
+    if not 1 <= len(cams) <= RECTIFY_MAX_CAMS:
+        raise ValueError(f"rectify_bayer: 1..{RECTIFY_MAX_CAMS} cameras per call")
+    plans = []
+    for c in cams:   # shapes first: they are refused the same way wherever the tensors live
+        m = c["mosaic"]
+        if getattr(m, "ndim", 0) != 2:
+            raise ValueError("mosaic: expected a 2-D Bayer frame")
+        H, W = m.shape
+        s, crop = int(c.get("subsample", 1)), int(c.get("crop_bottom", 0))
+        if s not in (1, 2):
+            raise NotImplementedError(f"subsample {s}: only PIL's resize(BILINEAR) by 1 or 2 is restated")
+        if not 0 <= crop < H:
+            raise ValueError("crop_bottom: expected 0 <= crop_bottom < H")
+        if (H - crop) % s or W % s:
+            raise ValueError(f"cropped size {H - crop} x {W} is not divisible by the subsample factor {s}")
+        _lut_rows(c["table"], H, W)
+        plans.append((H, W, s, crop, ((H - crop) // s, W // s, 3)))
+    arr = (_lib.RectifyCamera * len(cams))()
+    outs = []
+    for k, (c, (H, W, s, crop, shape)) in enumerate(zip(cams, plans)):
+        m = _chk(c["mosaic"], torch.uint8, "mosaic")
+        table = _chk(c["table"], torch.float64, "table")
+        out = c.get("out")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=m.device)
+        elif tuple(_chk(out, torch.uint8, "out").shape) != shape:
+            raise ValueError("Invalid shape")
+        a = arr[k]
+        a.mosaic, a.H, a.W, a.pattern = m.data_ptr(), H, W, _bayer(c["pattern"])
+        a.table, a.crop_bottom, a.subsample, a.out = table.data_ptr(), crop, s, out.data_ptr()
+        outs.append(out)
+    import ctypes as C_
+    lib = _lib.load()
+    p = C_.cast(arr, C_.c_void_p)
+    need = lib.vfm_rectify_bayer_workspace_bytes(len(cams), p)
+    if ws is None and need:
+        ws = _ws(need, outs[0].device)
+    _lib.check(lib.vfm_rectify_bayer(len(cams), p, _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "rectify_bayer")
+    return outs
+
+
 def transform_xyz(xyz: torch.Tensor, T: torch.Tensor) -> torch.Tensor:
     """transform_pcl's coordinate part (vfm_reg/utils.py:47-54): fp64 [N,3] x [4,4]."""
     _chk(xyz, torch.float64, "xyz")

@@ -8,7 +8,9 @@ Reference flow: per camera full-resolution features (image_features.py:104-110: 
 in a Python loop (PS:85-91), first camera wins (PS:96-101).  Here: ONE batched ViT forward for all
 cameras, then per camera (in ``sequence.cameras`` priority order) a projection kernel and a fused
 "interpolate at the pixel + black test + first-camera-wins scatter" kernel; the upsampled tensor is
-never materialised.  ``sequence`` needs ``read_images(filenames=...) -> {camera: HxWx3 uint8}``,
+never materialised.  ``images`` / ``images_list`` may hold uint8 device tensors
+(OxfordRobotcar.rectify_images(device=True)): they are used where they are, without a download.
+``sequence`` needs ``read_images(filenames=...) -> {camera: HxWx3 uint8}``,
 ``cameras`` and ``project_pcl_to_image`` (the vfmreg.dataloader classes); ``feature_generator`` is a
 vfmreg.image_features.ImageFeatureGenerator, or any object with
 ``get_image_features(image, upsample=True) -> HxWxC`` (then the gather reads that map).
@@ -25,6 +27,15 @@ from .dataloader import NCLT
 _FORCE_PER_CAMERA = False  # tests: run the per-camera path (project -> compact -> gather per camera)
 
 
+def _image_to_device(img, dev="cuda") -> torch.Tensor:
+    """An image as a uint8 device tensor: device tensors (OxfordRobotcar.rectify_images(device=True)) are taken as they are."""
+    if isinstance(img, torch.Tensor):
+        if img.dtype != torch.uint8:
+            raise TypeError(f"images: expected uint8, got {img.dtype}")
+        return img.to(dev).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).to(dev)
+
+
 def create_descriptors(image_files, sequence, feature_generator, pcl, images=None, _grids=None, _img_d=None) -> np.ndarray:
     """``_grids`` (create_descriptors_batch): the cameras' patch features, already computed in a larger batch -- {camera: device
     tensor [16, pw, C]}; ``_img_d``: the cameras' images where that batch already put them on the device ({camera: uint8 tensor})."""
@@ -35,7 +46,7 @@ def create_descriptors(image_files, sequence, feature_generator, pcl, images=Non
     # PS:69: np.insert(pcl, 3, 1, axis=1).T (float32 xyz promoted to fp64 inside the projection)
     pcl_h = np.insert(np.asarray(pcl)[:, :3], 3, values=1, axis=1).T
     pcl_d = torch.from_numpy(np.ascontiguousarray(pcl_h, dtype=np.float64)).to(dev)
-    img_d = _img_d if _img_d is not None else {c: torch.from_numpy(np.ascontiguousarray(images[c], dtype=np.uint8)).to(dev) for c in cams}
+    img_d = _img_d if _img_d is not None else {c: _image_to_device(images[c], dev) for c in cams}
     fused = hasattr(feature_generator, "patch_features_device")
     if _grids is not None:
         grid = _grids
@@ -47,7 +58,8 @@ def create_descriptors(image_files, sequence, feature_generator, pcl, images=Non
         else:
             grid = {c: feature_generator.patch_features_device(img_d[c].unsqueeze(0))[0] for c in cams}
     else:
-        grid = {c: torch.from_numpy(np.ascontiguousarray(feature_generator.get_image_features(images[c], upsample=True),
+        host = {c: images[c].cpu().numpy() if isinstance(images[c], torch.Tensor) else images[c] for c in cams}
+        grid = {c: torch.from_numpy(np.ascontiguousarray(feature_generator.get_image_features(host[c], upsample=True),
                                                          dtype=np.float32)).to(dev) for c in cams}
     C = next(iter(grid.values())).shape[-1]
     # (vfm_lift_multicam writes every row -- zeros where nothing is seen --; the per-camera path below writes only what it claims)
@@ -108,13 +120,16 @@ def create_descriptors_batch(image_files_list, sequence, feature_generator, pcls
     for i0 in range(0, n_clouds, max(clouds_per_forward, 1)):
         group = range(i0, min(n_clouds, i0 + max(clouds_per_forward, 1)))
         imgs = {i: images_of(i) for i in group}
-        shapes = {tuple(np.asarray(im).shape) for i in group for im in imgs[i].values()}
+        shapes = {tuple(im.shape) if isinstance(im, torch.Tensor) else tuple(np.asarray(im).shape) for i in group for im in imgs[i].values()}
         if not batched or len(shapes) != 1:
             for i in group:
                 out[i] = create_descriptors(None, sequence, feature_generator, pcls[i], images=imgs[i])
             continue
         keys = [(i, c) for i in group for c in imgs[i].keys()]
-        batch = torch.stack([torch.from_numpy(np.ascontiguousarray(imgs[i][c], dtype=np.uint8)) for i, c in keys]).to("cuda")
+        if all(isinstance(imgs[i][c], torch.Tensor) for i, c in keys):
+            batch = torch.stack([_image_to_device(imgs[i][c]) for i, c in keys])
+        else:
+            batch = torch.stack([_image_to_device(imgs[i][c], "cpu") for i, c in keys]).to("cuda")
         grids = feature_generator.patch_features_device(batch)
         per_cloud = {i: ({}, {}) for i in group}
         for k, (i, c) in enumerate(keys):
