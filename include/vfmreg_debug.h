@@ -11,7 +11,8 @@
  *     vfm_config_t bound per thread -- include/vfmreg.h, vfm_config_* -- and vfmreg/_lib.py keeps the old names as Python functions that
  *     set the calling thread's config, for the tools.)
  *   - vfm_debug_match_stats / vfm_debug_i8_rows / vfm_debug_mx6_rows / vfm_debug_ransac_state  read-backs for tests; they synchronise the device.
- *   - vfm_debug_search_plan / vfm_debug_prepare_plan / vfm_debug_vit_plan  read the calling thread's vfm_config and nothing else; host memory only.
+ *   - vfm_debug_search_plan / vfm_debug_coarse_plan / vfm_debug_prepare_plan / vfm_debug_vit_plan  read the calling thread's vfm_config and nothing
+ *                     else; host memory only.
  *   - vfm_debug_l2_narrow_slices  host arithmetic only; vfm_debug_l2_narrow_evals  reads a workspace's counters and synchronises the device.
  *   - vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names  THREAD-LOCAL like vfm_prof_*: which instantiation of the coarse kernels
  *                     the last search issued FROM THE CALLING THREAD launched, and the names of all of them; host memory only.
@@ -33,12 +34,12 @@ int vfm_prof_arm(void *start, void *stop);
 int vfm_prof_elapsed_ms(void *start, void *stop, float *ms_host);
 int vfm_prof_events_destroy(void *start, void *stop);
 
-/* tests: which coarse kernel ran.  Every launcher instantiation of csrc/match_coarse_*.hip has a name spelled from its template arguments
+/* tests: which coarse kernel ran.  Every instantiation of the kernels of csrc/match_coarse_*.hip has a name spelled from its template arguments
  * ("i8q2<12,top2=0,low=0,fused=0>", "mx6q2<3,FUSE,low=0,img=6,ring=5,T=4,NS=3>", "pipe<24,sparse>+seed": the sparse fp16 kernel launched with
- * seed units) and notes it, per thread, when it launches.  vfm_debug_last_coarse_kernel: the name noted last by the calling thread -- the
+ * seed units), and a launch notes it per thread.  vfm_debug_last_coarse_kernel: the name noted last by the calling thread -- the
  * Euclidean entry points launch one kernel per direction, the reverse direction last -- or "" if it has launched none.
- * vfm_debug_coarse_kernel_names: every name the library's launchers can note, sorted, separated by '\n'; the list is put together by the
- * instantiations themselves while the library is loaded.  Both write a NUL-terminated string to buf_host[cap] (VFM_EINVAL if it does not
+ * vfm_debug_coarse_kernel_names: every name a launch can note, sorted, separated by '\n'; the list is generated from the same lines of
+ * csrc/match_internal.h that instantiate the kernels.  Both write a NUL-terminated string to buf_host[cap] (VFM_EINVAL if it does not
  * fit) and do not touch the device. */
 int vfm_debug_last_coarse_kernel(char *buf_host, int cap);
 int vfm_debug_coarse_kernel_names(char *buf_host, int cap);
@@ -51,6 +52,16 @@ int vfm_debug_coarse_kernel_names(char *buf_host, int cap);
  *     finish=<the kernels of the finish stage in launch order, separated by ','>
  * A combination the search refuses fails here with the same error.  Host memory only: no device is touched. */
 int vfm_debug_search_plan(int records, int d, int64_t n, int64_t m, int gated, char *buf_host, int cap);
+
+/* tests / tools: the launch of that search's coarse pass, resolved by the function the search itself calls once (csrc/match_internal.h,
+ * resolve_coarse, behind resolve_search).  inner_product: 0 for the fp16 pass of the Euclidean entry points (d: their padded K); row_bias:
+ * that pass at K = 640 / 768, which adds a bias per map row; compute_units: of the device asked about, 0: the current device's.  One line
+ * of text to buf_host[cap]:
+ *     kernel=<the name vfm_debug_last_coarse_kernel reports after the launch> nqb=<query blocks> nslices=<map slices>
+ *     seed=<workgroups of the seed round at the head of the grid> block=<threads> lds=<bytes of dynamic LDS> tune=<CoarseArgs::tune>
+ * The grid is seed + nqb x nslices workgroups.  A combination the search refuses fails here with the same error.  Host memory only. */
+int vfm_debug_coarse_plan(int records, int d, int64_t n, int64_t m, int gated, int inner_product, int row_bias, int compute_units,
+                          char *buf_host, int cap);
 
 /* tests / tools: what a preparation would do under the calling thread's vfm_config, resolved by the same function the entry points use.
  * entry: which of them is asked about -- the six exported ones, and the two forms the library uses inside vfm_match_mutual_l2 (one operand,

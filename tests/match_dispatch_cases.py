@@ -1,8 +1,8 @@
 """The dispatch tree of the matcher's coarse pass as a table of cases, and one adversarial data set for all of them.
 
-Which coarse kernel a search launches is decided at call time (csrc/match_internal.h: resolve_search; csrc/match_api.hip:
-do_search_coarse, use_i8, use_sparse; the launchers at the end of csrc/match_coarse_f16.hip, _i8.hip and _mx6.hip) from the width, the record kind, gated or
-not, size thresholds and the thread's vfm_config.  Every case below names the kernel the launchers' rules give for it, with the rule
+Which coarse kernel a search launches is decided at call time (csrc/match_internal.h: resolve_search, then resolve_coarse; csrc/match_api.hip:
+use_i8, use_sparse) from the width, the record kind, gated or
+not, size thresholds and the thread's vfm_config.  Every case below names the kernel resolve_coarse's rules give for it, with the rule
 beside it; tests/test_gpu_coarse_dispatch.py runs each case, reads back which kernel ran (vfm_debug_last_coarse_kernel) and compares
 the answers with the fp64 oracle; tests/test_coarse_dispatch_table.py checks that the table names every launcher instantiation in the
 library.  No GPU and no torch in this module.

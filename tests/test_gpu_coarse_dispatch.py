@@ -101,11 +101,13 @@ def test_case_runs_its_kernel_and_gives_the_oracle_answers(case):
         if case.entry == "ip":
             idx, sim, kernel = _search_ip(_dev(q), _dev(b))
             assert kernel == case.kernel
+            assert _lib.coarse_plan(case.records, case.d, case.n, case.m, gated=False, compute_units=0)["kernel"] == kernel
             np.testing.assert_array_equal(idx, ridx)
             np.testing.assert_array_equal(sim, rsim)
         else:
             idx, sim, kernel = Gated(_dev(q), _dev(b), case.records).search()
             assert kernel == case.kernel
+            assert _lib.coarse_plan(case.records, case.d, case.n, case.m, gated=True, compute_units=0)["kernel"] == kernel
             _assert_gate_contract(idx, sim, ridx, rsim, case.id)
     assert _lib.current() is before     # the block's config is unbound again
 

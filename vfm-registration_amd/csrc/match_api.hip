@@ -1,63 +1,61 @@
 // match_api.hip -- the matcher's C ABI (include/vfmreg.h): which coarse pass and record kind a search takes, the argument
-// block of the coarse kernels, workspace layout queries, the one-shot and split entry points, experiment knobs and the
-// profiling hook.  Kernels: match_prep.hip, match_coarse_f16.hip, match_coarse_i8.hip, match_finish.hip, match_l2.hip.
+// block of the coarse kernels and the one frame their launches go through (which kernel, on what grid: match_internal.h,
+// resolve_coarse), workspace layout queries, the one-shot and split entry points, experiment knobs and the profiling hook.
+// Kernels: match_prep.hip, match_coarse_f16.hip, match_coarse_i8.hip, match_coarse_mx6.hip, match_finish.hip, match_l2.hip.
 #include "match_internal.h"
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 
 namespace vfmm {
 
-int choose_slices(int nqb, int nchunks) {
-    if (vfm_cfg().force_slices > 0) return vfm_cfg().force_slices < nchunks ? vfm_cfg().force_slices : nchunks;
-    // Fill 256 CUs with whole "rounds" of workgroups (tail efficiency).  Every (query block, slice) unit re-reads its 256
-    // queries (196 KB), so HBM / Infinity-Cache traffic grows with the slice count (C2: 55 slices 1.45 GB per launch).
-    // Round 2 sweep at C2 with the seeded sparse kernel (registrations/s in the pipeline): 14-16 slices 349, 21: 367,
-    // 29: 366, 35: 367, 42: 365, 48: 364, 55: 364 -- flat from ~8 rounds on.  So: among the counts within 1 % of the best
-    // tail efficiency take the SMALLEST that still gives >= 8 rounds (29 at C2); without such a count, the most efficient.
-    int best_s = 1;
-    double best_eff = -1.0;
-    const int smax = nchunks < 64 ? nchunks : 64;
-    auto eff_of = [&](int s, long long* rounds_out) {
-        const long long total = (long long)nqb * s;
-        const long long rounds = (total + 255) / 256;
-        if (rounds_out) *rounds_out = rounds;
-        return (double)total / (double)(rounds * 256);
-    };
-    for (int s = 1; s <= smax; ++s) {
-        if (nchunks / s < 8 && s > 1) break;  // keep >= 32 tiles per workgroup
-        const double eff = eff_of(s, nullptr);
-        if (eff > best_eff + 1e-9) {
-            best_eff = eff;
-            best_s = s;
-        }
+// profiling hook (vfm_prof_arm): events recorded around the next coarse launch on this thread
+static thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
+// the calling thread's last coarse launch (vfm_debug_last_coarse_kernel): CoarseInst * 2 + seeded, -1: none
+static thread_local int g_last_coarse = -1;
+
+// an instantiation as it spells itself from its template arguments (match_internal.h: k_coarse_insts)
+static std::string coarse_inst_name(int inst, bool seeded) {
+    const short* a = k_coarse_insts[inst].a;
+    char name[64];
+    switch (k_coarse_insts[inst].family) {
+        case CF_PIPE: snprintf(name, sizeof(name), "pipe<%d,%s>%s", a[0], a[1] ? "sparse" : "dense", seeded ? "+seed" : ""); break;
+        case CF_V: snprintf(name, sizeof(name), "v<%d,qsets=%d>", a[0], a[1]); break;
+        case CF_R: snprintf(name, sizeof(name), "r<%d,qsets=%d,nbuf=%d,bias=%d>", a[0], a[1], a[2], a[3]); break;
+        case CF_I8: snprintf(name, sizeof(name), "i8<%d,T=%d,top2=%d,low=%d>", a[0], a[1], a[2], a[3]); break;
+        case CF_I8Q2: snprintf(name, sizeof(name), "i8q2<%d,top2=%d,low=%d,fused=%d>", a[0], a[1], a[2], a[3]); break;
+        default: snprintf(name, sizeof(name), "mx6q2<%d,%s,low=%d,img=%d,ring=%d,T=%d,NS=%d>", a[0], a[1] == MX6_FUSE ? "FUSE" : a[1] == MX6_TOP2 ? "TOP2" : "BEST",
+                          a[2], a[3], a[4], a[5], a[6]); break;
     }
-    for (int s = 1; s < best_s; ++s) {
-        long long rounds;
-        const double eff = eff_of(s, &rounds);
-        if (rounds >= 8 && eff >= best_eff - 0.01) return s;
-    }
-    return best_s;
+    return name;
 }
 
-// profiling hook (vfm_prof_arm): events recorded around the next coarse launch on this thread
-thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
+int launch_coarse_kernel(CoarseKernel kernel, const char* what, const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st) {
+    static unsigned long long attr_set[CI_COUNT] = {};  // per instantiation, one bit per device
+    if (!attr_done(attr_set[l.inst])) {
+        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, l.lds));
+        attr_mark(attr_set[l.inst]);
+    }
+    g_last_coarse = l.inst * 2 + (l.seeded ? 1 : 0);
+    if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)l.grid()), dim3((unsigned)l.block), (size_t)l.lds, st, a);
+    VFM_CHECK_LAUNCH(what);
+    if (g_prof_stop) VFM_CHECK_HIP(hipEventRecord(g_prof_stop, st));
+    g_prof_start = g_prof_stop = nullptr;
+    return VFM_OK;
+}
 
-// the launcher instantiations' names (match_internal.h, CoarseKernelName): a list the objects link themselves into while the library is
-// loaded (the head is constant-initialised, so it is there before any of them is constructed), and the calling thread's last launch
-static const CoarseKernelName* g_coarse_kernel_names = nullptr;
-thread_local const CoarseKernelName* g_last_coarse_kernel = nullptr;
-
-CoarseKernelName::CoarseKernelName(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(name, sizeof(name), fmt, ap);
-    va_end(ap);
-    next = g_coarse_kernel_names;
-    g_coarse_kernel_names = this;
+int launch_coarse(const CoarseLaunch& l, CoarseArgs& a, hipStream_t st) {
+    a.nqb = l.nqb;
+    a.nslices = l.nslices;
+    a.seed_parts = l.seed_parts;
+    a.seed_chunks = l.seed_chunks;
+    a.nseed_pad = l.nseed_pad;
+    a.tune = l.tune;
+    const int family = k_coarse_insts[l.inst].family;   // (the file its kernels live in)
+    return family <= CF_R ? launch_coarse_f16(l, a, st) : family <= CF_I8Q2 ? launch_coarse_int8(l, a, st) : launch_coarse_mx6(l, a, st);
 }
 
 // 0 = default (pipelined kernel for d <= 384); 1 = match_coarse_kernel<.,1>; 2 = match_coarse_kernel<.,2>;
@@ -91,10 +89,7 @@ static bool runs_quantised(int records, int d, int64_t n, int64_t m, bool gated)
     return resolve_search(plan, records & ~VFM_RECORDS_NO_I8, d, n, m, gated, true) == VFM_OK && plan.quantised();
 }
 
-// queries per workgroup of the coarse kernel that do_search_coarse will launch
-int coarse_qblock(int d) { return d > 512 ? 128 : QBLOCK; }
-
-CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m, int qblock) {
+CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m) {
     const int64_t npad = rows_padded(n), mpad = rows_padded(m);
     CoarseArgs a;
     a.Qh = Q.tiles;
@@ -104,13 +99,12 @@ CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, 
     a.nchunks = (int)(mpad / CHUNK_ROWS);
     a.m_valid = m;
     a.npad = (int)npad;
-    a.nqb = (int)(npad / qblock);
-    a.nslices = choose_slices(a.nqb, a.nchunks);
+    a.nqb = a.nslices = 0;   // (launch_coarse)
     a.qmax = w.qmax;
     a.first_pad_chunk = (int)(m / CHUNK_ROWS);
     a.row_bias = nullptr;
     a.qinv = Q.inv;
-    a.seed_parts = a.seed_chunks = a.nseed_pad = 0;
+    a.seed_parts = a.seed_chunks = a.nseed_pad = a.tune = 0;
     a.rec_cnt = nullptr;
     a.rec = nullptr;
     a.rcap = 0;
@@ -129,27 +123,20 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
     SearchPlan plan;
     VFM_TRY(resolve_search(plan, records, d, n, m, gated, inner_product));
     VFM_TRY(check_plan_gate(plan.fused, gate, "search_coarse"));
+    CoarseLaunch launch;
+    VFM_TRY(resolve_coarse(launch, plan, d, n, m, bias_from_map_inv, vfm_compute_units()));
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
-    CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
-    if (bias_from_map_inv) {  // Euclidean search, d > 510: the map's "inv" array holds -|b~|^2 / 2
-        if (d != 640 && d != 768) return vfm_fail(VFM_EINVAL, "row bias needs the 4-wave coarse kernel (K = 640 / 768), got %d", d);
-        a.row_bias = B.inv;
-    }
+    CoarseArgs a = coarse_args(Q, B, w, n, m);
+    if (bias_from_map_inv) a.row_bias = B.inv;  // Euclidean search, d > 510: the map's "inv" array holds -|b~|^2 / 2
     if (plan.pass == PASS_F16_SPARSE) {
         a.rec_cnt = w.rec_cnt;
         a.rec = w.rec;
         a.rcap = w.rcap;
-        if (vfm_cfg().seed_units && a.nchunks >= 256 && a.nqb <= 256) {  // seed units: one short round at the head of the grid
-            a.seed_parts = 256 / a.nqb < 4 ? 256 / a.nqb : 4;
-            a.seed_chunks = 5;
-            a.nseed_pad = (a.nqb * a.seed_parts + 7) / 8 * 8;
-            a.nslices = choose_slices(a.nqb, a.nchunks - a.seed_parts * a.seed_chunks);
-        }
     }
     if (!ws_clean) VFM_CHECK_HIP(hipMemsetAsync(w.fb_count, 0, search_zero_bytes(n, m), st));  // fb_count | qmax | rec_cnt | bin_cnt
-    if (!plan.quantised()) return launch_coarse_f16(a, d, st);
+    if (!plan.quantised()) return launch_coarse(launch, a, st);
     if (plan.fused) {
         a.gate = gate;
         a.n_valid = n;
@@ -170,11 +157,11 @@ int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m,
         a.Qh = Q.tiles6;
         a.Bh = B.tiles6;
         if (plan.pilot) a.qbest = w.qbest;   // the full-width pass also notes every query's best chunk
-        return launch_coarse_mx6(a, d, plan.top2, plan.half, plan.fused, st);
+    } else {
+        a.Qh = plan.half ? Q.tiles8h : Q.tiles8;   // (half: the image of the first d / 2 columns)
+        a.Bh = plan.half ? B.tiles8h : B.tiles8;
     }
-    a.Qh = plan.half ? Q.tiles8h : Q.tiles8;   // (half: the image of the first d / 2 columns)
-    a.Bh = plan.half ? B.tiles8h : B.tiles8;
-    return launch_coarse_int8(a, d, n, plan.kind, st);
+    return launch_coarse(launch, a, st);
 }
 
 }  // namespace vfmm
@@ -487,8 +474,8 @@ VFM_EXPORT int vfm_debug_mx6_half_err(const void* prepared, int64_t rows, int d,
     return VFM_OK;
 }
 
-// The coarse kernel most recently launched from the calling thread, as its launcher instantiation spells itself ("" if none), and the
-// sorted, newline-separated list of every such name in the library.  Host memory only.
+// The coarse kernel most recently launched from the calling thread, as its instantiation spells itself ("" if none), and the sorted,
+// newline-separated list of every such name in the library.  Host memory only.
 static int copy_out(const std::string& s, char* buf_host, int cap, const char* what) {
     VFM_CHECK_ARG(buf_host && cap > 0, "%s: null buffer", what);
     if ((size_t)cap <= s.size()) return vfm_fail(VFM_EINVAL, "%s: the buffer holds %d bytes, the answer needs %zu", what, cap, s.size() + 1);
@@ -496,15 +483,33 @@ static int copy_out(const std::string& s, char* buf_host, int cap, const char* w
     return VFM_OK;
 }
 VFM_EXPORT int vfm_debug_last_coarse_kernel(char* buf_host, int cap) {
-    return copy_out(g_last_coarse_kernel ? g_last_coarse_kernel->name : "", buf_host, cap, "last_coarse_kernel");
+    return copy_out(g_last_coarse < 0 ? std::string() : coarse_inst_name(g_last_coarse / 2, g_last_coarse & 1), buf_host, cap, "last_coarse_kernel");
 }
 VFM_EXPORT int vfm_debug_coarse_kernel_names(char* buf_host, int cap) {
     std::vector<std::string> names;
-    for (const CoarseKernelName* e = g_coarse_kernel_names; e; e = e->next) names.push_back(e->name);
+    for (int i = 0; i < CI_COUNT; ++i) {
+        names.push_back(coarse_inst_name(i, false));
+        if (k_coarse_insts[i].family == CF_PIPE && k_coarse_insts[i].a[1]) names.push_back(coarse_inst_name(i, true));   // sparse: with seed units too
+    }
     std::sort(names.begin(), names.end());
     std::string all;
     for (const std::string& s : names) all += (all.empty() ? "" : "\n") + s;
     return copy_out(all, buf_host, cap, "coarse_kernel_names");
+}
+
+// The launch of a search's coarse pass (match_internal.h, resolve_search + resolve_coarse) as one line of text; a refused combination fails
+// as the search would.
+VFM_EXPORT int vfm_debug_coarse_plan(int records, int d, int64_t n, int64_t m, int gated, int inner_product, int row_bias, int compute_units,
+                                     char* buf_host, int cap) {
+    VFM_CHECK_ARG(n > 0 && m > 0 && d % 128 == 0 && d >= 128 && d <= 768 && compute_units >= 0, "coarse_plan: bad shape (n=%lld m=%lld d=%d)", (long long)n, (long long)m, d);
+    SearchPlan plan;
+    VFM_TRY(resolve_search(plan, records, d, n, m, gated != 0, inner_product != 0));
+    CoarseLaunch l;
+    VFM_TRY(resolve_coarse(l, plan, d, n, m, row_bias != 0, compute_units ? compute_units : vfm_compute_units()));
+    const std::string line = "kernel=" + coarse_inst_name(l.inst, l.seeded) + " nqb=" + std::to_string(l.nqb) + " nslices=" + std::to_string(l.nslices) +
+                             " seed=" + std::to_string(l.nseed_pad) + " block=" + std::to_string(l.block) + " lds=" + std::to_string(l.lds) +
+                             " tune=" + std::to_string(l.tune);
+    return copy_out(line, buf_host, cap, "coarse_plan");
 }
 
 // The plan of a preparation (match_internal.h, resolve_prepare) as one line of text; a refused combination fails as the entry would.

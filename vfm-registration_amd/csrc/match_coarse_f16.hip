@@ -586,95 +586,21 @@ __global__ __launch_bounds__(256, 1) void match_coarse_r_kernel(CoarseArgs a) {
 
 }  // namespace
 
-// the launchers' names (match_internal.h, CoarseKernelName).  The sparse pipelined kernel has two: with and without seed units at the head
-// of its grid (a launch argument, not a template one -- but a different grid and a different first round)
-template <int KSTEPS, bool SPARSE>
-CoarseKernelName k_pipe_name{"pipe<%d,%s>", KSTEPS, SPARSE ? "sparse" : "dense"};
-template <int KSTEPS>
-CoarseKernelName k_pipe_seeded_name{"pipe<%d,sparse>+seed", KSTEPS};
-template <int KSTEPS, int QSETS>
-CoarseKernelName k_v_name{"v<%d,qsets=%d>", KSTEPS, QSETS};
-template <int KSTEPS, int QSETS, int NBUF, bool BIAS>
-CoarseKernelName k_r_name{"r<%d,qsets=%d,nbuf=%d,bias=%d>", KSTEPS, QSETS, NBUF, (int)BIAS};
-
-template <int KSTEPS, bool SPARSE>
-int launch_coarse_pipe(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_pipe_name<KSTEPS, SPARSE>;
-    if constexpr (SPARSE) {
-        if (a.nseed_pad) g_last_coarse_kernel = &k_pipe_seeded_name<KSTEPS>;
+// the fp16 instantiations (match_internal.h: the lists every name of one is generated from), through the frame in match_api.hip
+int launch_coarse_f16(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st) {
+    switch ((CoarseInst)l.inst) {
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_pipe_kernel<__VA_ARGS__>, "match_coarse_kernel", l, a, st);
+        VFM_COARSE_PIPE_INSTS(X)
+#undef X
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_kernel<__VA_ARGS__>, "match_coarse_kernel", l, a, st);
+        VFM_COARSE_V_INSTS(X)
+#undef X
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_r_kernel<__VA_ARGS__>, "match_coarse_r_kernel", l, a, st);
+        VFM_COARSE_R_INSTS(X)
+#undef X
+        VFM_COARSE_INSTS_I8(VFM_CI_CASE) VFM_COARSE_MX6_INSTS(VFM_CI_CASE) case CI_COUNT: break;   // (the other files')
     }
-    const int lds = 6 * KSTEPS * 1024 + (SPARSE ? SPARSE_LREC_CAP * 8 + 16 : 0);
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_pipe_kernel<KSTEPS, SPARSE>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
-    }
-    hipLaunchKernelGGL((match_coarse_pipe_kernel<KSTEPS, SPARSE>), dim3(a.nseed_pad + a.nqb * a.nslices), dim3(512), lds, st, a);
-    return VFM_OK;
-}
-
-template <int KSTEPS, int QSETS>
-int launch_coarse_v(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_v_name<KSTEPS, QSETS>;
-    const int lds = ring_depth(KSTEPS) * KSTEPS * 1024;
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_kernel<KSTEPS, QSETS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
-    }
-    hipLaunchKernelGGL((match_coarse_kernel<KSTEPS, QSETS>), dim3(a.nqb * a.nslices), dim3(512 / QSETS), lds, st, a);
-    return VFM_OK;
-}
-
-template <int KSTEPS, int QSETS, int NBUF, bool BIAS>
-int launch_coarse_r(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_r_name<KSTEPS, QSETS, NBUF, BIAS>;
-    const int lds = NBUF * KSTEPS * 1024;
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_r_kernel<KSTEPS, QSETS, NBUF, BIAS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
-    }
-    if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
-    hipLaunchKernelGGL((match_coarse_r_kernel<KSTEPS, QSETS, NBUF, BIAS>), dim3(a.nqb * a.nslices), dim3(256), lds, st, a);
-    VFM_CHECK_LAUNCH("match_coarse_r_kernel");
-    if (g_prof_stop) VFM_CHECK_HIP(hipEventRecord(g_prof_stop, st));
-    g_prof_start = g_prof_stop = nullptr;
-    return VFM_OK;
-}
-
-template <int KSTEPS>
-int launch_coarse(const CoarseArgs& a, hipStream_t st) {
-    if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
-    int rc;
-    if constexpr (KSTEPS <= 24) {
-        rc = (vfm_cfg().coarse_qsets == 2)   ? launch_coarse_v<KSTEPS, 2>(a, st)
-             : (vfm_cfg().coarse_qsets == 1) ? launch_coarse_v<KSTEPS, 1>(a, st)
-                                     : (a.rec ? launch_coarse_pipe<KSTEPS, true>(a, st) : launch_coarse_pipe<KSTEPS, false>(a, st));  // 0, 3
-    } else {
-        rc = launch_coarse_v<KSTEPS, 1>(a, st);  // d = 512: 2 x 128 query VGPRs would not fit
-    }
-    if (rc) return rc;
-    VFM_CHECK_LAUNCH("match_coarse_kernel");
-    if (g_prof_stop) VFM_CHECK_HIP(hipEventRecord(g_prof_stop, st));
-    g_prof_start = g_prof_stop = nullptr;
-    return VFM_OK;
-}
-
-// the fp16 coarse kernel for the arguments do_search_coarse prepared (d in {128, ..., 768})
-int launch_coarse_f16(const CoarseArgs& a, int d, hipStream_t st) {
-    switch (d / 16) {
-        case 8: return launch_coarse<8>(a, st);
-        case 16: return launch_coarse<16>(a, st);
-        case 24: return launch_coarse<24>(a, st);
-        case 32: return launch_coarse<32>(a, st);  // 8-wave kernel, ring of 4: 3.45 ms at C2 x 512 (4-wave kernel: 4.42 ms)
-        case 40: return a.row_bias ? launch_coarse_r<40, 1, 3, true>(a, st) : launch_coarse_r<40, 1, 3, false>(a, st);
-        case 48: return a.row_bias ? launch_coarse_r<48, 1, 3, true>(a, st) : launch_coarse_r<48, 1, 3, false>(a, st);
-        default: return vfm_fail(VFM_EINVAL, "FAST matching supports d in {128,256,384,512,640,768}, got %d", d);
-    }
+    return vfm_fail(VFM_EINVAL, "launch_coarse: instantiation %d is not an fp16 kernel", l.inst);
 }
 
 }  // namespace vfmm

@@ -360,95 +360,18 @@ __global__ __launch_bounds__(512, 2) void match_coarse_i8q2_kernel(CoarseArgs a)
 
 }  // namespace
 
-// the launchers' names (match_internal.h, CoarseKernelName)
-template <int KSTEPS, int T, bool TOP2, bool LOW>
-CoarseKernelName k_i8_name{"i8<%d,T=%d,top2=%d,low=%d>", KSTEPS, T, (int)TOP2, (int)LOW};
-template <int KSTEPS, bool TOP2, bool LOW, bool FUSE>
-CoarseKernelName k_i8q2_name{"i8q2<%d,top2=%d,low=%d,fused=%d>", KSTEPS, (int)TOP2, (int)LOW, (int)FUSE};
-
-template <int KSTEPS, int T, bool TOP2 = false, bool LOW = true>
-int launch_coarse_i8(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_i8_name<KSTEPS, T, TOP2, LOW>;
-    const int lds = 3 * T * KSTEPS * 1024;
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_i8_kernel<KSTEPS, T, TOP2, LOW>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
+// the int8 instantiations (match_internal.h: the lists every name of one is generated from), through the frame in match_api.hip
+int launch_coarse_int8(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st) {
+    switch ((CoarseInst)l.inst) {
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_i8_kernel<__VA_ARGS__>, "match_coarse_i8_kernel", l, a, st);
+        VFM_COARSE_I8_INSTS(X)
+#undef X
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_i8q2_kernel<__VA_ARGS__>, "match_coarse_i8_kernel", l, a, st);
+        VFM_COARSE_I8Q2_INSTS(X)
+#undef X
+        VFM_COARSE_INSTS_F16(VFM_CI_CASE) VFM_COARSE_MX6_INSTS(VFM_CI_CASE) case CI_COUNT: break;   // (the other files')
     }
-    hipLaunchKernelGGL((match_coarse_i8_kernel<KSTEPS, T, TOP2, LOW>), dim3(a.nqb * a.nslices), dim3(512), lds, st, a);
-    return VFM_OK;
-}
-
-template <int KSTEPS, bool TOP2, bool LOW = true, bool FUSE = false>
-int launch_coarse_i8q2(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_i8q2_name<KSTEPS, TOP2, LOW, FUSE>;
-    const int lds = 12 * KSTEPS * 1024;
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_i8q2_kernel<KSTEPS, TOP2, LOW, FUSE>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
-    }
-    hipLaunchKernelGGL((match_coarse_i8q2_kernel<KSTEPS, TOP2, LOW, FUSE>), dim3(a.nqb * a.nslices), dim3(512), lds, st, a);
-    return VFM_OK;
-}
-
-
-// the int8 coarse kernel for the arguments do_search_coarse prepared; sets the query-block / slice split of the shape it picks
-int launch_coarse_int8(CoarseArgs& a, int d, int64_t n, int records, hipStream_t st) {
-    a.nqb = (int)(rows_padded(n) / QBLOCK);  // 8 waves x 32 queries at every width
-    a.nslices = choose_slices(a.nqb, a.nchunks);
-    if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
-    const bool top2 = records == VFM_RECORDS_TOP2;
-    int rc8;
-    if (records == VFM_RECORDS_HALF_FUSED) {   // d = 256 / 384, more than 2048 queries (resolve_search)
-        a.nqb = (a.nq_tiles + 15) / 16;
-        a.nslices = choose_slices(a.nqb, a.nchunks);
-        rc8 = d == 384 ? launch_coarse_i8q2<6, false, false, true>(a, st) : launch_coarse_i8q2<4, false, false, true>(a, st);
-    } else if (records == VFM_RECORDS_HALF) {
-        // the half-width pass: the same kernels on the image of the first d / 2 columns (a.Qh / a.Bh = tiles8h), best-score records
-        if (n > 2048 && vfm_cfg().coarse_qsets == 0) {   // 64 resident queries per wave at every width: d / 2 columns are at most 384
-            a.nqb = (a.nq_tiles + 15) / 16;
-            a.nslices = choose_slices(a.nqb, a.nchunks);
-            switch (d / 64) {
-                case 4: rc8 = launch_coarse_i8q2<4, false, false>(a, st); break;
-                case 6: rc8 = launch_coarse_i8q2<6, false, false>(a, st); break;
-                case 8: rc8 = launch_coarse_i8q2<8, false, false>(a, st); break;
-                case 10: rc8 = launch_coarse_i8q2<10, false, false>(a, st); break;
-                default: rc8 = launch_coarse_i8q2<12, false, false>(a, st); break;
-            }
-        } else {   // one query set per wave: few queries (variants 10 / 12: every size, A/B)
-            switch (d / 64) {
-                case 4: rc8 = launch_coarse_i8<4, 4, false, false>(a, st); break;
-                case 6: rc8 = launch_coarse_i8<6, 4, false, false>(a, st); break;
-                case 8: rc8 = launch_coarse_i8<8, 4, false, false>(a, st); break;
-                case 10: rc8 = launch_coarse_i8<10, 4, false, false>(a, st); break;
-                default: rc8 = launch_coarse_i8<12, 4, false, false>(a, st); break;
-            }
-        }
-    } else if (d <= 384 && n > 2048 && vfm_cfg().coarse_qsets == 0) {
-        // 64 resident queries per wave: 11-15 % faster than the one-set kernel from ~3000 queries on (C2: 1.09 vs 1.23 ms;
-        // 1500 x 100 000: 0.059 vs 0.056 ms -- half as many, twice as large workgroups); variants 10 / 12 = one set, A/B
-        a.nqb = (a.nq_tiles + 15) / 16;
-        a.nslices = choose_slices(a.nqb, a.nchunks);
-        rc8 = d == 384 ? (top2 ? launch_coarse_i8q2<12, true>(a, st) : launch_coarse_i8q2<12, false>(a, st))
-                       : (top2 ? launch_coarse_i8q2<8, true>(a, st) : launch_coarse_i8q2<8, false>(a, st));
-    } else {
-        const bool t2 = vfm_cfg().coarse_qsets == 10;  // variant 10 (A/B): 2 tiles per step at every width
-        switch (d / 32) {
-            case 8: rc8 = top2 ? launch_coarse_i8<8, 4, true>(a, st) : t2 ? launch_coarse_i8<8, 2>(a, st) : launch_coarse_i8<8, 4>(a, st); break;
-            case 12: rc8 = top2 ? launch_coarse_i8<12, 4, true>(a, st) : t2 ? launch_coarse_i8<12, 2>(a, st) : launch_coarse_i8<12, 4>(a, st); break;
-            case 16: rc8 = top2 ? launch_coarse_i8<16, 2, true>(a, st) : launch_coarse_i8<16, 2>(a, st); break;
-            case 20: rc8 = top2 ? launch_coarse_i8<20, 2, true>(a, st) : launch_coarse_i8<20, 2>(a, st); break;
-            default: rc8 = top2 ? launch_coarse_i8<24, 2, true>(a, st) : launch_coarse_i8<24, 2>(a, st); break;
-        }
-    }
-    if (rc8) return rc8;
-    VFM_CHECK_LAUNCH("match_coarse_i8_kernel");
-    if (g_prof_stop) VFM_CHECK_HIP(hipEventRecord(g_prof_stop, st));
-    g_prof_start = g_prof_stop = nullptr;
-    return VFM_OK;
+    return vfm_fail(VFM_EINVAL, "launch_coarse: instantiation %d is not an int8 kernel", l.inst);
 }
 
 }  // namespace vfmm

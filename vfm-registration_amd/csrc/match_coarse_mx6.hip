@@ -80,10 +80,7 @@ __device__ __forceinline__ float fmax_halves(float v) {
     return fmaxf(__uint_as_float((unsigned)sw[0]), __uint_as_float((unsigned)sw[1]));
 }
 
-enum { MX6_BEST = 0, MX6_TOP2 = 1, MX6_FUSE = 2 };
-constexpr int MX6_LTAB = 256;       // per-chunk constants of a workgroup's slice kept in the LDS (launch_coarse_mx6 keeps slices this short)
-constexpr int MX6_LCAP = 2047;      // FUSE: survivors a workgroup can list (+ the header = 8 KiB)
-
+// (MX6_BEST / _TOP2 / _FUSE, MX6_LTAB and MX6_LCAP: match_internal.h -- the launch plan reads them too)
 // KIND: MX6_BEST best-score records, MX6_TOP2 packed top-2 records (VFM_RECORDS_MX6_TOP2: the accumulators then start at 2.0 --
 // scores of unit rows stay in [0.9, 3.1], positive floats whose bit patterns order like the values, and coarse_fold -- the fp16
 // pass's: low six bits replaced by the row code, running best / second best by max / med3 -- works on them as it stands; at the
@@ -536,105 +533,18 @@ __global__ __launch_bounds__(512, 2) void match_coarse_mx6q2_kernel(CoarseArgs a
 #endif   // __HIP_DEVICE_COMPILE__
 }
 
-// the launcher's names (match_internal.h, CoarseKernelName)
-template <int KS6, int KIND, bool LOW, int IMG_KS6, int RING, int T, int NS>
-CoarseKernelName k_mx6q2_name{"mx6q2<%d,%s,low=%d,img=%d,ring=%d,T=%d,NS=%d>", KS6, KIND == MX6_FUSE ? "FUSE" : KIND == MX6_TOP2 ? "TOP2" : "BEST",
-                              (int)LOW, IMG_KS6, RING, T, NS};
-
-template <int KS6, int KIND, bool LOW, int IMG_KS6, int RING, int T = 4, int NS = 2>
-int launch_mx6q2(const CoarseArgs& a, hipStream_t st) {
-    g_last_coarse_kernel = &k_mx6q2_name<KS6, KIND, LOW, IMG_KS6, RING, T, NS>;
-    constexpr int LT = MX6_SCALE_PLANE + KS6 * MX6_KSTEP_BYTES;
-    constexpr int LCAP = RING * T * LT + MX6_LTAB * 8 + (MX6_LCAP + 1) * 4 <= 160 * 1024 ? MX6_LCAP : 1023;
-    const int lds = RING * T * LT + MX6_LTAB * 8 + (KIND == MX6_FUSE ? (LCAP + 1) * 4 : 0);
-    static unsigned long long attr_set = 0ull;  // one bit per device
-    if (!attr_done(attr_set)) {
-        VFM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_coarse_mx6q2_kernel<KS6, KIND, LOW, IMG_KS6, RING, T, NS>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_mark(attr_set);
-    }
-    hipLaunchKernelGGL((match_coarse_mx6q2_kernel<KS6, KIND, LOW, IMG_KS6, RING, T, NS>), dim3(a.nqb * a.nslices), dim3(512), lds, st, a);
-    return VFM_OK;
-}
-
 }  // namespace
 
-static_assert(MX6_LCAP + 1 + 3 == MX6_SURV_SLOT_WORDS, "carve_search sizes the slots");
-int mx6_survivor_slot_words() { return MX6_SURV_SLOT_WORDS; }
-
-// the fp6 coarse kernel for the arguments do_search_coarse prepared (a.Qh / a.Bh = the fp6 tiles, a.ib = mx6_bounds);
-// d = 256 / 384 (full width) or 256 / 384 / 512 / 768 (half width) and more than 2048 queries (resolve_search)
-int launch_coarse_mx6(CoarseArgs& a, int d, bool top2, bool half, bool fuse, hipStream_t st) {
-    const bool ns3 = half && fuse && d == 384 && vfm_cfg().mx6_ns3 && vfm_cfg().mx6_t4;
-    a.nqb = ns3 ? (a.nq_tiles + 23) / 24 : (a.nq_tiles + 15) / 16;
-    a.nslices = choose_slices(a.nqb, a.nchunks);
-    if (half && vfm_cfg().force_slices == 0) {
-        // the half-width kernel's workgroups are short, and shorter ones let the other stages of a pipeline in: ~7.5 rounds of 256
-        // workgroups instead of choose_slices' 5 (tools/sweep_slices.py, C2, 200 steps: 48 slices 1548 against 32 slices 1475
-        // registrations/s; the full-width fp6 kernel and the int8 kernels are flat from 32 on)
-        int s = (int)((1600 + a.nqb - 1) / a.nqb);   // (round 4, tools/sweep_slices_r4.py, fused kernel: 40 / 44 slices 1764 / 1762, 48: 1740, 57: 1690 registrations/s over 200 steps)
-        const int smax = a.nchunks / 8 < 64 ? a.nchunks / 8 : 64;
-        s = s > smax ? smax : s;
-        s = s < 1 ? 1 : s;
-        // Round 6: the workgroups are equal and a compute unit holds one, so the kernel lasts ceil(workgroups / units) rounds whatever the last
-        // round holds (tools/sweep_slices_r6.py, the kernel alone at C2, 27 query blocks: 60 slices = 6.33 rounds 0.388 ms; 56 = 5.9 rounds
-        // 0.370; 47 = 4.96 rounds 0.367; 19 slices = 2.004 rounds 0.445).  Near the count above, take the slice count whose last round is
-        // (almost) full -- at most 4 above, 12 below; in the pipeline 56 against 60 is +1 % over 200 steps, even in the 20-step form.
-        {
-            const int cus = vfm_compute_units();
-            int best = s;
-            double best_fill = 0.0;
-            for (int t = (s + 4 < smax ? s + 4 : smax); t >= 1 && t >= s - 12; --t) {
-                const long long wg = (long long)a.nqb * t, rounds = (wg + cus - 1) / cus;
-                const double fill = (double)wg / (double)(rounds * cus);
-                if (fill >= 0.975) {   // the largest such count (short workgroups let the pipeline's other stages in)
-                    best = t;
-                    best_fill = 2.0;
-                    break;
-                }
-                if (fill > best_fill) {
-                    best_fill = fill;
-                    best = t;
-                }
-            }
-            s = best;
-        }
-        a.nslices = s < 1 ? 1 : s;
+// the fp6 instantiations (match_internal.h: the lists every name of one is generated from), through the frame in match_api.hip;
+// a.Qh / a.Bh = the fp6 tiles, a.ib = mx6_bounds
+int launch_coarse_mx6(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st) {
+    switch ((CoarseInst)l.inst) {
+#define X(family, ...) VFM_CI_CASE(family, __VA_ARGS__) return launch_coarse_kernel(match_coarse_mx6q2_kernel<__VA_ARGS__>, "match_coarse_mx6q2_kernel", l, a, st);
+        VFM_COARSE_MX6_INSTS(X)
+#undef X
+        VFM_COARSE_INSTS_F16(VFM_CI_CASE) VFM_COARSE_INSTS_I8(VFM_CI_CASE) case CI_COUNT: break;   // (the other files')
     }
-    while ((a.nchunks + a.nslices - 1) / a.nslices + 1 > MX6_LTAB && a.nslices < a.nchunks) ++a.nslices;   // a slice's constants fit the LDS table
-    const int slices_cap = a.nchunks / 8 < 1 ? 1 : (a.nchunks / 8 > 64 ? 64 : a.nchunks / 8), slices_tab = (a.nchunks + 254) / 255;
-    if (fuse && (a.nqb > a.npad / 512 + 1 || a.nslices > (slices_cap > slices_tab ? slices_cap : slices_tab)))   // (what carve_search sized the slots for)
-        return vfm_fail(VFM_EINVAL, "search_coarse: %d x %d survivor slots exceed the workspace (n %d chunks %d)", a.nqb, a.nslices, a.npad, a.nchunks);
-    if (g_prof_start) VFM_CHECK_HIP(hipEventRecord(g_prof_start, st));
-    int rc;
-    // Two chunks per barrier (T = 8, ring of 3 x 8 tiles: 84 / 120 KiB at d = 256 / 384) is built, parity-tested and measured: 0.415 ms
-    // against 0.419 alone, 1715 against 1725 registrations/s in the pipeline (tools/ab_r4.py) -- the barrier share the ablations
-    // show (tools/ablate6.py: -10 % without barrier and staging) does not come back by halving the barriers, and the larger ring
-    // leaves the side kernels less LDS.  One chunk per barrier stays the default; vfm_debug_set_coarse_variant(31) selects T = 8.
-    const bool t8 = half && fuse && (d == 384 || d == 256) && !vfm_cfg().mx6_t4 && a.nslices <= a.nchunks / 2;
-    a.tune = vfm_cfg().mx6_tune;
-    if (ns3 && (vfm_cfg().mx6_tune & 2))   // (A/B) a ring of five steps
-        rc = launch_mx6q2<3, MX6_FUSE, false, 6, 5, 4, 3>(a, st);
-    else if (ns3)   // three query tiles per wave: 768 queries per workgroup (nqb set above)
-        rc = launch_mx6q2<3, MX6_FUSE, false, 6, 4, 4, 3>(a, st);
-    else if (fuse && !half)   // VFM_RECORDS_MX6_FUSED: the full-width pass with the gate test in its epilogue
-        rc = d == 384 ? launch_mx6q2<6, MX6_FUSE, false, 6, 4>(a, st) : launch_mx6q2<4, MX6_FUSE, false, 4, 4>(a, st);
-    else if (half && fuse && t8)
-        rc = d == 384 ? launch_mx6q2<3, MX6_FUSE, false, 6, 3, 8>(a, st) : launch_mx6q2<2, MX6_FUSE, false, 4, 3, 8>(a, st);
-    else if (half && fuse)
-        rc = d == 768 ? launch_mx6q2<6, MX6_FUSE, false, 12, 4>(a, st) : d == 512 ? launch_mx6q2<4, MX6_FUSE, false, 8, 4>(a, st)
-           : d == 384 ? launch_mx6q2<3, MX6_FUSE, false, 6, 4>(a, st) : launch_mx6q2<2, MX6_FUSE, false, 4, 4>(a, st);
-    else if (half)
-        rc = d == 768 ? launch_mx6q2<6, MX6_BEST, false, 12, 4>(a, st) : d == 512 ? launch_mx6q2<4, MX6_BEST, false, 8, 4>(a, st)
-           : d == 384 ? launch_mx6q2<3, MX6_BEST, false, 6, 4>(a, st) : launch_mx6q2<2, MX6_BEST, false, 4, 4>(a, st);
-    else
-        rc = d == 384 ? (top2 ? launch_mx6q2<6, MX6_TOP2, true, 6, 4>(a, st) : launch_mx6q2<6, MX6_BEST, true, 6, 4>(a, st))
-                      : (top2 ? launch_mx6q2<4, MX6_TOP2, true, 4, 4>(a, st) : launch_mx6q2<4, MX6_BEST, true, 4, 4>(a, st));
-    if (rc) return rc;
-    VFM_CHECK_LAUNCH("match_coarse_mx6q2_kernel");
-    if (g_prof_stop) VFM_CHECK_HIP(hipEventRecord(g_prof_stop, st));
-    g_prof_start = g_prof_stop = nullptr;
-    return VFM_OK;
+    return vfm_fail(VFM_EINVAL, "launch_coarse: instantiation %d is not an fp6 kernel", l.inst);
 }
 
 }  // namespace vfmm

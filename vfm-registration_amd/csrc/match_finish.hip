@@ -1991,7 +1991,7 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
-    const CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
+    const CoarseArgs a = coarse_args(Q, B, w, n, m);
     const float w2 = 2.0f * (float)(d / 16 + 4 + 2) * 5.9604645e-8f;
     const bool i8 = plan.quantised(), half = plan.gate_test, use_bins = plan.use_bins;
     // records of the fp6 pass: its own bounds in the selection; behind it the int8 image and bounds, as for the int8 kinds
@@ -2018,7 +2018,7 @@ int do_search_finish(Rows q, const void* qprep, int64_t n, Rows b, const void* b
                 break;
             case FIN_BIN_SURVIVORS:
                 hipLaunchKernelGGL(match_bin_survivors_kernel, dim3(256), dim3(256), 0, st, reinterpret_cast<const unsigned*>(w.partials),
-                                   mx6_survivor_slot_words(), (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
+                                   MX6_SURV_SLOT_WORDS, (const int*)w.fb_count, w.bin_cnt, w.bins, w.bin_cap, w.cand_cnt, w.cand, w.cap);
                 break;
             case FIN_SELECT_HALF: {
                 const int half_lds = (size_t)a.nchunks * 12 <= 63 * 1024;  // (step, max E, max |rest|) of every chunk in LDS
@@ -2147,7 +2147,7 @@ int probe_half_select(const SearchPlan& plan, const void* qprep, int64_t n, cons
     Prepared Q = carve_prepared(const_cast<void*>(qprep), n, d);
     Prepared B = carve_prepared(const_cast<void*>(bprep), m, d);
     SearchWs w = carve_search(ws, n, m);
-    const CoarseArgs a = coarse_args(Q, B, w, n, m, coarse_qblock(d));
+    const CoarseArgs a = coarse_args(Q, B, w, n, m);
     const int half_lds = (size_t)a.nchunks * 12 <= 63 * 1024;
     hipLaunchKernelGGL(match_select_half_kernel, dim3((unsigned)a.nq_tiles), dim3(64 * 8), half_lds ? (size_t)a.nchunks * 12 : 0, st,
                        reinterpret_cast<const unsigned*>(w.partials), a.nchunks, n, Q.inv, plan_bounds(plan, Q, B),

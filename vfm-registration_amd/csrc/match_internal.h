@@ -51,7 +51,10 @@ constexpr int RESCAN_SLICE = 256;    // bin entries one workgroup of match_resca
 // SearchWs::fb_count[7] is the flag (half_guard_kernel); the host policy (vfmreg/pipeline.py) leaves the mode on the same figure.
 constexpr int HALF_GUARD_PER_QUERY = 48;
 constexpr int HALF_GUARD_FLAG = 7;   // index into fb_count
-constexpr int MX6_SURV_SLOT_WORDS = 2047 + 4;   // fused fp6 half-width pass: a workgroup's survivor slot = header (4 words) + up to 2047 entries
+enum { MX6_BEST = 0, MX6_TOP2 = 1, MX6_FUSE = 2 };   // KIND of match_coarse_mx6q2_kernel
+constexpr int MX6_LTAB = 256;       // per-chunk constants of a workgroup's slice kept in the LDS (resolve_coarse keeps slices this short)
+constexpr int MX6_LCAP = 2047;      // FUSE: survivors a workgroup can list (+ the header = 8 KiB)
+constexpr int MX6_SURV_SLOT_WORDS = MX6_LCAP + 4;   // fused fp6 half-width pass: a workgroup's survivor slot = header (4 words) + up to MX6_LCAP entries
 constexpr int MX6_GRID_SLOT = 32;    // fb_count[.]: workgroups of the fused fp6 half-width kernel = survivor slots match_bin_survivors_kernel walks
 constexpr int FUSE_BIN_SATURATE_X = 8;  // fused form: a chunk that collected this many times its bin capacity stops recording (and raises the flag)
 constexpr int FILTER_LDS_ROWS = 1024;  // sparse fp16 records a query can hold (= SearchWs::rcap; match_filter_refine_kernel keeps them in LDS)
@@ -244,7 +247,7 @@ struct CoarseArgs {
     int* survivors;         // fb_count + 5: the search's load figure
     unsigned long long* qbest;   // VFM_RECORDS_MX6_PILOT: [npad] (float_key(lower bound) << 32 | chunk) of the query's best chunk, by 64-bit atomicMax (NULL: not kept)
     int tune;               // (A/B, vfm_config "mx6_tune") bit 0: waves 4 - 7 of a workgroup of the fp6 kernel at s_setprio 1; bit 2: absent query sets are multiplied (as copies of tile 0)
-    unsigned* surv;         // VFM_RECORDS_MX6_HALF_FUSED / _MX6_FUSED: a slot of mx6_survivor_slot_words() words per workgroup (in the record buffer)
+    unsigned* surv;         // VFM_RECORDS_MX6_HALF_FUSED / _MX6_FUSED: a slot of MX6_SURV_SLOT_WORDS words per workgroup (in the record buffer)
 };
 
 // XCD-aware unit mapping shared by the coarse kernels: workgroup b runs on XCD b % 8 (observed, speed
@@ -482,17 +485,24 @@ struct SearchWs {
     size_t bytes;
 };
 
+// The survivor slots of the fused fp6 kinds, one per workgroup: the most map slices and the most query blocks the record buffer is sized
+// for.  carve_search sizes it by them and resolve_coarse refuses a launch beyond them.
+inline int64_t surv_slot_slices(int64_t nchunks) {
+    const int64_t slices = nchunks / 8 < 1 ? 1 : (nchunks / 8 > 64 ? 64 : nchunks / 8);   // at most min(64, chunks / 8) slices, at least one
+    const int64_t tab = (nchunks + 254) / 255;   // (a slice's per-chunk constants fit the kernel's LDS table: <= 255 chunks)
+    return slices < tab ? tab : slices;
+}
+inline int64_t surv_slot_qblocks(int64_t npad) { return npad / 512 + 1; }
+
 inline SearchWs carve_search(void* p, int64_t n, int64_t m) {
     VfmCarver c(p);
     SearchWs w;
     const int64_t npad = rows_padded(n), mpad = rows_padded(m);
     // the records of a coarse pass: per (chunk, query) 8 bytes -- or, for the fused fp6 half-width pass (which writes none), one slot
-    // of MX6_SURV_SLOT_WORDS words per workgroup: (npad / 512 query blocks) x (at most min(64, chunks / 8) slices, at least one)
+    // of MX6_SURV_SLOT_WORDS words per workgroup: surv_slot_qblocks x surv_slot_slices of them
     {
         const size_t nch = (size_t)(mpad / CHUNK_ROWS);
-        size_t slices = nch / 8 < 1 ? 1 : (nch / 8 > 64 ? 64 : nch / 8);
-        if (slices < (nch + 254) / 255) slices = (nch + 254) / 255;   // (a slice's per-chunk constants fit the kernel's LDS table: <= 255 chunks)
-        const size_t slots = ((size_t)npad / 512 + 1) * slices * (size_t)MX6_SURV_SLOT_WORDS;   // 4-byte words
+        const size_t slots = (size_t)surv_slot_qblocks(npad) * (size_t)surv_slot_slices((int64_t)nch) * (size_t)MX6_SURV_SLOT_WORDS;   // 4-byte words
         const size_t recs = nch * (size_t)npad;                                                  // 8-byte records
         w.partials = c.take<uint2>(recs > (slots + 1) / 2 ? recs : (slots + 1) / 2);
     }
@@ -563,20 +573,97 @@ struct Rows {
 #endif
 };
 
-// experiment knobs and profiling hook (match_api.hip)
-extern thread_local hipEvent_t g_prof_start, g_prof_stop;  // vfm_prof_arm: events around the next coarse launch of this thread
 
-// Which coarse kernel a search ran (include/vfmreg_debug.h: vfm_debug_last_coarse_kernel / vfm_debug_coarse_kernel_names).  Every launcher
-// template of match_coarse_*.hip owns one CoarseKernelName per instantiation -- a variable template beside it, spelled from its template
-// arguments -- and stores its address on every launch: using the variable is what instantiates it, and its constructor (run when the
-// library is loaded) links it into the list the second function prints.  So the list is the set of launcher instantiations in the
-// binary, by construction.  Host side only: one thread-local pointer store per launch, nothing in CoarseArgs, nothing on the device.
-struct CoarseKernelName {
-    char name[56];
-    const CoarseKernelName* next;
-    explicit CoarseKernelName(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// ---------------------------------------------------------------------------------------------
+// The instantiations of the coarse kernels, one list per kernel family, one entry each: X(family, template arguments).  These lists are
+// ALL that names an instantiation: the enum CoarseInst, the table resolve_coarse looks its choice up in, the names of
+// vfm_debug_last_coarse_kernel / _coarse_kernel_names / _coarse_plan (match_api.hip spells them from the arguments) and the switch of each
+// match_coarse_*.hip that turns an enum value into its __global__ function are generated from them -- so a name without a kernel, or a
+// kernel the plan cannot name, does not exist.
+// ---------------------------------------------------------------------------------------------
+// match_coarse_pipe_kernel<KSTEPS, SPARSE>
+#define VFM_COARSE_PIPE_INSTS(X) X(PIPE, 8, false) X(PIPE, 8, true) X(PIPE, 16, false) X(PIPE, 16, true) X(PIPE, 24, false) X(PIPE, 24, true)
+// match_coarse_kernel<KSTEPS, QSETS>
+#define VFM_COARSE_V_INSTS(X) X(V, 8, 1) X(V, 8, 2) X(V, 16, 1) X(V, 16, 2) X(V, 24, 1) X(V, 24, 2) X(V, 32, 1)
+// match_coarse_r_kernel<KSTEPS, QSETS, NBUF, BIAS>
+#define VFM_COARSE_R_INSTS(X) X(R, 40, 1, 3, false) X(R, 40, 1, 3, true) X(R, 48, 1, 3, false) X(R, 48, 1, 3, true)
+// match_coarse_i8_kernel<KSTEPS, T, TOP2, LOW>: the half-width pass (LOW = false), then full width
+#define VFM_COARSE_I8_INSTS(X)                                                                                                         \
+    X(I8, 4, 4, false, false) X(I8, 6, 4, false, false) X(I8, 8, 4, false, false) X(I8, 10, 4, false, false) X(I8, 12, 4, false, false) \
+    X(I8, 8, 2, false, true) X(I8, 8, 4, false, true) X(I8, 8, 4, true, true) X(I8, 12, 2, false, true) X(I8, 12, 4, false, true)       \
+    X(I8, 12, 4, true, true) X(I8, 16, 2, false, true) X(I8, 16, 2, true, true) X(I8, 20, 2, false, true) X(I8, 20, 2, true, true)      \
+    X(I8, 24, 2, false, true) X(I8, 24, 2, true, true)
+// match_coarse_i8q2_kernel<KSTEPS, TOP2, LOW, FUSE>
+#define VFM_COARSE_I8Q2_INSTS(X)                                                                                                   \
+    X(I8Q2, 4, false, false, true) X(I8Q2, 6, false, false, true) X(I8Q2, 4, false, false, false) X(I8Q2, 6, false, false, false)  \
+    X(I8Q2, 8, false, false, false) X(I8Q2, 10, false, false, false) X(I8Q2, 12, false, false, false)                              \
+    X(I8Q2, 8, false, true, false) X(I8Q2, 8, true, true, false) X(I8Q2, 12, false, true, false) X(I8Q2, 12, true, true, false)
+// match_coarse_mx6q2_kernel<KS6, KIND, LOW, IMG_KS6, RING, T, NS>
+#define VFM_COARSE_MX6_INSTS(X)                                                                                                      \
+    X(MX6, 3, MX6_FUSE, false, 6, 5, 4, 3) X(MX6, 3, MX6_FUSE, false, 6, 4, 4, 3)                                                    \
+    X(MX6, 6, MX6_FUSE, false, 6, 4, 4, 2) X(MX6, 4, MX6_FUSE, false, 4, 4, 4, 2)                                                    \
+    X(MX6, 3, MX6_FUSE, false, 6, 3, 8, 2) X(MX6, 2, MX6_FUSE, false, 4, 3, 8, 2)                                                    \
+    X(MX6, 6, MX6_FUSE, false, 12, 4, 4, 2) X(MX6, 4, MX6_FUSE, false, 8, 4, 4, 2) X(MX6, 3, MX6_FUSE, false, 6, 4, 4, 2)            \
+    X(MX6, 2, MX6_FUSE, false, 4, 4, 4, 2)                                                                                           \
+    X(MX6, 6, MX6_BEST, false, 12, 4, 4, 2) X(MX6, 4, MX6_BEST, false, 8, 4, 4, 2) X(MX6, 3, MX6_BEST, false, 6, 4, 4, 2)            \
+    X(MX6, 2, MX6_BEST, false, 4, 4, 4, 2)                                                                                           \
+    X(MX6, 6, MX6_TOP2, true, 6, 4, 4, 2) X(MX6, 6, MX6_BEST, true, 6, 4, 4, 2) X(MX6, 4, MX6_TOP2, true, 4, 4, 4, 2) X(MX6, 4, MX6_BEST, true, 4, 4, 4, 2)
+#define VFM_COARSE_INSTS_F16(X) VFM_COARSE_PIPE_INSTS(X) VFM_COARSE_V_INSTS(X) VFM_COARSE_R_INSTS(X)
+#define VFM_COARSE_INSTS_I8(X) VFM_COARSE_I8_INSTS(X) VFM_COARSE_I8Q2_INSTS(X)
+#define VFM_COARSE_INSTS(X) VFM_COARSE_INSTS_F16(X) VFM_COARSE_INSTS_I8(X) VFM_COARSE_MX6_INSTS(X)
+// the enum value of an instantiation, and its case label (a switch over CoarseInst has no default: every value is named in it)
+#define VFM_CI_PIPE(k, s) CI_PIPE_##k##_##s
+#define VFM_CI_V(k, q) CI_V_##k##_##q
+#define VFM_CI_R(k, q, nb, b) CI_R_##k##_##q##_##nb##_##b
+#define VFM_CI_I8(k, t, t2, lo) CI_I8_##k##_##t##_##t2##_##lo
+#define VFM_CI_I8Q2(k, t2, lo, f) CI_I8Q2_##k##_##t2##_##lo##_##f
+#define VFM_CI_MX6(k, kind, lo, img, ring, t, ns) CI_##kind##_##k##_##lo##_##img##_##ring##_##t##_##ns
+#define VFM_CI(family, ...) VFM_CI_##family(__VA_ARGS__)
+#define VFM_CI_CASE(family, ...) case VFM_CI(family, __VA_ARGS__):
+#define VFM_CI_ENUM(family, ...) VFM_CI(family, __VA_ARGS__),
+#define VFM_CI_ARGS(family, ...) {CF_##family, {__VA_ARGS__}},
+enum CoarseFamily : unsigned char { CF_PIPE, CF_V, CF_R, CF_I8, CF_I8Q2, CF_MX6 };
+enum CoarseInst : unsigned char { VFM_COARSE_INSTS(VFM_CI_ENUM) CI_COUNT };
+struct CoarseInstArgs {
+    unsigned char family;   // CoarseFamily
+    short a[7];             // the template arguments, in order (the rest 0)
 };
-extern thread_local const CoarseKernelName* g_last_coarse_kernel;
+constexpr CoarseInstArgs k_coarse_insts[CI_COUNT] = {VFM_COARSE_INSTS(VFM_CI_ARGS)};
+// the instantiation of `family` with these template arguments, or -1
+inline int coarse_inst(int family, int a0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0, int a6 = 0) {
+    const int want[7] = {a0, a1, a2, a3, a4, a5, a6};
+    for (int i = 0; i < CI_COUNT; ++i) {
+        bool same = k_coarse_insts[i].family == family;
+        for (int j = 0; same && j < 7; ++j) same = k_coarse_insts[i].a[j] == want[j];
+        if (same) return i;
+    }
+    return -1;
+}
+// Dynamic LDS of a shape, one function per kernel family: what the launch asks for (resolve_coarse) and what must fit a compute unit's
+// 160 KiB (the static_assert below the functions; every kernel asserts the same of the ring it lays out)
+constexpr int pipe_lds(int ksteps, bool sparse) { return 6 * ksteps * 1024 + (sparse ? SPARSE_LREC_CAP * 8 + 16 : 0); }
+constexpr int v_lds(int ksteps) { return ring_depth(ksteps) * ksteps * 1024; }
+constexpr int r_lds(int ksteps, int nbuf) { return nbuf * ksteps * 1024; }
+constexpr int i8_lds(int ksteps, int t) { return 3 * t * ksteps * 1024; }
+constexpr int i8q2_lds(int ksteps) { return 12 * ksteps * 1024; }
+constexpr int mx6_lds(int ks6, int kind, int ring, int t) {
+    const int ring_bytes = ring * t * (MX6_SCALE_PLANE + ks6 * MX6_KSTEP_BYTES) + MX6_LTAB * 8;   // the tiles' prefix the pass reads, and the table
+    // FUSE: entries the workgroup's list holds (the slot in global memory is MX6_LCAP + 4 words for every shape; d = 768's ring leaves 4 KiB)
+    const int lcap = ring_bytes + (MX6_LCAP + 1) * 4 <= 160 * 1024 ? MX6_LCAP : 1023;
+    return ring_bytes + (kind == MX6_FUSE ? (lcap + 1) * 4 : 0);
+}
+constexpr int coarse_inst_lds(const CoarseInstArgs& k) {
+    return k.family == CF_PIPE ? pipe_lds(k.a[0], k.a[1]) : k.family == CF_V ? v_lds(k.a[0]) : k.family == CF_R ? r_lds(k.a[0], k.a[2])
+         : k.family == CF_I8 ? i8_lds(k.a[0], k.a[1]) : k.family == CF_I8Q2 ? i8q2_lds(k.a[0]) : mx6_lds(k.a[0], k.a[1], k.a[4], k.a[5]);
+}
+// threads per workgroup: 8 waves; match_coarse_kernel 512 / QSETS; match_coarse_r_kernel 4 waves
+constexpr int coarse_inst_block(const CoarseInstArgs& k) { return k.family == CF_V ? 512 / k.a[1] : k.family == CF_R ? 256 : 512; }
+constexpr bool coarse_lds_fits() {
+    for (int i = 0; i < CI_COUNT; ++i)
+        if (coarse_inst_lds(k_coarse_insts[i]) > 160 * 1024) return false;
+    return true;
+}
+static_assert(coarse_lds_fits(), "an instantiation's ring exceeds the LDS");
 
 // size and policy rules of the passes (match_api.hip)
 bool use_sparse(int d, int64_t n, int64_t m);
@@ -701,8 +788,146 @@ inline int check_plan_gate(bool needed, float gate, const char* who) {
     if (needed && !(gate > -__builtin_inff())) return vfm_fail(VFM_EINVAL, "%s: the half-width and fused record kinds need a finite gate", who);
     return VFM_OK;
 }
-int coarse_qblock(int d);
-int choose_slices(int nqb, int nchunks);
+
+// ---------------------------------------------------------------------------------------------
+// Which coarse kernel a plan's coarse pass launches and on what grid, resolved ONCE: do_search_coarse and l2i8_search hand the result to
+// launch_coarse, the read-back vfm_debug_coarse_plan prints it.  Host arithmetic on the shape, the calling thread's vfm_cfg() and the
+// compute-unit count the caller passes; no HIP call in here.
+// ---------------------------------------------------------------------------------------------
+struct CoarseLaunch {
+    int inst = 0;          // CoarseInst
+    bool seeded = false;   // the sparse pipelined kernel with seed units at the head of its grid: a launch argument, not a template one -- but a
+                           // different grid and a different first round, so it goes by a second name ("pipe<24,sparse>+seed")
+    int nqb = 0, nslices = 0, seed_parts = 0, seed_chunks = 0, nseed_pad = 0, tune = 0;   // CoarseArgs' fields of the same names
+    int block = 0, lds = 0;   // threads per workgroup, bytes of dynamic LDS
+    int grid() const { return nseed_pad + nqb * nslices; }
+};
+
+inline int choose_slices(int nqb, int nchunks) {
+    if (vfm_cfg().force_slices > 0) return vfm_cfg().force_slices < nchunks ? vfm_cfg().force_slices : nchunks;
+    // Fill 256 CUs with whole "rounds" of workgroups (tail efficiency).  Every (query block, slice) unit re-reads its 256
+    // queries (196 KB), so HBM / Infinity-Cache traffic grows with the slice count (C2: 55 slices 1.45 GB per launch).
+    // Round 2 sweep at C2 with the seeded sparse kernel (registrations/s in the pipeline): 14-16 slices 349, 21: 367,
+    // 29: 366, 35: 367, 42: 365, 48: 364, 55: 364 -- flat from ~8 rounds on.  So: among the counts within 1 % of the best
+    // tail efficiency take the SMALLEST that still gives >= 8 rounds (29 at C2); without such a count, the most efficient.
+    int best_s = 1;
+    double best_eff = -1.0;
+    const int smax = nchunks < 64 ? nchunks : 64;
+    auto eff_of = [&](int s, long long* rounds_out) {
+        const long long total = (long long)nqb * s;
+        const long long rounds = (total + 255) / 256;
+        if (rounds_out) *rounds_out = rounds;
+        return (double)total / (double)(rounds * 256);
+    };
+    for (int s = 1; s <= smax; ++s) {
+        if (nchunks / s < 8 && s > 1) break;  // keep >= 32 tiles per workgroup
+        const double eff = eff_of(s, nullptr);
+        if (eff > best_eff + 1e-9) {
+            best_eff = eff;
+            best_s = s;
+        }
+    }
+    for (int s = 1; s < best_s; ++s) {
+        long long rounds;
+        const double eff = eff_of(s, &rounds);
+        if (rounds >= 8 && eff >= best_eff - 0.01) return s;
+    }
+    return best_s;
+}
+
+// row_bias: the launch adds CoarseArgs::row_bias (Euclidean search, d > 510); compute_units: of the device the launch goes to
+inline int resolve_coarse(CoarseLaunch& l, const SearchPlan& p, int d, int64_t n, int64_t m, bool row_bias, int compute_units) {
+    l = CoarseLaunch{};
+    const VfmConfig& cfg = vfm_cfg();
+    const int npad = (int)rows_padded(n), nchunks = (int)chunks_padded(m), nq_tiles = (int)((n + TILE_ROWS - 1) / TILE_ROWS);
+    const bool top2 = p.top2;
+    int inst;
+    if (row_bias && d != 640 && d != 768) return vfm_fail(VFM_EINVAL, "row bias needs the 4-wave coarse kernel (K = 640 / 768), got %d", d);
+    if (!p.quantised()) {   // the fp16 pass, d in {128, ..., 768}
+        const int ks = d / 16;
+        const bool sparse = p.pass == PASS_F16_SPARSE;
+        l.nqb = npad / (d > 512 ? 128 : QBLOCK);   // queries per workgroup: 8 waves x 32 or 4 x 64; the 4-wave kernel of d > 512 4 x 32
+        l.nslices = choose_slices(l.nqb, nchunks);
+        if (d > 512) inst = coarse_inst(CF_R, ks, 1, 3, row_bias);
+        else if (d > 384) inst = coarse_inst(CF_V, ks, 1);   // d = 512: 2 x 128 query VGPRs would not fit; 8-wave kernel, ring of 4: 3.45 ms at C2 x 512 (4-wave kernel: 4.42 ms)
+        else if (cfg.coarse_qsets == 1 || cfg.coarse_qsets == 2) inst = coarse_inst(CF_V, ks, cfg.coarse_qsets);
+        else inst = coarse_inst(CF_PIPE, ks, sparse);   // 0, 3
+        if (inst < 0) return vfm_fail(VFM_EINVAL, "FAST matching supports d in {128,256,384,512,640,768}, got %d", d);
+        if (sparse && cfg.seed_units && nchunks >= 256 && l.nqb <= 256) {  // seed units: one short round at the head of the grid
+            l.seed_parts = 256 / l.nqb < 4 ? 256 / l.nqb : 4;
+            l.seed_chunks = 5;
+            l.nseed_pad = (l.nqb * l.seed_parts + 7) / 8 * 8;
+            l.nslices = choose_slices(l.nqb, nchunks - l.seed_parts * l.seed_chunks);
+        }
+    } else if (p.pass == PASS_I8) {   // KSTEPS = d / 32 (the half-width kinds: the image of the first d / 2 columns, d / 64)
+        // 64 resident queries per wave: 11-15 % faster than the one-set kernel from ~3000 queries on (C2: 1.09 vs 1.23 ms;
+        // 1500 x 100 000: 0.059 vs 0.056 ms -- half as many, twice as large workgroups); variants 10 / 12 = one set, A/B.
+        // The half-width pass has them at every width (d / 2 columns are at most 384), the fused one (d = 256 / 384, more than 2048
+        // queries: resolve_search) nothing else
+        const bool q2 = p.fused || ((p.half || d <= 384) && n > 2048 && cfg.coarse_qsets == 0);
+        const bool t2 = cfg.coarse_qsets == 10;  // variant 10 (A/B): 2 tiles per step at every width
+        l.nqb = q2 ? (nq_tiles + 15) / 16 : npad / QBLOCK;  // 8 waves x 64 / x 32 queries at every width
+        l.nslices = choose_slices(l.nqb, nchunks);
+        if (q2) inst = coarse_inst(CF_I8Q2, p.half ? d / 64 : d / 32, top2, !p.half, p.fused);
+        else if (p.half) inst = coarse_inst(CF_I8, d / 64, 4, false, false);   // one query set per wave: few queries (variants 10 / 12: every size, A/B)
+        else inst = coarse_inst(CF_I8, d / 32, d <= 384 && (top2 || !t2) ? 4 : 2, top2, true);
+    } else {   // the fp6 pass: d = 256 / 384 (full width) or 256 / 384 / 512 / 768 (half width) and more than 2048 queries (resolve_search)
+        const bool half = p.half, fuse = p.fused;   // (fuse && !half: VFM_RECORDS_MX6_FUSED, the full-width pass with the gate test in its epilogue)
+        const bool ns3 = half && fuse && d == 384 && cfg.mx6_ns3 && cfg.mx6_t4;   // three query tiles per wave: 768 queries per workgroup
+        l.nqb = ns3 ? (nq_tiles + 23) / 24 : (nq_tiles + 15) / 16;
+        l.nslices = choose_slices(l.nqb, nchunks);
+        if (half && cfg.force_slices == 0) {
+            // the half-width kernel's workgroups are short, and shorter ones let the other stages of a pipeline in: ~7.5 rounds of 256
+            // workgroups instead of choose_slices' 5 (tools/sweep_slices.py, C2, 200 steps: 48 slices 1548 against 32 slices 1475
+            // registrations/s; the full-width fp6 kernel and the int8 kernels are flat from 32 on)
+            int s = (int)((1600 + l.nqb - 1) / l.nqb);   // (round 4, tools/sweep_slices_r4.py, fused kernel: 40 / 44 slices 1764 / 1762, 48: 1740, 57: 1690 registrations/s over 200 steps)
+            const int smax = nchunks / 8 < 64 ? nchunks / 8 : 64;
+            s = s > smax ? smax : s;
+            s = s < 1 ? 1 : s;
+            // Round 6: the workgroups are equal and a compute unit holds one, so the kernel lasts ceil(workgroups / units) rounds whatever the last
+            // round holds (tools/sweep_slices_r6.py, the kernel alone at C2, 27 query blocks: 60 slices = 6.33 rounds 0.388 ms; 56 = 5.9 rounds
+            // 0.370; 47 = 4.96 rounds 0.367; 19 slices = 2.004 rounds 0.445).  Near the count above, take the slice count whose last round is
+            // (almost) full -- at most 4 above, 12 below; in the pipeline 56 against 60 is +1 % over 200 steps, even in the 20-step form.
+            {
+                const int cus = compute_units;
+                int best = s;
+                double best_fill = 0.0;
+                for (int t = (s + 4 < smax ? s + 4 : smax); t >= 1 && t >= s - 12; --t) {
+                    const long long wg = (long long)l.nqb * t, rounds = (wg + cus - 1) / cus;
+                    const double fill = (double)wg / (double)(rounds * cus);
+                    if (fill >= 0.975) {   // the largest such count (short workgroups let the pipeline's other stages in)
+                        best = t;
+                        best_fill = 2.0;
+                        break;
+                    }
+                    if (fill > best_fill) {
+                        best_fill = fill;
+                        best = t;
+                    }
+                }
+                s = best;
+            }
+            l.nslices = s < 1 ? 1 : s;
+        }
+        while ((nchunks + l.nslices - 1) / l.nslices + 1 > MX6_LTAB && l.nslices < nchunks) ++l.nslices;   // a slice's constants fit the LDS table
+        if (fuse && (l.nqb > surv_slot_qblocks(npad) || l.nslices > surv_slot_slices(nchunks)))   // (what carve_search sized the slots for)
+            return vfm_fail(VFM_EINVAL, "search_coarse: %d x %d survivor slots exceed the workspace (n %d chunks %d)", l.nqb, l.nslices, npad, nchunks);
+        // Two chunks per barrier (T = 8, ring of 3 x 8 tiles: 84 / 120 KiB at d = 256 / 384) is built, parity-tested and measured: 0.415 ms
+        // against 0.419 alone, 1715 against 1725 registrations/s in the pipeline (tools/ab_r4.py) -- the barrier share the ablations
+        // show (tools/ablate6.py: -10 % without barrier and staging) does not come back by halving the barriers, and the larger ring
+        // leaves the side kernels less LDS.  One chunk per barrier stays the default; vfm_debug_set_coarse_variant(31) selects T = 8.
+        const bool t8 = half && fuse && (d == 384 || d == 256) && !cfg.mx6_t4 && l.nslices <= nchunks / 2;
+        l.tune = cfg.mx6_tune;
+        const int ring = ns3 ? ((cfg.mx6_tune & 2) ? 5 : 4) : t8 ? 3 : 4;   // (A/B, three-tile shape) a ring of five steps
+        inst = coarse_inst(CF_MX6, half ? d / 128 : d / 64, fuse ? MX6_FUSE : top2 ? MX6_TOP2 : MX6_BEST, !half && !fuse, d / 64, ring, t8 ? 8 : 4, ns3 ? 3 : 2);
+    }
+    if (inst < 0) return vfm_fail(VFM_EINVAL, "search_coarse: no coarse kernel for d = %d, record kind %d", d, p.kind);
+    l.inst = inst;
+    l.seeded = l.nseed_pad != 0;
+    l.block = coarse_inst_block(k_coarse_insts[inst]);
+    l.lds = coarse_inst_lds(k_coarse_insts[inst]);
+    return VFM_OK;
+}
 inline I8Bounds i8_bounds(const Prepared& Q, const Prepared& B, bool on, int top2 = 0) {
     return on ? I8Bounds{Q.err, Q.gstep, B.gstep, B.gerr, top2 == VFM_RECORDS_TOP2 ? 1 : 0} : I8Bounds{nullptr, nullptr, nullptr, nullptr, 0};
 }
@@ -717,7 +942,9 @@ inline I8Bounds plan_bounds(const SearchPlan& p, const Prepared& Q, const Prepar
     if (p.bounds == BOUNDS_MX6) return mx6_bounds(Q, B, p.top2 ? 1 : 0);
     return i8_bounds(Q, B, p.bounds == BOUNDS_I8, p.top2 ? 1 : 0);
 }
-CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m, int qblock = QBLOCK);
+// everything of the argument block but the launch geometry (nqb, nslices, the seed units, tune: launch_coarse sets them from a CoarseLaunch;
+// the finish stage reads none of them)
+CoarseArgs coarse_args(const Prepared& Q, const Prepared& B, const SearchWs& w, int64_t n, int64_t m);
 
 // match_prep.hip
 // What do_search_coarse clears in front of a coarse pass, as two ranges of whole 16-byte units: a preparation that runs just before on
@@ -865,11 +1092,15 @@ int do_prepare2(int entry, int schedule, Rows x1, int64_t rows1, void* prepared1
 // int8 image alone of ONE operand whose row r is x[perm[r]] (perm == NULL: identity) -- the Euclidean search prepares its map
 // sorted by norm and the queries of its reverse direction gathered by the forward result
 int do_prepare_perm(const float* x, int64_t rows, const int* perm, int d, void* prepared, hipStream_t st);
-// match_coarse_f16.hip / match_coarse_i8.hip: launch the coarse kernel for arguments prepared by do_search_coarse
-int launch_coarse_f16(const CoarseArgs& a, int d, hipStream_t st);
-int launch_coarse_int8(CoarseArgs& a, int d, int64_t n, int records, hipStream_t st);
-int launch_coarse_mx6(CoarseArgs& a, int d, bool top2, bool half, bool fuse, hipStream_t st);   // match_coarse_mx6.hip (fuse && !half: VFM_RECORDS_MX6_FUSED)
-int mx6_survivor_slot_words();   // words per workgroup slot of the fused half-width pass (header + entries)
+// match_api.hip: the coarse kernel `l` names on the grid it gives, for arguments prepared by do_search_coarse (sets a's launch geometry)
+int launch_coarse(const CoarseLaunch& l, CoarseArgs& a, hipStream_t st);
+// ... and the one frame every launch goes through: dynamic LDS allowed once per device, the profiling events around the launch
+typedef void (*CoarseKernel)(CoarseArgs);
+int launch_coarse_kernel(CoarseKernel kernel, const char* what, const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st);
+// match_coarse_f16.hip / _i8.hip / _mx6.hip: the instantiations of each file's families
+int launch_coarse_f16(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st);
+int launch_coarse_int8(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st);
+int launch_coarse_mx6(const CoarseLaunch& l, const CoarseArgs& a, hipStream_t st);
 // match_api.hip
 int do_search_coarse(const void* qprep, int64_t n, const void* bprep, int64_t m, int d, void* ws, hipStream_t st,
                      bool bias_from_map_inv = false, bool inner_product = false, bool gated = false, int records = 0,

@@ -583,7 +583,7 @@ int l2_search(const float* q, void* qprep, int64_t n, const float* b, void* bpre
     if (int rc = do_search_coarse(qprep, n, bprep, m, kp, ws, st, !l2_aug(d))) return rc;
     Prepared Q = carve_prepared(qprep, n, kp);
     SearchWs w = carve_search(ws, n, m);
-    const CoarseArgs a = coarse_args(Q, carve_prepared(bprep, m, kp), w, n, m, coarse_qblock(kp));
+    const CoarseArgs a = coarse_args(Q, carve_prepared(bprep, m, kp), w, n, m);
     if (int rc = launch_select_dense(w, a, Q.inv, n, st)) return rc;
     hipLaunchKernelGGL(l2_rescore_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)d * 4 * 8, st, q, b, n, m, d, w.cand_cnt,
                        w.cand, w.cap, nn, d2);
@@ -733,12 +733,17 @@ int l2i8_search(const float* qx, const int* qperm, int64_t n, const float* qn, v
     Prepared Q = carve_prepared(qprep, n, d);
     Prepared P = carve_prepared(B.prep, m, d);
     SearchWs w = carve_search(ws, n, m);
-    CoarseArgs a = coarse_args(Q, P, w, n, m, QBLOCK);
+    CoarseArgs a = coarse_args(Q, P, w, n, m);
+    SearchPlan plan;   // the int8 pass with best-score records at every size: no fallback of resolve_search applies
+    plan.pass = PASS_I8;
+    plan.kind = VFM_RECORDS_BEST;
+    CoarseLaunch launch;
+    VFM_TRY(resolve_coarse(launch, plan, d, n, m, false, vfm_compute_units()));
     VFM_CHECK_HIP(hipMemsetAsync(w.fb_count, 0, search_zero_bytes(n, m), st));
     a.Qh = Q.tiles8;
     a.Bh = P.tiles8;
     a.ib = I8Bounds{Q.err, Q.gstep, P.gstep, P.gerr, 0};
-    if (int rc = launch_coarse_int8(a, d, n, VFM_RECORDS_BEST, st)) return rc;
+    if (int rc = launch_coarse(launch, a, st)) return rc;
     const bool use_bins = n >= 4 * (int64_t)a.nchunks;
     const int chunk_lds = (size_t)a.nchunks * sizeof(float4) <= 63 * 1024;
     const float slack = (float)(d + 16) * 2.3841858e-7f;   // (d + 16) 2^-22: the fp32 roundings of the norms and of the evaluation

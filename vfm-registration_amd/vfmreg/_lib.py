@@ -164,6 +164,7 @@ DEBUG_SIGNATURES = {
     "vfm_debug_last_coarse_kernel": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_coarse_kernel_names": (C.c_int, [C.c_char_p, C.c_int]),
     "vfm_debug_search_plan": (C.c_int, [C.c_int, C.c_int, c_i64, c_i64, C.c_int, C.c_char_p, C.c_int]),
+    "vfm_debug_coarse_plan": (C.c_int, [C.c_int, C.c_int, c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "vfm_debug_prepare_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i64, C.c_int, c_i64, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "vfm_debug_match_stats": (C.c_int, [c_vp, c_i64, c_i64, c_vp]),
     "vfm_debug_i8_rows": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
@@ -327,6 +328,17 @@ def search_plan(records: int, d: int, n: int, m: int, gated: bool = True) -> dic
     out = {k: bool(int(v)) for k, v in plan.items() if k not in ("pass", "kind", "finish")}
     out.update({"pass": plan["pass"], "kind": int(plan["kind"]), "finish": plan["finish"].split(",")})
     return out
+
+
+def coarse_plan(records: int, d: int, n: int, m: int, gated: bool = True, inner_product: bool = True, row_bias: bool = False,
+                compute_units: int = 0) -> dict:
+    """The launch of that search's coarse pass (include/vfmreg_debug.h, vfm_debug_coarse_plan; compute_units 0: the current device's):
+    {"kernel": the name last_coarse_kernel() reports after it, "nqb", "nslices", "seed", "block", "lds", "tune": int}.  Raises
+    RuntimeError with the library's message where the search itself would refuse.  Touches no device."""
+    buf = C.create_string_buffer(1024)
+    check(load().vfm_debug_coarse_plan(records, d, n, m, int(gated), int(inner_product), int(row_bias), compute_units, buf, len(buf)), "coarse_plan")
+    plan = dict(item.split("=", 1) for item in buf.value.decode().split(" "))
+    return {k: (v if k == "kernel" else int(v)) for k, v in plan.items()}
 
 
 def prepare_plan(entry: int, schedule: int, d: int, rows1: int, rows2: int = 0, dtype1: int = 0, dtype2: int = 0, zero: bool = False) -> dict:
