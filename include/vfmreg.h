@@ -130,11 +130,11 @@ int vfm_match_ip_top1_gated(const float *q, int64_t n, const float *b, int64_t m
  * launched, as for null outputs); n == 0 succeeds and writes nothing; a workspace smaller than _workspace_bytes is VFM_EWORKSPACE.
  * No gate: the caller applies !(sim < thr) to the result, as the reference does (VHM:503).
  * VFM_MATCH_EXACT (d <= 8192): all pairs in fp64 on the vector ALUs.
- * VFM_MATCH_FAST, d = 128 / 256 / 384 and at most 2^24 map rows: an fp16 MFMA coarse pass that keeps, per query, a lower bound of
- * the k-th best coarse score and records every row within the proven window of it, then the fp64 decision among the records
+ * VFM_MATCH_FAST, d = 128 / 256 / 384 / 640 / 768 and at most 2^24 map rows: an fp16 MFMA coarse pass that keeps, per query, a lower
+ * bound of the k-th best coarse score and records every row within the proven window of it, then the fp64 decision among the records
  * (csrc/match_topk.hip); a query with more than 1024 records is decided by the all-pairs kernel inside the same
- * call.  Same answers as EXACT.  Any other shape given FAST runs EXACT (the d = 512 and d = 640 / 768 kernel shapes of the top-1
- * search have no k-best form).
+ * call.  Same answers as EXACT.  Any other shape given FAST runs EXACT (d = 512 is the one width of the top-1 search's fp16 kernels
+ * that has no k-best form).
  * info_out (nullable, DEVICE int32[4]): the largest record count of a query, the number of queries decided by the all-pairs
  * kernel, the largest number of map slices of a coarse launch, 0.  A call that ran EXACT reports (0, n, 0, 0). */
 #define VFM_MATCH_TOPK_MAX 8
@@ -142,6 +142,21 @@ size_t vfm_match_ip_topk_workspace_bytes(int64_t n, int64_t m, int d, int k, int
 int vfm_match_ip_topk(const float *q, int64_t n, const float *b, int64_t m, int d, int k, int prec_mode,
                       int64_t *idx_out, float *sim_out, int32_t *info_out /* may be NULL */,
                       void *ws, size_t ws_bytes, vfm_stream_t stream);
+/* The FAST search on operands prepared beforehand -- for a map that every scan of a scene searches (IndexFlatIP.add once, VHM:487):
+ * what vfm_match_ip_topk(..., VFM_MATCH_FAST, ...) runs after preparing both operands, and, bit for bit, its idx_out, sim_out and
+ * info_out.  q_prepared / b_prepared: images written by vfm_match_prepare or vfm_match_prepare2 (vfm_match_prepared_bytes(rows, d)
+ * bytes: the fp16 fragment image and 1 / |row|) of the rows q / b, which the fp64 decision reads as well; the call leaves both
+ * images as it found them.  An image written by one of the gated preparations (vfm_match_prepare2_gated*) may lack the fp16
+ * fragment image and is NOT an operand of this call.  The workspace holds the records alone.
+ * Refused before any launch: k outside 1 .. VFM_MATCH_TOPK_MAX, null outputs or operands, and (VFM_EINVAL -- no fallback to the
+ * all-pairs kernel here, for which a prepared image means nothing) a shape FAST has no kernel for: d not in {128, 256, 384, 640,
+ * 768}, m < 1, more than 2^24 padded map rows; VFM_EWORKSPACE for a workspace smaller than _workspace_bytes, which is 0 for
+ * arguments the call would refuse.  n == 0 succeeds and writes nothing. */
+size_t vfm_match_ip_topk_prepared_workspace_bytes(int64_t n, int d, int k);
+int vfm_match_ip_topk_prepared(const float *q, const void *q_prepared, int64_t n,
+                               const float *b, const void *b_prepared, int64_t m, int d, int k,
+                               int64_t *idx_out, float *sim_out, int32_t *info_out /* may be NULL */,
+                               void *ws, size_t ws_bytes, vfm_stream_t stream);
 
 /* Split form for a map that is searched many times (IndexFlatIP.add once, VHM:487): the
  * prepared operand holds 1/|row| and the fp16 MFMA-fragment image of the normalised rows. */

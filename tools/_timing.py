@@ -42,15 +42,15 @@ def write_step(path, result, show=0):
         print(json.dumps(result)[:show], flush=True)
 
 
-def run_steps(script, out, steps):
+def run_steps(script, out, steps, extra=()):
     """``script --step [name] --json FILE`` for every (name, limit in seconds) of ``steps``, each a child process of its own under
     ``timeout -k 10 limit``; a non-zero status ends the run.  (status, {name: result}, device description).  An empty name stands for a
-    tool whose ``--step`` takes no value."""
+    tool whose ``--step`` takes no value; ``extra``: further arguments every child receives."""
     res, box = {}, ""
     for name, limit in steps:
         js = out.with_suffix(f".{name or 'step'}.json")
         rc = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, str(script), "--step", *([name] if name else []),
-                             "--json", str(js)]).returncode
+                             "--json", str(js), *extra]).returncode
         if rc != 0:
             print(f"step {name or 'timing'} ended with status {rc}: stopping", flush=True)
             return rc, res, box

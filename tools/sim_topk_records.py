@@ -3,7 +3,8 @@
     python tools/sim_topk_records.py
 
 Rows are L2-normalised Gaussian (seed 0); the "common" cases add a shared 2 x Gaussian vector to both sides first.  Scores are fp32
-Q @ B.T.  A lane sees the rows of its half-wave, ((row % 32) >> 2) & 1, and updates its bound once per 64-row step; a row is a record
+Q @ B.T.  A lane sees the rows of its half-wave, ((row % 32) >> 2) & 1, and updates its bound once per step -- 64 map rows up to
+d = 384, 32 map rows in the 4-wave form of d = 640 / 768, whose workgroups hold 128 queries instead of 256 --; a row is a record
 iff its score >= bound before the step - 2.5e-3.  Two schedules:
   one slice   the whole map in one workgroup per query block (the figures the feature request quotes);
   launches    what vfm_match_ip_topk launches: 16 chunks in one slice, then launches of three times the chunks already done, each
@@ -43,9 +44,14 @@ def choose_slices(nqb: int, nchunks: int) -> int:
     return best_s
 
 
-def launches(n: int, m: int):
+def wide(d: int) -> bool:
+    """the 4-wave form of the coarse kernel: 128 queries per workgroup, one 32-row tile per step"""
+    return d > 384
+
+
+def launches(n: int, m: int, d: int = 128):
     """[(first chunk, chunks, slices)] of the coarse pass."""
-    nqb = (n + 255) // 256
+    nqb = (n + 255) // 256 * (2 if wide(d) else 1)
     total = (m + 255) // 256 * 2
     out, done = [], 0
     while done < total:
@@ -55,14 +61,14 @@ def launches(n: int, m: int):
     return out
 
 
-def walk(scores: np.ndarray, rows: np.ndarray, k: int, start: np.ndarray):
-    """One lane per query over `rows` in steps of 32 of its rows: (records per query, final bound)."""
+def walk(scores: np.ndarray, rows: np.ndarray, k: int, start: np.ndarray, step: int = 32):
+    """One lane per query over `rows` in steps of `step` of its rows: (records per query, final bound)."""
     n = scores.shape[0]
     L = np.full((n, k), -np.inf, np.float32)
     tau = start.copy()
     count = np.zeros(n, np.int64)
-    for s0 in range(0, len(rows), 32):
-        x = scores[:, rows[s0:s0 + 32]]
+    for s0 in range(0, len(rows), step):
+        x = scores[:, rows[s0:s0 + step]]
         rec = x >= (tau - WINDOW)[:, None]
         count += rec.sum(1)
         L = -np.sort(-np.concatenate([L, np.where(rec, x, -np.inf)], 1), axis=1)[:, :k]
@@ -70,7 +76,7 @@ def walk(scores: np.ndarray, rows: np.ndarray, k: int, start: np.ndarray):
     return count, tau
 
 
-def simulate(scores: np.ndarray, k: int, schedule):
+def simulate(scores: np.ndarray, k: int, schedule, step: int = 32):
     n, m = scores.shape
     half = ((np.arange(m) % 32) >> 2) & 1
     pub = np.full(n, -np.inf, np.float32)
@@ -81,7 +87,7 @@ def simulate(scores: np.ndarray, k: int, schedule):
             lo, hi = (c0 + s * nch // ns) * 128, min((c0 + (s + 1) * nch // ns) * 128, m)
             for h in (0, 1):
                 rows = np.arange(lo, hi)[half[lo:hi] == h]
-                c, t = walk(scores, rows, k, pub)
+                c, t = walk(scores, rows, k, pub, step)
                 count += c
                 nxt = np.maximum(nxt, t)
         pub = nxt
@@ -105,15 +111,19 @@ def rows_of(n, m, d, common, rng):
 def main():
     cases = [("Gaussian", 257, 4097, 128, 8, False), ("Gaussian", 257, 4097, 384, 8, False), ("Gaussian", 64, 20000, 128, 8, False),
              ("Gaussian", 64, 20000, 128, 2, False), ("common", 257, 4097, 384, 8, True), ("common", 64, 20000, 128, 8, True),
-             ("Gaussian", 64, 200000, 128, 8, False), ("common", 64, 200000, 128, 8, True)]
+             ("Gaussian", 64, 200000, 128, 8, False), ("common", 64, 200000, 128, 8, True),
+             ("Gaussian", 257, 4097, 640, 8, False), ("common", 257, 4097, 640, 8, True), ("Gaussian", 257, 4097, 768, 8, False),
+             ("common", 257, 4097, 768, 8, True), ("Gaussian", 129, 300, 768, 8, False), ("common", 129, 300, 768, 8, True),
+             ("Gaussian", 64, 200000, 768, 8, False), ("common", 64, 200000, 768, 8, True)]
     print("| Data | N x M x d | k | one slice: mean | max | launches: mean | max | launches (chunks x slices) |")
     print("|---|---|---|---|---|---|---|---|")
     for name, n, m, d, k, common in cases:
         q, b = rows_of(n, m, d, common, np.random.default_rng(0))
         scores = q @ b.T
-        one = simulate(scores, k, [(0, (m + 255) // 256 * 2, 1)])
-        sched = launches(n, m)
-        many = simulate(scores, k, sched)
+        step = 16 if wide(d) else 32   # a lane's rows of a step
+        one = simulate(scores, k, [(0, (m + 255) // 256 * 2, 1)], step)
+        sched = launches(n, m, d)
+        many = simulate(scores, k, sched, step)
         print(f"| {name} | {n} x {m} x {d} | {k} | {one.mean():.0f} | {one.max()} | {many.mean():.0f} | {many.max()} | "
               + " ".join(f"{c}x{s}" for _, c, s in sched) + " |")
 

@@ -10,11 +10,14 @@
 // VFM_MATCH_TOPK_MAX entries per thread, then k rounds of a workgroup-wide arg-max over the lists' heads.  The score chain, the
 // order and the arg-max are the top-1 search's own (match_exact.h), and so is 1 / |row| (launch_inv_norm, match_finish.hip).
 //
-// FAST (d = 128 / 256 / 384, at most 2^24 padded map rows; anything else given FAST runs EXACT, as the top-1 entry point falls back;
-// the d = 512 and d = 640 / 768 kernel shapes of the top-1 search are out of scope here):
-//   coarse   match_topk_coarse_kernel<d / 16>: v_mfma_f32_32x32x16_f16 on the fragment images vfm_match_prepare writes, in the shape
-//            of match_coarse_kernel<KSTEPS, 1> (match_coarse_f16.hip): 8 waves x 32 resident queries, map tiles through an LDS ring of
-//            6 by LDS-DMA, two tiles (64 map rows) per step, accumulators started at COARSE_OFFSET so that uint order == float order.
+// FAST (d = 128 / 256 / 384 / 640 / 768, at most 2^24 padded map rows; anything else given FAST runs EXACT, as the top-1 entry point
+// falls back -- d = 512 is the one width of the top-1 search's fp16 kernels left without a k-best form; vfm_match_ip_topk_prepared,
+// the same search on operands prepared beforehand, refuses such a shape instead):
+//   coarse   match_topk_coarse_kernel<d / 16, waves>: v_mfma_f32_32x32x16_f16 on the fragment images vfm_match_prepare writes.  Up to
+//            d = 384 in the shape of match_coarse_kernel<KSTEPS, 1> (match_coarse_f16.hip): 8 waves x 32 resident queries, map tiles
+//            through an LDS ring of 6 by LDS-DMA, two tiles (64 map rows) per step; d = 640 / 768 in the shape of
+//            match_coarse_r_kernel<KSTEPS, 1, 3>: 4 waves, one tile per step, ring of 3 (TopkShape below: the two forms and the
+//            wide form's accumulation order and error bound).  Accumulators started at COARSE_OFFSET so that uint order == float order.
 //            A lane holds ONE query's scores for 16 of a tile's 32 rows and keeps the k best coarse scores it has seen in a sorted
 //            list of registers.  The list's smallest entry, tau, is a lower bound of the query's final k-th best coarse score c_k (the
 //            k-th best of a subset never exceeds the k-th best of the whole).  Per step the epilogue is one max per accumulator
@@ -50,6 +53,7 @@ constexpr int TOPK_RECORD_CAP = FILTER_LDS_ROWS;   // records a query can hold (
 constexpr int TOPK_LREC_CAP = SPARSE_LREC_CAP;     // records a coarse workgroup buffers in LDS
 constexpr int TOPK_NBUF = 6;                       // LDS ring, tiles
 constexpr int TOPK_SEED_CHUNKS = 16;               // map chunks of the first, one-slice launch of the coarse pass
+constexpr int TOPK_FAST_MAX_D = 768;               // widest row FAST serves (match_topk_finish_kernel keeps a query row in LDS)
 static_assert(TOPK_MAX == 8, "the lanes' lists and the threads' lists are eight registers");
 static_assert(TOPK_RECORD_CAP >= 1024, "record cap");
 
@@ -93,15 +97,42 @@ struct TopkArgs {
     uint2* rec;
 };
 
-template <int KSTEPS>
-__global__ __launch_bounds__(512) void match_topk_coarse_kernel(TopkArgs a) {
+// The two forms of the coarse kernel, by the number of waves of a workgroup (32 resident queries each):
+//   8 waves (d = 128 / 256 / 384)  two waves per SIMD; a step is two map tiles (a lane sees 32 elements), ring of six tiles;
+//   4 waves (d = 640 / 768)        the shape of match_coarse_r_kernel<48 | 40, 1, 3> (match_coarse_f16.hip): one wave per SIMD and
+//                                  the whole 512-register file -- the query fragments alone are 192 registers at d = 768 --; a step
+//                                  is ONE map tile (48 KiB at d = 768; a lane sees 16 elements and refreshes its bound twice as
+//                                  often), ring of three tiles.  The k-steps alternate between two accumulator chains, the first
+//                                  started at COARSE_OFFSET and the second at 0, added before the epilogue: the accumulation
+//                                  order of the top-1 wide kernel, whose bound E < 1.15e-3 at 48 k-steps (40
+//                                  k-steps at d = 640 stay below it) gives 2E < 2.3e-3 <= DEFAULT_WINDOW = 2.5e-3 -- no packed row
+//                                  index in the score here, so nothing is added to it.
+// Either ring is three steps deep: the tiles of step i in use, those of step i + 1 landed, those of step i + 2 staged behind the
+// barrier of step i into the slots step i - 1 read.  Everything after the accumulation is one copy.
+template <int NWAVES>
+struct TopkShape {
+    static_assert(NWAVES == 8 || NWAVES == 4, "8 waves x 2 tiles per step, or 4 waves x 1");
+    static constexpr int TPS = NWAVES == 8 ? 2 : 1;   // map tiles per step
+    static constexpr int NBUF = 3 * TPS;              // LDS ring, tiles
+    static constexpr int SPLIT = NWAVES == 8 ? 1 : 2; // accumulator chains per tile
+    static constexpr int QROWS = NWAVES * 32;         // queries of a workgroup
+    static constexpr int lds_bytes(int ksteps) { return NBUF * ksteps * 1024 + TOPK_LREC_CAP * 8 + 16; }
+};
+static_assert(TopkShape<8>::NBUF == TOPK_NBUF && TopkShape<8>::QROWS == QBLOCK, "the 8-wave form is the top-1 search's block");
+static_assert(TopkShape<4>::lds_bytes(48) == 159760 && TopkShape<4>::lds_bytes(48) <= 160 * 1024,
+              "d = 768: three 48 KiB tiles and the record buffer fit the 160 KiB of a compute unit, and no more");
+
+template <int KSTEPS, int NWAVES>
+__global__ __launch_bounds__(NWAVES * 64) void match_topk_coarse_kernel(TopkArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NWAVES = 8;
+    using Shape = TopkShape<NWAVES>;
     constexpr int TILE_U4 = KSTEPS * 64;
     constexpr int TILE_BYTES = TILE_U4 * 16;
     constexpr int PASSES = KSTEPS / NWAVES;   // 1 KiB pieces per wave per tile
-    constexpr int NBUF = TOPK_NBUF;
-    static_assert(KSTEPS % 8 == 0 && KSTEPS <= 24, "d = 128, 256, 384");
+    constexpr int TPS = Shape::TPS, NBUF = Shape::NBUF, SPLIT = Shape::SPLIT;
+    constexpr int NE = 16 * TPS;              // accumulator elements of a lane per step
+    static_assert(KSTEPS % NWAVES == 0 && (NWAVES == 8 ? KSTEPS <= 24 : KSTEPS == 40 || KSTEPS == 48), "d = 128, 256, 384 | 640, 768");
+    static_assert(Shape::lds_bytes(KSTEPS) <= 160 * 1024, "ring and record buffer must fit the LDS");
 
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -134,7 +165,7 @@ __global__ __launch_bounds__(512) void match_topk_coarse_kernel(TopkArgs a) {
         }
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) stage(i);
+    for (int i = 0; i < 2 * TPS; ++i) stage(i);   // (a slice has at least four tiles)
 
     uint2* lrec = reinterpret_cast<uint2*>(smem + NBUF * TILE_BYTES);   // [TOPK_LREC_CAP] (query in block << 24 | row, score bits)
     unsigned* lrec_count = reinterpret_cast<unsigned*>(lrec + TOPK_LREC_CAP);
@@ -159,48 +190,55 @@ __global__ __launch_bounds__(512) void match_topk_coarse_kernel(TopkArgs a) {
     unsigned thr = thr_of(tau);
     const int half4 = 4 * (lane >> 5);
 
-    for (int it = 0; it < ntiles; it += 2) {
-        // every DMA issued so far has landed: tiles it, it + 1 (issued two steps ago) and it + 2, it + 3
+    for (int it = 0; it < ntiles; it += TPS) {
+        // every DMA issued so far has landed: the tiles of this step (issued two steps ago) and of the next
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (it + 4 < ntiles) {   // into the slots of tiles it - 2, it - 1: their last read retired before this barrier
-            stage(it + 4);
-            stage(it + 5);
-        }
-        const uint4* buf0 = reinterpret_cast<const uint4*>(smem + (it % NBUF) * TILE_BYTES) + lane;
-        const uint4* buf1 = reinterpret_cast<const uint4*>(smem + ((it + 1) % NBUF) * TILE_BYTES) + lane;
-        floatx16 acc0, acc1;
+        if (it + 2 * TPS < ntiles) {   // into the slots of the previous step's tiles: their last read retired before this barrier
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = COARSE_OFFSET;
+            for (int t = 0; t < TPS; ++t) stage(it + 2 * TPS + t);
+        }
+        const uint4* buf[TPS];
+        floatx16 acc[TPS][SPLIT];
+#pragma unroll
+        for (int t = 0; t < TPS; ++t) {
+            buf[t] = reinterpret_cast<const uint4*>(smem + ((it + t) % NBUF) * TILE_BYTES) + lane;
+#pragma unroll
+            for (int c = 0; c < SPLIT; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][c][r] = c == 0 ? COARSE_OFFSET : 0.f;
+        }
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
-            uint4 v0 = buf0[s * 64], v1 = buf1[s * 64];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<half8*>(&v0), qf[s], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<half8*>(&v1), qf[s], acc1, 0, 0, 0);
+            uint4 v[TPS];
+#pragma unroll
+            for (int t = 0; t < TPS; ++t) v[t] = buf[t][s * 64];
+#pragma unroll
+            for (int t = 0; t < TPS; ++t)
+                acc[t][s % SPLIT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<half8*>(&v[t]), qf[s], acc[t][s % SPLIT], 0, 0, 0);
         }
         // accumulator register r of a lane: map row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the tile, query lane & 31
         const long long row0 = ((long long)t0 + it) * TILE_ROWS;
-        unsigned x[32];
+        unsigned x[NE];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            x[r] = __float_as_uint(acc0[r]);
-            x[16 + r] = __float_as_uint(acc1[r]);
-        }
-        if (row0 + 2 * TILE_ROWS > a.m_valid) {   // wave-uniform, the last tiles of the map only: zero padding out of the way
+        for (int t = 0; t < TPS; ++t)
 #pragma unroll
-            for (int e = 0; e < 32; ++e) {
+            for (int r = 0; r < 16; ++r) x[16 * t + r] = __float_as_uint(SPLIT == 2 ? acc[t][0][r] + acc[t][SPLIT - 1][r] : acc[t][0][r]);
+        if (row0 + TPS * TILE_ROWS > a.m_valid) {   // wave-uniform, the last tiles of the map only: zero padding out of the way
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
                 const long long row = row0 + (e >> 4) * TILE_ROWS + (e & 3) + 8 * ((e & 15) >> 2) + half4;
                 if (row >= a.m_valid) x[e] = 0u;
             }
         }
         unsigned smax = 0u;
 #pragma unroll
-        for (int e = 0; e < 32; ++e) smax = max(smax, x[e]);
+        for (int e = 0; e < NE; ++e) smax = max(smax, x[e]);
         if (smax >= thr) {   // rare after warm-up (never for a lane that is not live)
             const unsigned ql = (unsigned)(wave * 32 + (lane & 31));
 #pragma unroll
-            for (int e = 0; e < 32; ++e) {
+            for (int e = 0; e < NE; ++e) {
                 if (x[e] >= thr) {
                     const unsigned row = (unsigned)(row0 + (e >> 4) * TILE_ROWS + (e & 3) + 8 * ((e & 15) >> 2) + half4);
                     const unsigned slot = atomicAdd(lrec_count, 1u);
@@ -232,9 +270,9 @@ __global__ __launch_bounds__(512) void match_topk_coarse_kernel(TopkArgs a) {
     // flush the workgroup's records to the per-query lists (no DMA in flight any more)
     __syncthreads();
     const unsigned cnt = min(*lrec_count, (unsigned)TOPK_LREC_CAP);
-    for (unsigned i = threadIdx.x; i < cnt; i += 512) {
+    for (unsigned i = threadIdx.x; i < cnt; i += NWAVES * 64) {
         const uint2 r = lrec[i];
-        const size_t q = (size_t)qb * QBLOCK + (r.x >> 24);
+        const size_t q = (size_t)qb * Shape::QROWS + (r.x >> 24);
         const unsigned gs = atomicAdd(a.rec_cnt + q, 1u);
         if (gs < (unsigned)TOPK_RECORD_CAP) a.rec[q * TOPK_RECORD_CAP + gs] = make_uint2(r.x & 0xFFFFFFu, r.y);
     }
@@ -326,7 +364,7 @@ __global__ __launch_bounds__(256) void match_topk_finish_kernel(const float* __r
                                                                 const uint2* __restrict__ rec, int* __restrict__ counters,
                                                                 int* __restrict__ fb_list, int64_t* __restrict__ idx_out,
                                                                 float* __restrict__ sim_out) {
-    __shared__ float qn[384];
+    __shared__ float qn[TOPK_FAST_MAX_D];
     __shared__ double red_s[8];
     __shared__ long long red_j[8];
     const int64_t qi = blockIdx.x;
@@ -410,20 +448,31 @@ __global__ void topk_info_kernel(const int* __restrict__ counters, int fallback_
     info_out[3] = 0;
 }
 
-template <int KSTEPS>
+template <int KSTEPS, int NWAVES>
 int launch_topk_coarse(const TopkArgs& a, hipStream_t st) {
-    const int lds = TOPK_NBUF * KSTEPS * 1024 + TOPK_LREC_CAP * 8 + 16;
+    const int lds = TopkShape<NWAVES>::lds_bytes(KSTEPS);
     static std::atomic<unsigned long long> done{0ull};
     int dev = 0;
     (void)hipGetDevice(&dev);
-    VFM_TRY(vfm_allow_dynamic_lds(reinterpret_cast<const void*>(&match_topk_coarse_kernel<KSTEPS>), lds, dev, done));
-    hipLaunchKernelGGL((match_topk_coarse_kernel<KSTEPS>), dim3((unsigned)(a.nqb * a.nslices)), dim3(512), lds, st, a);
+    VFM_TRY(vfm_allow_dynamic_lds(reinterpret_cast<const void*>(&match_topk_coarse_kernel<KSTEPS, NWAVES>), lds, dev, done));
+    hipLaunchKernelGGL((match_topk_coarse_kernel<KSTEPS, NWAVES>), dim3((unsigned)(a.nqb * a.nslices)), dim3(NWAVES * 64), lds, st, a);
     VFM_CHECK_LAUNCH("match_topk_coarse_kernel");
     return VFM_OK;
 }
+inline int launch_topk_coarse(int d, const TopkArgs& a, hipStream_t st) {
+    switch (d) {
+        case 128: return launch_topk_coarse<8, 8>(a, st);
+        case 256: return launch_topk_coarse<16, 8>(a, st);
+        case 384: return launch_topk_coarse<24, 8>(a, st);
+        case 640: return launch_topk_coarse<40, 4>(a, st);
+        case 768: return launch_topk_coarse<48, 4>(a, st);
+    }
+    return vfm_fail(VFM_EINVAL, "match_topk: no coarse kernel for d = %d", d);
+}
+inline bool topk_wide(int d) { return d > 384; }   // the 4-wave form: 128 queries per workgroup
 
-inline bool topk_fast_shape(int64_t m, int d) {
-    return (d == 128 || d == 256 || d == 384) && m >= 1 && rows_padded(m) <= (1ll << 24);   // (a record holds the row in 24 bits)
+inline bool topk_fast_shape(int64_t m, int d) {   // (a record holds the row in 24 bits)
+    return (d == 128 || d == 256 || d == 384 || d == 640 || d == 768) && m >= 1 && rows_padded(m) <= (1ll << 24);
 }
 inline size_t topk_exact_bytes(int64_t n, int64_t m) {
     return vfm_align_up((size_t)n * sizeof(float), 256) + vfm_align_up((size_t)m * sizeof(float), 256) + 256;
@@ -438,6 +487,62 @@ inline size_t topk_bytes(int64_t n, int64_t m, int d, int prec_mode) {
     if (prec_mode == VFM_MATCH_FAST && topk_fast_shape(m, d) && n > 0)
         return vfm_match_prepared_bytes(n, d) + vfm_match_prepared_bytes(m, d) + carve_topk(nullptr, n).bytes;
     return topk_exact_bytes(n, m);
+}
+
+// FAST after the operands' preparation -- what vfm_match_ip_topk and vfm_match_ip_topk_prepared share: the counters cleared, the
+// coarse launches with the bound kernel between them, the finish, the all-pairs kernel for the overflowed queries, the read-back
+int run_topk_fast(const float* q, const Prepared& Q, int64_t n, const float* b, const Prepared& B, int64_t m, int d, int k,
+                  const TopkWs& w, int64_t* idx_out, float* sim_out, int32_t* info_out, hipStream_t st) {
+    const unsigned egrid = (unsigned)(n < 4096 ? n : 4096);
+    VFM_CHECK_HIP(hipMemsetAsync(w.counters, 0, w.zero_bytes, st));
+    TopkArgs a;
+    a.Qh = Q.tiles;
+    a.Bh = B.tiles;
+    a.qinv = Q.inv;
+    a.nq_tiles = (int)((n + TILE_ROWS - 1) / TILE_ROWS);
+    a.nqb = (int)(rows_padded(n) / (topk_wide(d) ? TopkShape<4>::QROWS : TopkShape<8>::QROWS));
+    a.m_valid = m;
+    a.n_valid = n;
+    a.k = k;
+    a.window = DEFAULT_WINDOW;
+    a.tau = w.tau;
+    a.rec_cnt = w.rec_cnt;
+    a.rec = w.rec;
+    // Launches.  Workgroups that run at the same time seed each other only weakly -- a lane publishes the k-th best of ITS rows --
+    // and a fresh bound records ~k (1 + ln(rows / k)) rows per half-wave: 64 unseeded slices would fill a query's list with warm-up
+    // alone (tools/sim_topk_records.py: 1166 records per query at 200 000 rows where one slice leaves 210).  So the map is walked in
+    // launches that each take three times the chunks already done -- TOPK_SEED_CHUNKS in one slice first --, every one sliced by the
+    // top-1 search's rule (choose_slices: whole rounds of workgroups, at least 8 chunks per slice), and between two launches
+    // match_topk_bound_kernel sets every query's bound to the k-th best score of the prefix.  Every slice then starts where a single
+    // workgroup would stand at the start of the launch: the record counts stay those of one slice (same tool: 213 at 200 000 rows).
+    const int total_chunks = (int)chunks_padded(m);
+    int max_slices = 0;
+    for (int done = 0; done < total_chunks;) {
+        const int want = done ? 3 * done : TOPK_SEED_CHUNKS;
+        a.chunk0 = done;
+        a.nchunks = total_chunks - done < want ? total_chunks - done : want;
+        a.nslices = done ? choose_slices(a.nqb, a.nchunks) : 1;
+        if (a.nslices > max_slices) max_slices = a.nslices;
+        VFM_TRY(launch_topk_coarse(d, a, st));
+        done += a.nchunks;
+        if (done < total_chunks) {
+            hipLaunchKernelGGL(match_topk_bound_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, k, (const unsigned*)w.rec_cnt,
+                               (const uint2*)w.rec, w.tau);
+            VFM_CHECK_LAUNCH("match_topk_bound_kernel");
+        }
+    }
+    hipLaunchKernelGGL(match_topk_finish_kernel, dim3((unsigned)n), dim3(256), 0, st, q, (const float*)Q.inv, b, (const float*)B.inv, n, m, d,
+                       k, (const unsigned*)w.rec_cnt, (const uint2*)w.rec, w.counters, w.fb_list, idx_out, sim_out);
+    VFM_CHECK_LAUNCH("match_topk_finish_kernel");
+    hipLaunchKernelGGL(match_topk_exact_kernel, dim3(egrid < 256u ? egrid : 256u), dim3(256), ((size_t)d * 4 + 15) & ~(size_t)15, st, q,
+                       (const float*)Q.inv, b, (const float*)B.inv, n, m, d, k, (const int*)w.fb_list,
+                       (const int*)(w.counters + CNT_FALLBACK), idx_out, sim_out);
+    VFM_CHECK_LAUNCH("match_topk_exact_kernel");
+    if (info_out) {
+        hipLaunchKernelGGL(topk_info_kernel, dim3(1), dim3(1), 0, st, (const int*)w.counters, 0, max_slices, info_out);
+        VFM_CHECK_LAUNCH("topk_info_kernel");
+    }
+    return VFM_OK;
 }
 
 }  // namespace
@@ -486,60 +591,35 @@ VFM_EXPORT int vfm_match_ip_topk(const float* q, int64_t n, const float* b, int6
         }
         return VFM_OK;
     }
-    // FAST: prepare both operands (fp16 fragment images + 1 / |row|), coarse pass, finish, all-pairs for the overflowed queries
+    // FAST: prepare both operands (fp16 fragment images + 1 / |row|), then run_topk_fast
     unsigned char* p = static_cast<unsigned char*>(ws);
     void* qprep = p;
     void* bprep = p + vfm_match_prepared_bytes(n, d);
     const TopkWs w = carve_topk(p + vfm_match_prepared_bytes(n, d) + vfm_match_prepared_bytes(m, d), n);
     VFM_TRY(do_prepare2(VFM_PREP_ENTRY_PREPARE2, 0, q, n, qprep, b, m, bprep, d, st));
     const Prepared Q = carve_prepared(qprep, n, d), B = carve_prepared(bprep, m, d);
-    VFM_CHECK_HIP(hipMemsetAsync(w.counters, 0, w.zero_bytes, st));
-    TopkArgs a;
-    a.Qh = Q.tiles;
-    a.Bh = B.tiles;
-    a.qinv = Q.inv;
-    a.nq_tiles = (int)((n + TILE_ROWS - 1) / TILE_ROWS);
-    a.nqb = (int)(rows_padded(n) / QBLOCK);
-    a.m_valid = m;
-    a.n_valid = n;
-    a.k = k;
-    a.window = DEFAULT_WINDOW;
-    a.tau = w.tau;
-    a.rec_cnt = w.rec_cnt;
-    a.rec = w.rec;
-    // Launches.  Workgroups that run at the same time seed each other only weakly -- a lane publishes the k-th best of ITS rows --
-    // and a fresh bound records ~k (1 + ln(rows / k)) rows per half-wave: 64 unseeded slices would fill a query's list with warm-up
-    // alone (tools/sim_topk_records.py: 1166 records per query at 200 000 rows where one slice leaves 210).  So the map is walked in
-    // launches that each take three times the chunks already done -- TOPK_SEED_CHUNKS in one slice first --, every one sliced by the
-    // top-1 search's rule (choose_slices: whole rounds of workgroups, at least 8 chunks per slice), and between two launches
-    // match_topk_bound_kernel sets every query's bound to the k-th best score of the prefix.  Every slice then starts where a single
-    // workgroup would stand at the start of the launch: the record counts stay those of one slice (same tool: 213 at 200 000 rows).
-    const int total_chunks = (int)chunks_padded(m);
-    int max_slices = 0;
-    for (int done = 0; done < total_chunks;) {
-        const int want = done ? 3 * done : TOPK_SEED_CHUNKS;
-        a.chunk0 = done;
-        a.nchunks = total_chunks - done < want ? total_chunks - done : want;
-        a.nslices = done ? choose_slices(a.nqb, a.nchunks) : 1;
-        if (a.nslices > max_slices) max_slices = a.nslices;
-        VFM_TRY(d == 128 ? launch_topk_coarse<8>(a, st) : d == 256 ? launch_topk_coarse<16>(a, st) : launch_topk_coarse<24>(a, st));
-        done += a.nchunks;
-        if (done < total_chunks) {
-            hipLaunchKernelGGL(match_topk_bound_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, n, k, (const unsigned*)w.rec_cnt,
-                               (const uint2*)w.rec, w.tau);
-            VFM_CHECK_LAUNCH("match_topk_bound_kernel");
-        }
-    }
-    hipLaunchKernelGGL(match_topk_finish_kernel, dim3((unsigned)n), dim3(256), 0, st, q, (const float*)Q.inv, b, (const float*)B.inv, n, m, d,
-                       k, (const unsigned*)w.rec_cnt, (const uint2*)w.rec, w.counters, w.fb_list, idx_out, sim_out);
-    VFM_CHECK_LAUNCH("match_topk_finish_kernel");
-    hipLaunchKernelGGL(match_topk_exact_kernel, dim3(egrid < 256u ? egrid : 256u), dim3(256), ((size_t)d * 4 + 15) & ~(size_t)15, st, q,
-                       (const float*)Q.inv, b, (const float*)B.inv, n, m, d, k, (const int*)w.fb_list,
-                       (const int*)(w.counters + CNT_FALLBACK), idx_out, sim_out);
-    VFM_CHECK_LAUNCH("match_topk_exact_kernel");
-    if (info_out) {
-        hipLaunchKernelGGL(topk_info_kernel, dim3(1), dim3(1), 0, st, (const int*)w.counters, 0, max_slices, info_out);
-        VFM_CHECK_LAUNCH("topk_info_kernel");
-    }
-    return VFM_OK;
+    return run_topk_fast(q, Q, n, b, B, m, d, k, w, idx_out, sim_out, info_out, st);
+}
+
+// the FAST search on operands prepared beforehand (include/vfmreg.h): no all-pairs fallback for a shape without a kernel
+VFM_EXPORT size_t vfm_match_ip_topk_prepared_workspace_bytes(int64_t n, int d, int k) {
+    if (!topk_args_ok(n, 1, d, k, VFM_MATCH_FAST) || !topk_fast_shape(1, d)) return 0;
+    return carve_topk(nullptr, n).bytes;
+}
+
+VFM_EXPORT int vfm_match_ip_topk_prepared(const float* q, const void* q_prepared, int64_t n, const float* b, const void* b_prepared,
+                                          int64_t m, int d, int k, int64_t* idx_out, float* sim_out, int32_t* info_out, void* ws,
+                                          size_t ws_bytes, vfm_stream_t stream) {
+    VFM_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "match_topk_prepared: k must be in 1 .. %d, got %d", TOPK_MAX, k);
+    VFM_CHECK_ARG(idx_out && sim_out, "match_topk_prepared: null output");
+    VFM_CHECK_ARG(n >= 0 && m >= 0 && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, "match_topk_prepared: bad row counts (n=%lld m=%lld)",
+                  (long long)n, (long long)m);
+    VFM_CHECK_ARG(topk_fast_shape(m, d), "match_topk_prepared: no kernel for this shape (d=%d must be 128, 256, 384, 640 or 768; m=%lld "
+                  "must be 1 .. 2^24 padded rows)", d, (long long)m);
+    if (n == 0) return VFM_OK;   // nothing to answer, nothing written
+    VFM_CHECK_ARG(q && q_prepared && b && b_prepared, "match_topk_prepared: null operand");
+    const TopkWs w = carve_topk(ws, n);
+    if (!ws || ws_bytes < w.bytes) return vfm_fail(VFM_EWORKSPACE, "match_topk_prepared: workspace too small");
+    const Prepared Q = carve_prepared(const_cast<void*>(q_prepared), n, d), B = carve_prepared(const_cast<void*>(b_prepared), m, d);
+    return run_topk_fast(q, Q, n, b, B, m, d, k, w, idx_out, sim_out, info_out, (hipStream_t)stream);
 }

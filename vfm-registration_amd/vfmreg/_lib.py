@@ -49,6 +49,8 @@ SIGNATURES = {
                                           c_vp]),
     "vfm_match_ip_topk_workspace_bytes": (C.c_size_t, [c_i64, c_i64, C.c_int, C.c_int, C.c_int]),
     "vfm_match_ip_topk": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vfm_match_ip_topk_prepared_workspace_bytes": (C.c_size_t, [c_i64, C.c_int, C.c_int]),
+    "vfm_match_ip_topk_prepared": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
     "vfm_match_prepared_bytes": (C.c_size_t, [c_i64, C.c_int]),
     "vfm_match_prepare": (C.c_int, [c_vp, c_i64, C.c_int, c_vp, c_vp]),
     "vfm_match_prepare2": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_int, c_vp]),

@@ -448,8 +448,16 @@ class VoxelHashMap:
             if q_rows.dim() != 2 or q_rows.shape[1] != b_desc.shape[1] + 3:
                 raise RuntimeError("Unable to cast Python instance to C++ type: expected %d columns" % (b_desc.shape[1] + 3))
             q_desc = q_rows[:, 3:].float().contiguous()            # VoxelHashMap.cpp:478-481
-        prec = ops.FAST if q_desc.shape[1] in (128, 256, 384) else ops.EXACT
-        idx, sim = ops.match_ip_topk(q_desc, b_desc, k, prec)
+        if q_desc.shape[1] in ops.MATCH_TOPK_FAST_WIDTHS and q_desc.shape[0] > 0 and b_desc.shape[0] > 0:
+            # the map's operand is prepared once and kept, under search_device's rule -- the top-1 and the k-best search of a map share
+            # one image --; a call prepares its query rows alone
+            if self._prep is None or self._prep.x is not b_desc:
+                self._prep = ops.PreparedRows(b_desc)
+                self._half = None   # not yet probed for this map
+            idx, sim = ops.match_ip_topk_prepared(ops.PreparedRows(q_desc), self._prep, k)
+        else:
+            prec = ops.FAST if q_desc.shape[1] in ops.MATCH_TOPK_FAST_WIDTHS else ops.EXACT
+            idx, sim = ops.match_ip_topk(q_desc, b_desc, k, prec)
         valid = ~(sim.double() < float(min_cosine_similarity)) & (idx >= 0)   # (the padding never passes a gate a cosine can reach)
         at = torch.nonzero(valid)                                  # row-major: query-major, rank-minor
         return at[:, 0], idx[valid], at[:, 1], sim

@@ -133,6 +133,34 @@ class PreparedRows:
                    "match_prepare")
 
 
+MATCH_TOPK_FAST_WIDTHS = (128, 256, 384, 640, 768)   # row widths the k-best search has a matrix-core kernel for
+
+
+def match_ip_topk_prepared(q: PreparedRows, b: PreparedRows, k: int, ws: Optional[torch.Tensor] = None, return_info: bool = False):
+    """``match_ip_topk(q.x, b.x, k, FAST)`` on operands prepared beforehand (vfm_match_ip_topk_prepared) -- for a map that is
+    prepared once and searched by many scans.  The same (idx, sim[, info]), bit for bit; both operands are left as they were.  A width
+    outside ``MATCH_TOPK_FAST_WIDTHS`` is refused: a prepared image means nothing to the all-pairs kernel."""
+    if q.d != b.d or q.d not in MATCH_TOPK_FAST_WIDTHS:
+        raise ValueError("Invalid shape")
+    k = int(k)
+    if not 1 <= k <= MATCH_TOPK_MAX_K:
+        raise ValueError(f"k must be in 1 .. {MATCH_TOPK_MAX_K}, got {k}")
+    lib = _lib.load()
+    dev = q.x.device
+    n = q.rows
+    need = lib.vfm_match_ip_topk_prepared_workspace_bytes(n, q.d, k)
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
+    sim = torch.empty((n, k), dtype=torch.float32, device=dev)
+    info = torch.zeros(4, dtype=torch.int32, device=dev) if return_info else None
+    if n > 0:
+        _lib.check(lib.vfm_match_ip_topk_prepared(q.x.data_ptr(), q.buf.data_ptr(), n, b.x.data_ptr(), b.buf.data_ptr(), b.rows, q.d, k,
+                                                  idx.data_ptr(), sim.data_ptr(), _ptr(info), ws.data_ptr(), ws.numel(), _stream()),
+                   "match_ip_topk_prepared")
+    return (idx, sim, info) if return_info else (idx, sim)
+
+
 def match_search(q: PreparedRows, b: PreparedRows, idx: Optional[torch.Tensor] = None,
                  sim: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
     lib = _lib.load()
