@@ -658,6 +658,31 @@ int vfm_icp_step_nearest_desc(const double *src, int64_t n, const double *T_host
                               const double *pts, const double *map_desc, const double *map_norm, const uint8_t *map_has,
                               int32_t n_voxels, double voxel_size, double max_dist, double *tgt_out, uint8_t *valid_out,
                               vfm_stream_t stream);
+
+/* The same search on descriptor rows kept in their own type next to a device-resident grid (the "weighted" local map of
+ * VoxelHashMap.update; csrc/icp_rows.hip).  Rows are contiguous [n][f], f >= 1, of elem_bytes = 4 (fp32) or 8 (fp64) -- one type for
+ * the source rows and the map's rows --, and everything is computed on their fp64 image (fp32 -> fp64 is exact): on that image the
+ * outputs equal those of vfm_icp_desc_stats / vfm_icp_step_nearest_desc bit for bit (sums in column order, no FMA, the same clamp, the
+ * first minimum in scan order -- voxels i, j, k ascending, then insertion order, strict '<' --, acceptance on the Euclidean distance of
+ * the chosen neighbour; a candidate whose cost is NaN never wins).
+ * vfm_icp_rows_stats: norm_out[i] (fp64[n]) = |row i|, has_out[i] (uint8[n]) = "element sum != 0".  n == 0: nothing is launched (the
+ * pointers may be NULL).
+ * vfm_icp_step_nearest_rows: src n x 3 fp64; T_host 16 fp64 in HOST memory, row-major, read at the call, applied to src first with the
+ * moved points written to src_out (n x 3 fp64; may equal src) -- NULL: the points are searched where they are and src_out is not
+ * touched --; src_desc [n][f], src_norm fp64[n], src_has uint8[n]: the source rows and their statistics; keys[n_voxels],
+ * start[n_voxels + 1], pts[nk][3] (nk = start[n_voxels]): the grid; map_desc [nk][f], map_norm fp64[nk], map_has uint8[nk]: the map's
+ * rows and statistics in the order of pts.  Written: tgt_out[n][3] (the chosen neighbour, (0, 0, 0) where there is none), valid_out[n]
+ * and, with T_host, src_out[n][3]; nothing else.  Rows are read in 16-byte units when f * elem_bytes % 16 == 0 and src_desc and
+ * map_desc are 16-byte aligned, element by element otherwise: the same values.  n_voxels == 0 is an empty map (keys, pts and map_* may
+ * be NULL): every valid_out is 0.  n <= 2^30; n == 0: nothing is launched.  One enqueue, no host synchronisation. */
+int vfm_icp_rows_stats(const void *desc, int32_t elem_bytes, int64_t n, int32_t f, double *norm_out, uint8_t *has_out,
+                       vfm_stream_t stream);
+int vfm_icp_step_nearest_rows(const double *src, int64_t n, const double *T_host, double *src_out, const void *src_desc,
+                              const double *src_norm, const uint8_t *src_has, int32_t elem_bytes, int32_t f, const int64_t *keys,
+                              const int32_t *start, const double *pts, const void *map_desc, const double *map_norm,
+                              const uint8_t *map_has, int32_t n_voxels, double voxel_size, double max_dist, double *tgt_out,
+                              uint8_t *valid_out, vfm_stream_t stream);
+
 /* BuildLinearSystem (src/kiss-icp/cpp/kiss_icp/core/Registration.cpp:96-141): out43 =
  * [J^T W J row-major 6x6 | J^T W r (6) | pair count], J = [I | -hat(s)], w = k^2/(k+|r|^2)^2. */
 int vfm_icp_build_system(const double *src, const double *tgt, const uint8_t *valid, int64_t n,

@@ -30,7 +30,7 @@ FILE_FLAGS = {"vit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # ... and vit.hip once more for its second part (vit_mlp_kernel: 192 accumulators in the accumulation file), without that option
 EXTRA_OBJECTS = [("vit.hip", ["-DVFM_VIT_PART=1"], "vit_mlp.hip.o")]
 SOURCES = ["error.cpp", "config.cpp", "match_api.hip", "match_prep.hip", "match_coarse_f16.hip", "match_coarse_i8.hip", "match_coarse_mx6.hip", "match_finish.hip",
-           "match_topk.hip", "match_l2.hip", "match_l2_narrow.hip", "ransac.hip", "project.hip", "camera.hip", "vit.hip", "icp.hip", "voxel.hip", "fpfh.hip", "nn3.hip", "hdbscan.hip", "hdbscan_host.cpp", "pca.hip", "odometry.hip", "teaser.hip", "teaser_host.cpp"]
+           "match_topk.hip", "match_l2.hip", "match_l2_narrow.hip", "ransac.hip", "project.hip", "camera.hip", "vit.hip", "icp.hip", "icp_rows.hip", "voxel.hip", "fpfh.hip", "nn3.hip", "hdbscan.hip", "hdbscan_host.cpp", "pca.hip", "odometry.hip", "teaser.hip", "teaser_host.cpp"]
 
 
 def _stale(target: Path, deps) -> bool:

@@ -112,6 +112,9 @@ SIGNATURES = {
     "vfm_icp_desc_stats": (C.c_int, [c_vp, c_i64, C.c_int32, c_vp, c_vp, c_vp]),
     "vfm_icp_step_nearest_desc": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int32,
                                             C.c_double, C.c_double, c_vp, c_vp, c_vp]),
+    "vfm_icp_rows_stats": (C.c_int, [c_vp, C.c_int32, c_i64, C.c_int32, c_vp, c_vp, c_vp]),
+    "vfm_icp_step_nearest_rows": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int32, C.c_int32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            C.c_int32, C.c_double, C.c_double, c_vp, c_vp, c_vp]),
     "vfm_range_crop": (C.c_int, [c_vp, c_i64, c_i64, C.c_double, C.c_double, c_vp, c_vp, c_vp]),
     "vfm_deskew_scan": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "vfm_icp_grid_update_workspace_bytes": (C.c_size_t, [C.c_int32, c_i64, c_i64]),

@@ -442,12 +442,83 @@ def _register_frame_xd(points: np.ndarray, voxel_map, initial_guess: np.ndarray,
     return T_icp @ initial_guess
 
 
+def register_frame_weighted_device(src_desc: torch.Tensor, src_xyz: torch.Tensor, voxel_map, initial_guess: np.ndarray,
+                                   max_correspondance_distance: float, kernel: float) -> np.ndarray:
+    """RegisterFrame(std::vector<Eigen::VectorXd> ...) (Registration.cpp:384-423) against a map made with descriptor_mode="weighted", on a
+    scan that is on the device: ``src_desc`` [n, D] (float32 / float64, contiguous) and its coordinates ``src_xyz`` fp64 [n, 3].  The map is
+    searched where it lives -- its grid, its descriptor rows in their own dtype and their statistics (``VoxelHashMap.weighted_operand``);
+    nothing is downloaded or sorted again -- by csrc/icp_rows.hip; the source statistics are computed once.  An iteration = the search's
+    launch (which also applies the previous update), the normal equations' and one 344-byte read-back; every iterate equals
+    oracle.register_frame_xd's bit for bit."""
+    from .mapping import VoxelHashMap
+    lib = _lib.load()
+    st = ops._stream()
+    initial_guess = np.ascontiguousarray(initial_guess, dtype=np.float64)
+    operand = voxel_map.weighted_operand()
+    n = src_xyz.shape[0]
+    if operand is None or n == 0:
+        return initial_guess                                             # Registration.cpp:389
+    g, mdesc, mnorm, mhas = operand
+    if src_desc.dim() != 2 or src_desc.shape[0] != n or src_desc.shape[1] != mdesc.shape[1]:
+        raise ValueError("Invalid shape")
+    if src_desc.dtype != mdesc.dtype:                                    # one type for both: double, as pybind's cast would give
+        src_desc, mdesc = src_desc.double(), mdesc.double()
+    src_desc = src_desc.contiguous()
+    snorm, shas = ops.icp_rows_stats(src_desc)
+    cur = src_xyz
+    source = torch.empty_like(src_xyz)
+    tgt = torch.empty_like(src_xyz)
+    valid = torch.empty(n, dtype=torch.uint8, device=src_xyz.device)
+    out = torch.empty(43, dtype=torch.float64, device=src_xyz.device)
+    out_h = torch.empty(43, dtype=torch.float64).pin_memory()
+    step = initial_guess                                                 # Equation (9), applied by the first launch
+    T_icp = np.eye(4)
+    for j in range(MAX_NUM_ITERATIONS):
+        ops.icp_step_nearest_rows(cur, step, src_desc, snorm, shas, g.keys, g.start, g.pts, mdesc, mnorm, mhas, g.voxel_size,
+                                  max_correspondance_distance, src_out=source, tgt=tgt, valid=valid)
+        cur = source                                                     # (in place from the second iteration on)
+        _lib.check(lib.vfm_icp_build_system(source.data_ptr(), tgt.data_ptr(), valid.data_ptr(), n, float(kernel), out.data_ptr(), st),
+                   "icp_build_system")
+        out_h.copy_(out, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        o = out_h.numpy()
+        if j == 0 and not VoxelHashMap.quiet:
+            print(f"[XD] [{j}] correspondences {int(o[42])}")          # Registration.cpp:400
+        if o[42] == 0:
+            break
+        dx = _solve6(o[:36].reshape(6, 6), -o[36:42])
+        if dx is None:
+            break
+        estimation = se3_exp(dx)
+        step = estimation
+        T_icp = estimation @ T_icp
+        if np.linalg.norm(dx) < ESTIMATION_THRESHOLD:
+            break
+    return T_icp @ initial_guess
+
+
+def _register_frame_weighted(points: np.ndarray, voxel_map, initial_guess, max_correspondance_distance: float, kernel: float):
+    """``register_frame`` on rows of 3 + D columns against a "weighted" map: the rows go up once, in their own dtype"""
+    from .voxelization import to_device_rows
+    ncols = voxel_map.width_n()
+    if ncols is not None and points.shape[1] != ncols:
+        raise ValueError("Invalid shape")
+    if voxel_map.empty_x() or len(points) == 0:
+        return initial_guess                                             # Registration.cpp:389
+    rows, xyz = to_device_rows(points)
+    return register_frame_weighted_device(rows[:, 3:].contiguous(), xyz, voxel_map, initial_guess, max_correspondance_distance, kernel)
+
+
 def register_frame(points: np.ndarray, voxel_map, initial_guess: np.ndarray, max_correspondance_distance: float,
                    kernel: float, src_=None, tgt_=None):
     points = np.asarray(points)
     if points.ndim != 2 or points.shape[1] < 3:
         raise ValueError("Invalid shape")  # registration.py:43
     initial_guess = np.ascontiguousarray(initial_guess, dtype=np.float64)
+    if points.shape[1] != 3 and getattr(voxel_map, "descriptor_mode", "seeded") == "weighted":
+        # a map made with descriptor_mode="weighted" keeps its wide rows as the reference's map_x_: rows of every width, 387 included,
+        # take RegisterFrame(VectorXd ...) against the device-resident grid
+        return _register_frame_weighted(points, voxel_map, initial_guess, max_correspondance_distance, kernel)
     if points.shape[1] != 3:
         # registration.py:37-66: rows of _point_size() = 387 columns take the descriptor-seeded RegisterFrame and return the surviving pairs
         # when the caller passed src_ / tgt_; every other width > 3 takes RegisterFrame(VectorXd ...) (Registration.cpp:384-423, round 6):

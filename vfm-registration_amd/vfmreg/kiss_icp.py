@@ -15,7 +15,14 @@ reference's behaviour), as the C++ pipeline (KissICP.cpp:69-103) and upstream do
 ``frame_downsample`` keep their 384 descriptor columns, the pose comes from the descriptor-seeded RegisterFrame
 (``icp._register_frame_nd_device``) against a local map that carries descriptors, and ``VoxelHashMap.update`` moves the map's descriptor
 rows along with its points (``vfm_icp_grid_update_src`` + ``vfm_rows_merge``).  The map's search operand is prepared again for the whole
-map every frame.  Frames of another width would need the reference's ``VectorXd`` local map, which is not built."""
+map every frame.  In this mode (``descriptor_mode="seeded"``, the default) frames of another width are refused.
+
+``KissICP(config, map_update_threshold, descriptor_mode="weighted")`` is the reference's ``VectorXd`` local map (``map_x_``) and the paper's
+descriptor-weighted ICP: ``use_descriptors=True`` then takes frames of 3 + D columns, D >= 1 (387 included), through the same stages, keeps
+them in a local map of that width (``VoxelHashMap(descriptor_mode="weighted")``) and registers with RegisterFrame(VectorXd ...)
+(Registration.cpp:384-423; ``icp.register_frame_weighted_device``, csrc/icp_rows.hip), whose search picks the neighbour that minimises
+``|dxyz|^2 * clamp(0.5 (1 - cos), 0.01, 1)``; the initial guess is returned while ``empty_x()`` (Registration.cpp:389).  The first frame
+fixes the width.  ``use_descriptors=False`` is the same in both modes."""
 from __future__ import annotations
 
 import time
@@ -25,7 +32,7 @@ import torch
 
 from . import icp, ops
 from .deskew import get_motion_compensator
-from .mapping import get_voxel_hash_map
+from .mapping import check_descriptor_mode, get_voxel_hash_map
 from .preprocess import get_preprocessor
 from .threshold import get_threshold_estimator
 
@@ -33,12 +40,13 @@ from .threshold import get_threshold_estimator
 class KissICP:
     CHAIN_MAX = 1 << 18   # the one-launch voxel level's limit (vfm_voxel_robin_level)
 
-    def __init__(self, config, map_update_threshold=0.0):
+    def __init__(self, config, map_update_threshold=0.0, descriptor_mode="seeded"):
+        self.descriptor_mode = check_descriptor_mode(descriptor_mode)     # what ``use_descriptors=True`` runs (the module docstring)
         self.poses = []
         self.config = config
         self.compensator = get_motion_compensator(config)
         self.adaptive_threshold = get_threshold_estimator(self.config)
-        self.local_map = get_voxel_hash_map(self.config)
+        self.local_map = get_voxel_hash_map(self.config, descriptor_mode)
         self.preprocess = get_preprocessor(self.config)
         self.map_update_threshold = map_update_threshold
         self.profile = False      # True: synchronise between the stages and keep their wall-clock times in ``timings``
@@ -152,7 +160,12 @@ class KissICP:
         frame = np.asarray(frame)
         if frame.ndim != 2 or frame.shape[1] < 3:
             raise ValueError("Invalid shape")
-        if frame.shape[1] != icp.POINT_SIZE:     # (before anything is uploaded)
+        weighted = self.descriptor_mode == "weighted"
+        if weighted:                             # (before anything is uploaded) xyz + D >= 1 descriptor columns, the width of the map's rows
+            held = self.local_map.width_n()
+            if frame.shape[1] < 4 or (held is not None and held != frame.shape[1]):
+                raise ValueError("Invalid shape")
+        elif frame.shape[1] != icp.POINT_SIZE:   # (before anything is uploaded)
             raise NotImplementedError(f"use_descriptors=True: descriptor odometry takes frames of {icp.POINT_SIZE} columns (xyz + "
                                       f"{icp.POINT_SIZE - 3} descriptor columns), got {frame.shape[1]}; the VectorXd local map of other "
                                       "widths is not built")
@@ -187,7 +200,13 @@ class KissICP:
         last_pose = self.poses[-1] if self.poses else np.eye(4)
         initial_guess = last_pose @ prediction
 
-        if source_rows.shape[0] == 0 or self.local_map.empty_n():
+        if weighted:
+            if source_rows.shape[0] == 0 or self.local_map.empty_x():
+                new_pose = np.ascontiguousarray(initial_guess, dtype=np.float64)   # Registration.cpp:389
+            else:
+                new_pose = icp.register_frame_weighted_device(source_rows[:, 3:].contiguous(), source_xyz, self.local_map, initial_guess,
+                                                              3 * sigma, sigma / 3)
+        elif source_rows.shape[0] == 0 or self.local_map.empty_n():
             new_pose = np.ascontiguousarray(initial_guess, dtype=np.float64)       # Registration.cpp:204
         else:
             new_pose, _, _ = icp._register_frame_nd_device(source_rows, source_xyz, self.local_map, initial_guess, 3 * sigma, sigma / 3)

@@ -17,6 +17,11 @@ of registration_node.py:288-317 unnecessary.
 the sorted-key grid ICP searches, updated in place on the device (csrc/odometry.hip ``vfm_icp_grid_update``).  The 387-column map keeps
 its descriptor rows next to that grid, in the grid's order, and every update moves them along with the points
 (``vfm_icp_grid_update_src`` + ``vfm_rows_merge``).
+
+``descriptor_mode="weighted"`` (default ``"seeded"``: everything above) makes the wide rows the reference's ``map_x_``
+(VoxelHashMap.cpp:717-731, 759-770, 789-795): rows of any width 3 + D, D >= 1, are kept as such a local map -- the same grid, the same two
+enqueues -- and searched by the descriptor-weighted RegisterFrame (``icp.register_frame`` on the map, csrc/icp_rows.hip), for which the map
+keeps every row's norm and "element sum != 0" flag, computed on the device (``weighted_operand``).  ``empty_x()`` tells whether it holds rows.
 """
 from __future__ import annotations
 
@@ -29,16 +34,28 @@ from . import ops
 from .voxelization import to_device_rows
 
 
-def get_voxel_hash_map(config):
+DESCRIPTOR_MODES = ("seeded", "weighted")
+
+
+def check_descriptor_mode(mode) -> str:
+    if mode not in DESCRIPTOR_MODES:
+        raise ValueError(f"descriptor_mode: expected one of {DESCRIPTOR_MODES}, got {mode!r}")
+    return mode
+
+
+def get_voxel_hash_map(config, descriptor_mode="seeded"):
     return VoxelHashMap(voxel_size=config.mapping.voxel_size, max_distance=config.data.max_range,
-                        max_points_per_voxel=config.mapping.max_points_per_voxel)
+                        max_points_per_voxel=config.mapping.max_points_per_voxel, descriptor_mode=descriptor_mode)
 
 
 class VoxelHashMap:
     quiet = False  # the reference prints a stats line per search (VoxelHashMap.cpp:613-616)
     HALF_LIMIT = 24.0  # surviving chunks per query up to which a map's searches take the half-width coarse pass (pipeline.py's rule)
 
-    def __init__(self, voxel_size: float, max_distance: float, max_points_per_voxel: int):
+    def __init__(self, voxel_size: float, max_distance: float, max_points_per_voxel: int, descriptor_mode: str = "seeded"):
+        # "seeded": wide rows are the reference's map_n_ (387 columns as a local map, the descriptor-seeded RegisterFrame); "weighted": they
+        # are its map_x_ -- rows of any width 3 + D, D >= 1, as a local map, searched by the descriptor-weighted RegisterFrame
+        self.descriptor_mode = check_descriptor_mode(descriptor_mode)
         self.voxel_size = float(voxel_size)
         self.max_distance = float(max_distance)
         self.max_points_per_voxel = int(max_points_per_voxel)
@@ -61,9 +78,11 @@ class VoxelHashMap:
 
     def _drop_icp_grids(self):
         # the ICP grids register_frame keeps with the map (icp._grid_of, icp._register_frame_xd) are keyed on the kept-row count only:
-        # a map refilled with as many other rows would be searched through the old coordinates and descriptors
+        # a map refilled with as many other rows would be searched through the old coordinates and descriptors.  The weighted search's
+        # norms and flags (weighted_operand) go with them, and are tied to the tensor of rows they were computed from besides
         self.__dict__.pop("_icp_grid", None)
         self.__dict__.pop("_icp_desc_grid", None)
+        self.__dict__.pop("_wide_stats", None)
 
     @staticmethod
     def _kind(width: int) -> str:
@@ -79,6 +98,10 @@ class VoxelHashMap:
     def empty_n(self):
         return not self._chunks.get("n")
 
+    def empty_x(self):
+        """VoxelHashMap::Empty_x: whether map_x_ -- the wide rows of a "weighted" map -- holds nothing (a "seeded" map has no map_x_)"""
+        return self.descriptor_mode != "weighted" or self.empty_n()
+
     def add_points(self, points: np.ndarray):
         points = np.asarray(points)
         if points.ndim != 2 or points.shape[1] < 3:
@@ -86,6 +109,8 @@ class VoxelHashMap:
         if len(points) == 0:
             return
         kind = self._kind(points.shape[1])
+        if kind == "n" and self.width_n() not in (None, points.shape[1]):
+            raise ValueError("Invalid shape")      # (before anything is uploaded)
         if (kind == "n" and not self._chunks.get(kind) and len(points) >= self.OVERLAP_UPLOAD_FROM and points.dtype in (np.float32, np.float64)
                 and torch.cuda.is_available()):
             return self._add_first_block_overlapped(points)
@@ -186,22 +211,28 @@ class VoxelHashMap:
     # and the grid's order -- (voxel key, insertion), the row numbering of the searches from then on (ties to the lower row).  The update
     # says where every output point came from and vfm_rows_merge moves the rows: two enqueues, one 6-int read-back.  A map filled by
     # add_points converts at its first update (its kept rows enter an empty grid in insertion order).  Other widths (the reference's map_x_)
-    # are not kept as a local map.
+    # are kept as a local map by a map made with descriptor_mode="weighted" only: there every width 3 + D, D >= 1, takes this path.
     def update(self, points, pose: np.ndarray = np.eye(4)):
         """mapping.py:59-75 for 3-column points (numpy, or fp64 [n, 3] on the device) and for rows of icp.POINT_SIZE = 387 columns (numpy
-        or a device tensor, float32 or float64)"""
+        or a device tensor, float32 or float64); a map made with descriptor_mode="weighted" takes rows of any width 3 + D, D >= 1, instead
+        -- the first wide rows fix the width, another one later is ValueError("Invalid shape")"""
         from .icp import POINT_SIZE
         if not isinstance(points, torch.Tensor):
             points = np.asarray(points)
         if points.ndim != 2 or points.shape[1] < 3:
             raise ValueError("Invalid shape")  # mapping.py:73
-        if points.shape[1] not in (3, POINT_SIZE):
+        weighted = self.descriptor_mode == "weighted"
+        if weighted and points.shape[1] > 3:
+            have = self.width_n()
+            if have is not None and have != points.shape[1]:      # (before anything is uploaded)
+                raise ValueError("Invalid shape")
+        elif points.shape[1] not in (3, POINT_SIZE):
             raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {points.shape[1]} (only 3-column "
                                       f"points and {POINT_SIZE}-column rows are kept in a device-resident local map)")
         pose = np.ascontiguousarray(pose, dtype=np.float64)
         if pose.shape != (4, 4):
             raise ValueError("expected a 4 x 4 pose")
-        if points.shape[1] == POINT_SIZE:
+        if points.shape[1] == POINT_SIZE or (weighted and points.shape[1] > 3):
             if isinstance(points, torch.Tensor):
                 if not points.is_cuda:
                     raise RuntimeError("points: expected a tensor on the ROCm device (no CPU path exists)")
@@ -219,7 +250,7 @@ class VoxelHashMap:
         origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
         if origin.shape != (3,):
             raise ValueError("expected an origin of 3 values")
-        if self.empty_n() or self.width_n() - 3 != self._descriptor_width():     # (rows of another width are no local map: left alone)
+        if self.empty_n() or not self._is_local_width(self.width_n() - 3):      # (rows of another width are no local map: left alone)
             return self._grid_update(None, None, origin)
         first = None
         if not self.empty():
@@ -233,6 +264,10 @@ class VoxelHashMap:
     def _descriptor_width() -> int:
         from .icp import POINT_SIZE
         return POINT_SIZE - 3
+
+    def _is_local_width(self, d: int) -> bool:
+        """whether rows of ``d`` descriptor columns are kept as a device-resident local map"""
+        return d >= 1 if self.descriptor_mode == "weighted" else d == self._descriptor_width()
 
     def _read_update_info(self, info):
         from .icp import OUT_OF_RANGE_MESSAGE
@@ -266,6 +301,7 @@ class VoxelHashMap:
         self._half = None
         self._xyz = None
         self.__dict__.pop("_icp_desc_grid", None)
+        self.__dict__.pop("_wide_stats", None)     # (the weighted search's norms and flags: of the rows that were here before)
         self.last_update = dict(points_added=added, voxels_removed=voxels_removed, points_removed=points_removed)
 
     def _grid_update_n(self, desc, xyz, pose, origin):
@@ -273,15 +309,7 @@ class VoxelHashMap:
         (None: no new points), ``pose`` a host 4 x 4 or None, ``origin`` 3 host values or None (nothing is removed)"""
         if desc is not None and desc.shape[0] == 0:
             desc = xyz = None
-        if self._wide_grid is None and not self.empty_n():
-            # the first update of a map add_points filled: every stored row is a kept one, so they all enter an empty grid, in insertion order
-            chunks = self._chunks["n"]
-            rows = torch.cat([r for r, _ in chunks], dim=0) if len(chunks) > 1 else chunks[0][0]
-            old_xyz = torch.cat([x for _, x in chunks], dim=0) if len(chunks) > 1 else chunks[0][1]
-            if rows.shape[1] - 3 != self._descriptor_width():
-                raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {rows.shape[1]}")
-            self._install_wide(ops.icp_grid_update(None, None, None, old_xyz.contiguous(), None, self.voxel_size, self.max_points_per_voxel, None,
-                                                   self.max_distance, rows_new=rows[:, 3:].contiguous()))
+        self._ensure_wide_grid()
         g = self._wide_grid
         if g is None and desc is None:
             self.last_update = dict(points_added=0, voxels_removed=0, points_removed=0)
@@ -295,6 +323,36 @@ class VoxelHashMap:
         out = ops.icp_grid_update(None if g is None else g.keys, None if g is None else g.start, None if g is None else g.pts, xyz, pose,
                                   self.voxel_size, self.max_points_per_voxel, origin, self.max_distance, rows_old=old, rows_new=desc)
         self._install_wide(out)
+
+    def _ensure_wide_grid(self):
+        """a wide map that add_points filled becomes the grid + descriptor columns an updated map is (nothing happens to one that is, or
+        to an empty one)"""
+        if self._wide_grid is None and not self.empty_n():
+            # the first update of a map add_points filled: every stored row is a kept one, so they all enter an empty grid, in insertion order
+            chunks = self._chunks["n"]
+            rows = torch.cat([r for r, _ in chunks], dim=0) if len(chunks) > 1 else chunks[0][0]
+            old_xyz = torch.cat([x for _, x in chunks], dim=0) if len(chunks) > 1 else chunks[0][1]
+            if not self._is_local_width(rows.shape[1] - 3):
+                raise NotImplementedError(f"update of a local map that carries descriptors: rows of width {rows.shape[1]}")
+            self._install_wide(ops.icp_grid_update(None, None, None, old_xyz.contiguous(), None, self.voxel_size, self.max_points_per_voxel, None,
+                                                   self.max_distance, rows_new=rows[:, 3:].contiguous()))
+
+    def weighted_operand(self):
+        """What the descriptor-weighted search reads of a "weighted" map, all on the device: (grid, descriptor rows [n_kept, D] in the
+        grid's order and the rows' dtype, norm fp64[n_kept], "element sum != 0" uint8[n_kept]).  The statistics are computed on the device
+        for the whole map (``vfm_icp_rows_stats``) at the first search after the map changed and kept until it changes again: they belong
+        to the very tensor of rows they were computed from (profiles/odometry_weighted_timing.md has the figures behind "recomputed, not
+        carried through the update").  A map that add_points filled becomes a grid here, as at its first update."""
+        if self.descriptor_mode != "weighted":
+            raise RuntimeError("weighted_operand: the map was not made with descriptor_mode=\"weighted\"")
+        self._ensure_wide_grid()
+        if self._wide_grid is None:
+            return None
+        desc = self._chunks["n"][0][0]
+        stats = self.__dict__.get("_wide_stats")
+        if stats is None or stats[0] is not desc:
+            stats = self._wide_stats = (desc,) + ops.icp_rows_stats(desc)
+        return self._wide_grid, desc, stats[1], stats[2]
 
     def _grid_update(self, xyz, pose, origin):
         from .icp import VoxelGridDevice, _grid_of

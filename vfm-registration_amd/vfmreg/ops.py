@@ -1169,3 +1169,88 @@ def icp_grid_update(keys: Optional[torch.Tensor], start: Optional[torch.Tensor],
     else:
         rows = rows_merge(rows_old if nk else None, rows_new if m else None, src, info[1:])
     return dict(keys=keys_out, start=start_out, pts=pts_out, info=info, src=src, rows=rows)
+
+
+# ------------------------------------------------------------------------------------- descriptor-weighted ICP search (csrc/icp_rows.hip)
+def _desc_rows(rows: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise RuntimeError(f"{name}: expected a tensor on the ROCm device (no CPU path exists)")
+    if rows.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name}: expected float32 or float64 rows, got {rows.dtype}")
+    if rows.dim() != 2 or rows.shape[1] < 1:
+        raise ValueError("Invalid shape")
+    if not rows.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return rows
+
+
+def icp_rows_stats(desc: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vfm_icp_rows_stats: (norm fp64[n], has uint8[n]) of the descriptor rows ``desc`` [n, f >= 1] (float32 or float64, contiguous, on the
+    device) -- |row| and "element sum != 0" on the rows' fp64 image, sums in column order.  No read-back."""
+    _desc_rows(desc, "desc")
+    n, f = desc.shape
+    norm = torch.empty(n, dtype=torch.float64, device=desc.device)
+    has = torch.empty(n, dtype=torch.uint8, device=desc.device)
+    _lib.check(_lib.load().vfm_icp_rows_stats(desc.data_ptr() if n else None, desc.element_size(), n, f, norm.data_ptr() if n else None,
+                                              has.data_ptr() if n else None, _stream()), "icp_rows_stats")
+    return norm, has
+
+
+def icp_step_nearest_rows(src: torch.Tensor, T, src_desc: torch.Tensor, src_norm: torch.Tensor, src_has: torch.Tensor, keys: torch.Tensor,
+                          start: torch.Tensor, pts: torch.Tensor, map_desc: torch.Tensor, map_norm: torch.Tensor, map_has: torch.Tensor,
+                          voxel_size: float, max_dist: float, src_out: Optional[torch.Tensor] = None, tgt: Optional[torch.Tensor] = None,
+                          valid: Optional[torch.Tensor] = None):
+    """vfm_icp_step_nearest_rows: one iteration's search of the descriptor-weighted ICP.  ``src`` fp64 [n, 3]; ``T``: a 4 x 4 on the host
+    applied to ``src`` first (None: the points as they are); ``src_desc`` [n, f] / ``map_desc`` [nk, f]: descriptor rows of ONE dtype
+    (float32 or float64) with their statistics (``icp_rows_stats``); ``keys`` int64[nv], ``start`` int32[nv + 1], ``pts`` fp64 [nk, 3]: the
+    grid, its rows in the order of ``map_desc``.  Returns (moved fp64 [n, 3] -- ``src`` itself without ``T`` --, tgt fp64 [n, 3], valid
+    uint8[n]); ``src_out`` (may be ``src``), ``tgt`` and ``valid`` are written where given.  No read-back."""
+    _chk(src, torch.float64, "src")
+    if src.dim() != 2 or src.shape[1] != 3:
+        raise ValueError("Invalid shape")
+    n = int(src.shape[0])
+    _desc_rows(src_desc, "src_desc")
+    _desc_rows(map_desc, "map_desc")
+    if map_desc.dtype != src_desc.dtype:
+        raise TypeError(f"map_desc: expected the source rows' {src_desc.dtype}, got {map_desc.dtype}")
+    f = int(src_desc.shape[1])
+    if map_desc.shape[1] != f or src_desc.shape[0] != n:
+        raise ValueError("Invalid shape")
+    _chk(keys, torch.int64, "keys")
+    _chk(start, torch.int32, "start")
+    _chk(pts, torch.float64, "pts")
+    nv, nk = int(keys.shape[0]), int(map_desc.shape[0])
+    if start.shape[0] != nv + 1 or pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] != nk:
+        raise ValueError("expected start [nv + 1] and one descriptor row per grid point")
+    for t, dtype, name, rows in ((src_norm, torch.float64, "src_norm", n), (src_has, torch.uint8, "src_has", n),
+                                 (map_norm, torch.float64, "map_norm", nk), (map_has, torch.uint8, "map_has", nk)):
+        _chk(t, dtype, name)
+        if t.dim() != 1 or t.shape[0] != rows:
+            raise ValueError(f"{name}: expected one entry per row")
+    Th = None if T is None else np.ascontiguousarray(T, dtype=np.float64)
+    if Th is not None and Th.shape != (4, 4):
+        raise ValueError("expected a 4 x 4 pose")
+    if Th is None:
+        src_out = src
+    elif src_out is None:
+        src_out = torch.empty_like(src)
+    else:
+        _chk(src_out, torch.float64, "src_out")
+        if src_out.shape != src.shape:
+            raise ValueError("Invalid shape")
+    if tgt is None:
+        tgt = torch.empty((n, 3), dtype=torch.float64, device=src.device)
+    if valid is None:
+        valid = torch.empty(n, dtype=torch.uint8, device=src.device)
+    _chk(tgt, torch.float64, "tgt")
+    _chk(valid, torch.uint8, "valid")
+    if tgt.shape != src.shape or valid.shape != (n,):
+        raise ValueError("Invalid shape")
+    if n:
+        _lib.check(_lib.load().vfm_icp_step_nearest_rows(
+            src.data_ptr(), n, None if Th is None else Th.ctypes.data, None if Th is None else src_out.data_ptr(), src_desc.data_ptr(),
+            src_norm.data_ptr(), src_has.data_ptr(), src_desc.element_size(), f, keys.data_ptr() if nv else None, start.data_ptr(),
+            pts.data_ptr() if nv else None, map_desc.data_ptr() if nv else None, map_norm.data_ptr() if nv else None,
+            map_has.data_ptr() if nv else None, nv, float(voxel_size), float(max_dist), tgt.data_ptr(), valid.data_ptr(), _stream()),
+            "icp_step_nearest_rows")
+    return src_out, tgt, valid
