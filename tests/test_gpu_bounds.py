@@ -7,7 +7,7 @@ reports, and every call must show five properties:
   2. inputs unchanged -- byte for byte (documented in/out arguments excepted);
   3. no dependence on earlier contents -- outputs pre-filled with 0 and with -1 / NaN (bytes 0xFF) give the same result; a workspace
      used first by a LARGER call of the same entry point (stale counters that are plausible in-range values, as product reuse leaves
-     them) gives the same result as a fresh, zeroed one;
+     them) gives the same result as a fresh, zeroed one -- and so does, for the k-best search, a fresh one filled with bytes 0xFF;
   4. no reads past the ends of inputs -- guards of every input poisoned (NaN for floating-point data, 0 -- a valid index -- for index
      arrays, 0x00 then 0xFF for images, 0x00 for opaque prepared operands) give the same result, bit for bit;
   5. still the reference answer at these edge shapes (oracle.oracle, tests/fpfh_oracle.py; for the ViT the unguarded forward).
@@ -88,7 +88,7 @@ def _bound(cfg):
     return L.using(L.Config(**cfg))
 
 
-def _run(case, out_byte=0x00, poison_round=None, ws=None, tag=""):
+def _run(case, out_byte=0x00, poison_round=None, ws=None, tag="", ws_byte=0x00):
     where = f"{case.name} [{tag}]"
     bufs = {}
     for i, (name, s) in enumerate(case.bufs.items()):
@@ -101,7 +101,7 @@ def _run(case, out_byte=0x00, poison_round=None, ws=None, tag=""):
             g.poison_guards(s.poison[min(poison_round, len(s.poison) - 1)] if s.role == IN else ZERO)
         bufs[name] = g
     if ws is None and case.ws_bytes is not None:
-        ws = GuardedBuffer(case.ws_bytes, torch.uint8, seed=97).fill_bytes(0)
+        ws = GuardedBuffer(case.ws_bytes, torch.uint8, seed=97).fill_bytes(ws_byte)
     with _bound(case.cfg):
         case.call(bufs, ws)
     torch.cuda.synchronize()
@@ -129,8 +129,9 @@ def _same(case, A, B, what):
                         f"{b.reshape(-1)[first]})")
 
 
-def check_case(case):
-    """The five properties of the module docstring for one call."""
+def check_case(case, ws_ff=False):
+    """The five properties of the module docstring for one call.  ``ws_ff``: one more run, in a fresh workspace pre-filled with bytes
+    0xFF instead of 0 (counts of 4 billion, bounds above every score, list entries of -1), must give the same outputs."""
     A = _run(case, 0x00, tag="outputs pre-filled with 0")
     B = _run(case, 0xFF, tag="outputs pre-filled with -1 / NaN")
     _same(case, A, B, "between outputs pre-filled with 0 and with -1 / NaN")
@@ -145,6 +146,9 @@ def check_case(case):
         _run(big, 0x00, ws=W, tag="the larger call")
         R = _run(case, 0x00, ws=W, tag="workspace reused from a larger call")
         _same(case, A, R, "in a workspace used by a larger call first")
+    if ws_ff and case.ws_bytes is not None:
+        F = _run(case, 0x00, ws_byte=0xFF, tag="workspace pre-filled with bytes 0xFF")
+        _same(case, A, F, "in a workspace pre-filled with bytes 0xFF")
     if case.ref is not None:
         case.ref(A)
     return A
@@ -1057,6 +1061,166 @@ def test_vit_forward_stays_in_its_buffers(B, policy):
     case = make(B)
     case.ref = lambda A: np.testing.assert_array_equal(A["out"].reshape(shape), expect)
     check_case(case)
+
+
+# ================================================================================================================ k-best search
+# vfm_match_ip_topk / vfm_match_ip_topk_prepared (csrc/match_topk.hip).  The state where stale memory would bite: counters | rec_cnt |
+# tau cleared by ONE memset whose length rests on the three arrays being contiguous; fb_list and rec never cleared and trusted only up
+# to the counts; info written by a kernel of its own; both prepared images promised to be left as they were found.
+TOPK_INFO = ("max_records", "fallback", "slices", "reserved")
+EINVAL, EWORKSPACE = -1, -2
+
+
+def _topk_rows(n, m, d, zero_rows=False):
+    from tests import topk_oracle as to
+    q, b = to.gaussian_rows(n, m, d, seed=n + m + d)
+    if zero_rows:
+        q[n // 2] = 0.0
+        b[min(3, m - 1)] = 0.0
+    return q, b
+
+
+def _prepared_image(x, d):
+    """vfm_match_prepare's image of the rows x, written into a guarded buffer of exactly vfm_match_prepared_bytes: its bytes"""
+    lib = _lib().load()
+    rows = x.shape[0]
+    src = GuardedBuffer(x.shape, torch.float32, seed=11)
+    src.set(torch.from_numpy(x))
+    img = GuardedBuffer(lib.vfm_match_prepared_bytes(rows, d), torch.uint8, seed=12).fill_bytes(0)
+    _chk(lib.vfm_match_prepare(src.ptr(), rows, d, img.ptr(), _stream()), "match_prepare")
+    torch.cuda.synchronize()
+    for g in (src, img):
+        chk = g.intact()
+        assert chk, f"vfm_match_prepare rows={rows} d={d}: {chk!r}"
+    return img.body_bytes()
+
+
+def topk_case(form, n, m, d, k, prec=FAST, rows=None, zero_rows=False, want_info=None, big=True):
+    """form "topk": vfm_match_ip_topk; "prepared": vfm_match_ip_topk_prepared on images written beforehand (role IN: unchanged byte
+    for byte).  The reference is tests/topk_oracle.py, bit for bit, and ``info`` as include/vfmreg.h documents it."""
+    from tests import topk_cases as tc
+    from tests import topk_oracle as to
+    lib = _lib().load()
+    q, b = rows if rows is not None else _topk_rows(n, m, d, zero_rows)
+    name = f"{form} n={n} m={m} d={d} k={k} prec={prec}" + (" zero rows" if zero_rows else "")
+    fast = prec == FAST and d in tc.FAST_WIDTHS and m >= 1
+    # info[0], the largest record count, is compared with its documented range below and not between runs
+    bufs = dict(q=Buf(IN, q), b=Buf(IN, b), idx=Buf(OUT, shape=(n, k), dtype=np.int64), sim=Buf(OUT, shape=(n, k), dtype=np.float32),
+                info=Buf(OUT, shape=4, dtype=np.int32, view=lambda res, a: a[1:]))
+    if form == "prepared":
+        bufs["qp"] = Buf(IN, _prepared_image(q, d), poison=(ZERO,))
+        bufs["bp"] = Buf(IN, _prepared_image(b, d), poison=(ZERO,))
+        ws = lib.vfm_match_ip_topk_prepared_workspace_bytes(n, d, k)
+
+        def call(B, W):
+            _chk(lib.vfm_match_ip_topk_prepared(B["q"].ptr(), B["qp"].ptr(), n, B["b"].ptr(), B["bp"].ptr(), m, d, k, B["idx"].ptr(),
+                                                B["sim"].ptr(), B["info"].ptr(), W.ptr(), W.nbytes, _stream()), name)
+    else:
+        ws = lib.vfm_match_ip_topk_workspace_bytes(n, m, d, k, prec)
+
+        def call(B, W):
+            _chk(lib.vfm_match_ip_topk(B["q"].ptr(), n, B["b"].ptr(), m, d, k, prec, B["idx"].ptr(), B["sim"].ptr(), B["info"].ptr(),
+                                       W.ptr(), W.nbytes, _stream()), name)
+    assert ws > 0, name
+
+    def ref(A):
+        info = dict(zip(TOPK_INFO, A["info"].tolist()))
+        print(f"{name}: {info}")
+        want_idx, want_sim = to.topk(q, b, k)
+        np.testing.assert_array_equal(A["idx"], want_idx, err_msg=name)
+        np.testing.assert_array_equal(A["sim"].view(np.uint32), want_sim.view(np.uint32), err_msg=name)
+        if want_info is not None:
+            assert tuple(A["info"].tolist()) == want_info, (name, info)
+        elif fast:   # ordinary rows: the matrix-core pass answered every query from its records
+            assert info["fallback"] == 0 and info["reserved"] == 0 and info["slices"] == tc.max_slices(n, m, d), (name, info)
+            assert min(k, m) <= info["max_records"] <= min(m, tc.RECORD_CAP), (name, info)
+        else:        # a call that ran the all-pairs kernel
+            assert tuple(A["info"].tolist()) == (0, n, 0, 0), (name, info)
+
+    make_big = None
+    if big and fast:   # the larger call that leaves plausible counters, bounds, records and a fallback list behind
+        make_big = lambda: topk_case(form, tc.STALE_N, tc.STALE_M, d, tc.STALE_K, rows=tc.stale_maker(d), big=False)   # noqa: E731
+    return Case(name, bufs, call, ws, ref, make_big)
+
+
+TOPK = [
+    ("topk", dict(n=1, m=1, d=128, k=1)), ("topk", dict(n=33, m=129, d=256, k=5)), ("topk", dict(n=257, m=2049, d=384, k=8)),
+    ("topk", dict(n=129, m=300, d=640, k=8)), ("topk", dict(n=33, m=2049, d=768, k=2)), ("topk", dict(n=257, m=5, d=256, k=8)),
+    ("topk", dict(n=65, m=300, d=128, k=5, zero_rows=True)),
+    ("topk", dict(n=33, m=129, d=33, k=2, prec=EXACT)), ("topk", dict(n=257, m=300, d=128, k=8, prec=EXACT)),
+    ("topk", dict(n=1, m=5, d=1028, k=8, prec=EXACT)),
+    ("topk", dict(n=33, m=300, d=512, k=5, want_info=(0, 33, 0, 0))),      # FAST at a width without a kernel runs EXACT
+    ("topk", dict(n=5, m=0, d=128, k=3, want_info=(0, 0, 0, 0))),          # no map rows: all padding
+    ("prepared", dict(n=1, m=129, d=128, k=1)), ("prepared", dict(n=257, m=2049, d=256, k=8)),
+    ("prepared", dict(n=129, m=300, d=640, k=5)), ("prepared", dict(n=33, m=2049, d=768, k=8)),
+]
+
+
+@pytest.mark.parametrize("form,kw", TOPK, ids=[f"{f}-" + "-".join(f"{k}{v}" for k, v in kw.items()) for f, kw in TOPK])
+def test_topk_stays_in_its_buffers(form, kw):
+    A = check_case(topk_case(form, **kw), ws_ff=True)
+    if kw["m"] == 0:
+        assert (A["idx"] == -1).all() and (A["sim"] == np.finfo(np.float32).min).all()
+
+
+def test_topk_refusals_launch_nothing():
+    """Every refusal of the two entry points returns its documented code and leaves outputs, info, workspace and guards as they were;
+    the size functions return 0 for arguments the calls refuse; an empty query set succeeds and writes nothing."""
+    lib = _lib().load()
+    n, m, d, k = 33, 129, 128, 5
+    q, b = _topk_rows(n, m, d)
+    need = lib.vfm_match_ip_topk_workspace_bytes(n, m, d, k, FAST)
+    need_p = lib.vfm_match_ip_topk_prepared_workspace_bytes(n, d, k)
+    assert need > need_p > 0
+    G = dict(q=GuardedBuffer(q.shape, torch.float32, seed=1), b=GuardedBuffer(b.shape, torch.float32, seed=2),
+             idx=GuardedBuffer((n, 8), torch.int64, seed=3), sim=GuardedBuffer((n, 8), torch.float32, seed=4),
+             info=GuardedBuffer(4, torch.int32, seed=5), ws=GuardedBuffer(need, torch.uint8, seed=6),
+             qp=GuardedBuffer(lib.vfm_match_prepared_bytes(n, d), torch.uint8, seed=7),
+             bp=GuardedBuffer(lib.vfm_match_prepared_bytes(m, d), torch.uint8, seed=8))
+    G["q"].set(torch.from_numpy(q))
+    G["b"].set(torch.from_numpy(b))
+    for name in ("idx", "sim", "info", "ws", "qp", "bp"):
+        G[name].fill_bytes(0xA5)
+    before = {name: g.body_bytes() for name, g in G.items()}
+
+    def plain(k=k, d=d, n=n, idx=G["idx"].ptr(), sim=G["sim"].ptr(), ws=G["ws"].ptr(), ws_bytes=need, prec=FAST):
+        return lib.vfm_match_ip_topk(G["q"].ptr(), n, G["b"].ptr(), m, d, k, prec, idx, sim, G["info"].ptr(), ws, ws_bytes, _stream())
+
+    def prepared(k=k, d=d, n=n, m=m, idx=G["idx"].ptr(), sim=G["sim"].ptr(), ws=G["ws"].ptr(), ws_bytes=need_p, qp=G["qp"].ptr()):
+        return lib.vfm_match_ip_topk_prepared(G["q"].ptr(), qp, n, G["b"].ptr(), G["bp"].ptr(), m, d, k, idx, sim, G["info"].ptr(), ws,
+                                              ws_bytes, _stream())
+
+    calls = [("k = 0", lambda: plain(k=0), EINVAL), ("k = 9", lambda: plain(k=9), EINVAL), ("null idx", lambda: plain(idx=None), EINVAL),
+             ("null sim", lambda: plain(sim=None), EINVAL), ("d = 0", lambda: plain(d=0), EINVAL),
+             ("unknown mode", lambda: plain(prec=7), EINVAL), ("one byte short", lambda: plain(ws_bytes=need - 1), EWORKSPACE),
+             ("null workspace", lambda: plain(ws=None), EWORKSPACE),
+             ("prepared k = 0", lambda: prepared(k=0), EINVAL), ("prepared k = 9", lambda: prepared(k=9), EINVAL),
+             ("prepared null idx", lambda: prepared(idx=None), EINVAL), ("prepared null sim", lambda: prepared(sim=None), EINVAL),
+             ("prepared d = 512", lambda: prepared(d=512), EINVAL), ("prepared m = 0", lambda: prepared(m=0), EINVAL),
+             ("prepared null image", lambda: prepared(qp=None), EINVAL),
+             ("prepared one byte short", lambda: prepared(ws_bytes=need_p - 1), EWORKSPACE),
+             ("prepared null workspace", lambda: prepared(ws=None), EWORKSPACE),
+             ("no queries", lambda: plain(n=0), 0), ("prepared no queries", lambda: prepared(n=0), 0)]
+    for what, fn, code in calls:
+        assert fn() == code, what
+        torch.cuda.synchronize()
+        for name, g in G.items():
+            chk = g.intact()
+            assert chk, f"{what}: {name}: {chk!r}"
+            assert np.array_equal(g.body_bytes(), before[name]), f"{what}: {name} was written"
+    # the size functions: 0 for what the calls refuse
+    for args in ((n, m, d, 0, FAST), (n, m, d, 9, FAST), (n, m, 0, k, FAST), (n, m, d, k, 7), (-1, m, d, k, FAST), (n, -1, d, k, EXACT)):
+        assert lib.vfm_match_ip_topk_workspace_bytes(*args) == 0, args
+    for args in ((n, 512, k), (n, 33, k), (n, d, 0), (n, d, 9), (-1, d, k)):
+        assert lib.vfm_match_ip_topk_prepared_workspace_bytes(*args) == 0, args
+    # ... and after all of them the same buffers still serve a real call
+    _chk(plain(), "match_ip_topk")
+    torch.cuda.synchronize()
+    from tests import topk_oracle as to
+    want_idx, want_sim = to.topk(q, b, k)
+    np.testing.assert_array_equal(G["idx"].numpy().reshape(-1)[:n * k].reshape(n, k), want_idx)
+    np.testing.assert_array_equal(G["sim"].numpy().reshape(-1)[:n * k].reshape(n, k).view(np.uint32), want_sim.view(np.uint32))
+    assert all(g.intact() for g in G.values())
 
 
 # ================================================================================================================ the harness itself

@@ -42,10 +42,13 @@ def rows(n, m, d, seed=0, common=False):
 
 
 # ------------------------------------------------------------------------------------------------- 1. every tiling edge
-# every N of {1, 33, 257}, M of {1, 5, 127, 129, 300, 4097}, d of {128, 384} and k of {1, 2, 5, 8}; M < k among them
+# every N of {1, 33, 257}, M of {1, 5, 127, 129, 300, 4097}, d of {128, 384} and k of {1, 2, 5, 8}; M < k among them; then d = 256
+# (match_topk_coarse_kernel<16, 8>) at every N and k, M of {1, 129, 300, 4097}
 FAST_SHAPES = [(1, 1, 128, 1), (1, 5, 384, 8), (33, 127, 128, 2), (33, 129, 384, 5), (257, 300, 128, 8), (257, 4097, 384, 8),
                (33, 4097, 128, 5), (257, 1, 384, 2), (1, 300, 128, 5), (257, 5, 128, 8), (1, 127, 384, 1), (257, 129, 128, 1),
-               (1, 4097, 128, 2), (33, 300, 384, 2)]
+               (1, 4097, 128, 2), (33, 300, 384, 2),
+               (1, 1, 256, 1), (33, 129, 256, 5), (257, 300, 256, 8), (257, 4097, 256, 8), (33, 4097, 256, 2), (1, 300, 256, 5),
+               (257, 129, 256, 1), (1, 4097, 256, 8)]
 # the same N, M and k at d of {33, 128, 512}; then the two sides of the row norm's paths: d = 1024 is the last width whose sum of
 # squares takes the float4 chunks (all four of a lane in use), d = 1028 the first multiple of 4 that takes the element loop
 EXACT_SHAPES = [(1, 1, 33, 1), (33, 5, 128, 8), (257, 300, 512, 5), (33, 129, 33, 2), (1, 127, 512, 8), (257, 4097, 33, 8),
@@ -56,7 +59,7 @@ EXACT_SHAPES = [(1, 1, 33, 1), (33, 5, 128, 8), (257, 300, 512, 5), (33, 129, 33
 def test_fast_equals_the_oracle_across_the_tiling_edges(n, m, d, k):
     q, b = rows(n, m, d)
     _, _, info = check(q, b, k, FAST)
-    assert info["slices"] >= 1, "FAST at d = 128 / 384 runs the matrix-core pass"
+    assert info["slices"] >= 1, "FAST at d = 128 / 256 / 384 runs the matrix-core pass"
 
 
 @pytest.mark.parametrize("n,m,d,k", EXACT_SHAPES)
@@ -88,7 +91,7 @@ def test_no_map_rows_is_all_padding():
 
 # ------------------------------------------------------------------------------------------------- 2. the fast path answered
 @pytest.mark.parametrize("common", [False, True], ids=["gaussian", "common-component"])
-@pytest.mark.parametrize("d", [128, 384])
+@pytest.mark.parametrize("d", [128, 256, 384])
 def test_matrix_core_path_answers_ordinary_data(d, common):
     """tools/sim_topk_records.py gives at most ~250 records per query on these cases: a query that overflows a list of 1024 here is a
     kernel fault, not bad luck -- and a FAST mode that quietly ran the all-pairs kernel would report every query as a fallback."""
@@ -101,9 +104,9 @@ def test_matrix_core_path_answers_ordinary_data(d, common):
 
 
 # ------------------------------------------------------------------------------------------------- 3. k = 1 is today's search
-def test_k1_equals_the_top1_search():
+def _k1_equals_the_top1_search(d):
     from vfmreg import ops
-    q, b = rows(257, 4097, 384, 2)
+    q, b = rows(257, 4097, d, 2)
     cases = [("gaussian", q, b)]
     rng = np.random.default_rng(3)
     q2, b2 = q.copy(), b.copy()
@@ -118,6 +121,14 @@ def test_k1_equals_the_top1_search():
         np.testing.assert_array_equal(idx[:, 0], i1.cpu().numpy(), err_msg=name)
         np.testing.assert_array_equal(sim[:, 0].view(np.uint32), s1.cpu().numpy().view(np.uint32), err_msg=name)
         check(qq, bb, 5, FAST, msg=name)
+
+
+def test_k1_equals_the_top1_search():
+    _k1_equals_the_top1_search(384)
+
+
+def test_k1_equals_the_top1_search_at_256():
+    _k1_equals_the_top1_search(256)   # (the top-1 search serves 256 columns too: column 0 is its answer)
 
 
 # ------------------------------------------------------------------------------------------------- 4. ties and twins

@@ -156,7 +156,7 @@ def test_fast_equals_exact(d):
 @pytest.mark.parametrize("k", [1, 8])
 @pytest.mark.parametrize("m", [129, 4097])
 @pytest.mark.parametrize("n", [1, 257])
-@pytest.mark.parametrize("d", [128, 384, 768])
+@pytest.mark.parametrize("d", [128, 256, 384, 640, 768])   # ops.MATCH_TOPK_FAST_WIDTHS
 def test_prepared_entry_equals_the_unprepared_call(d, n, m, k):
     from vfmreg import ops
     q, b = rows(n, m, d)
@@ -170,7 +170,7 @@ def test_prepared_entry_equals_the_unprepared_call(d, n, m, k):
     equal(idx.cpu().numpy(), sim.cpu().numpy(), oracle(n, m, d, k), "prepared vs oracle")
 
 
-@pytest.mark.parametrize("d", [384, 768])
+@pytest.mark.parametrize("d", [128, 256, 384, 640, 768])   # ops.MATCH_TOPK_FAST_WIDTHS
 def test_a_prepared_map_is_left_as_it_was(d):
     from vfmreg import ops
     _, b = rows(257, 4097, d)
